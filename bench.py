@@ -11,6 +11,13 @@ written to HBM.  So `--steps 20 --warmup 5` = 20 timed launches after 5 untimed 
 `--steps 20` a single 20-step launch: launch-latency bound, 5 % of the HBM roofline; the kernel needs ~200 us launches to show its
 steady state.)
 
+A plain run does only what the headline needs: it builds the env, settles the clock and warms up, times exactly K launches once (one
+timed region), and prints the compact line; `--dump-outputs DIR` writes what the last timed launch computed (dump_outputs()).  Everything
+else below -- the cold start, the repeated regions and their median, telemetry, the in-run PMC passes, the CPU baseline, the extra legs
+and configurations, and for N > 1 the gather / rccl / config5 legs -- runs with `--full` only, which also writes the full record to the
+side file.  With the same arguments every run steps the same inputs: the actions are seeded, and the envs are reset after the settle
+launches (whose number depends on the clock), so the warm-up and timed launches start from the same state.
+
 Default workload = BASELINE.json configs[2], the config the metric ("batched PMSM") is quoted on: Finite-CC-PMSM-v0 (Finite-B6C +
 dq transform), 16384 envs per GPU, RK4, fp32, default SquaredConstraint(i_sd, i_sq) done mask with in-kernel auto-reset, uniformly
 random discrete actions resident in HBM (synthetic).  tau = 1e-4 as the metric line states (the env's own default is 1e-5; the
@@ -38,7 +45,7 @@ One clock (round 4): `roofline.achieved / frac / launch_ms` are priced with the 
 `value` and `ms_per_step` use -- so value x bytes per env-step == roofline.achieved; the HIP-event mean is `launch_ms_hip_events`.
 Legs whose launches are short (BASELINE config 2: 20 us) time >= 3 ms of launches per region for the same reason.
 
-Robustness to the box (round 3): the timed region is run `--repeats` (3) times back to back and the MEDIAN region is what `value`,
+Robustness to the box (round 3, `--full`): the timed region is run `--repeats` (3) times back to back and the MEDIAN region is what `value`,
 `ms_per_step` and `roofline` report (min / max under `repeats`); core clock, memory clock, socket power and temperature are read from
 the GPU's hwmon files before and after every leg (`telemetry`); `sustained_1s` legs run >= `--sustain-s` seconds of back-to-back
 launches with those sensors sampled every 20 ms -- a slower line can be told from a slower or power-limited box.
@@ -253,10 +260,12 @@ def median_of(ts):
     return sorted(ts, key=lambda t: t.wall)[len(ts) // 2]
 
 
-def measure(torch, dist, env, n_local, steps, warmup, spl, device, world, seed, gather="off", gd=None, settle_ms=0.0, repeats=1):
+def measure(torch, dist, env, n_local, steps, warmup, spl, device, world, seed, gather="off", gd=None, settle_ms=0.0, repeats=1, outputs=None):
     """`warmup` untimed + `steps` timed launches of `spl` control steps each, after `settle_ms` of the same launches (clock governor, see
     module docstring).  gather: off | chunk | step.  repeats > 1: the timed region (exactly `steps` launches between barrier +
-    synchronize on both sides) is run that many times back to back; returns the list of Timed (repeats == 1: the one Timed)."""
+    synchronize on both sides) is run that many times back to back; returns the list of Timed (repeats == 1: the one Timed).
+    The envs are reset once more after the settle launches, whose number depends on the clock: the warm-up and timed launches then start
+    from the same state in every run.  outputs: a dict that receives the `obs` / `done` tensors the last launch wrote."""
     ps = env.physical_system
     n_act_bufs = max(1, min(4, steps))
     acts = make_actions(torch, ps, spl * n_act_bufs, n_local, device, seed)
@@ -299,6 +308,7 @@ def measure(torch, dist, env, n_local, steps, warmup, spl, device, world, seed, 
         for j in range(8):
             bound[j % n_act_bufs]()
         torch.cuda.synchronize()
+    env.reset()
     for i in range(warmup):
         launch(i)
     out = []
@@ -329,6 +339,8 @@ def measure(torch, dist, env, n_local, steps, warmup, spl, device, world, seed, 
         out.append(Timed(dt, e0.elapsed_time(e1) / steps))
     if gather != "step":
         assert torch.isfinite(obs).all()
+    if outputs is not None:
+        outputs.update(obs=obs, done=done)
     return out if repeats > 1 else out[0]
 
 
@@ -595,15 +607,20 @@ def worker(args, rank, world, local_rank, backend):
     K, W, spl = args.steps, args.warmup, args.steps_per_launch
 
     S = args.settle_ms
-    tele = Telemetry(dev_index)
+    full = args.full
+    tele = Telemetry(dev_index) if full else None
     env = make_env(ga, w, n_local, dev_index)  # the solver make(env_id) hands out (Finite-CC-PMSM-v0: plain RK4; --workload scim: RK4 + kink correction)
-    t_cold = measure(torch, dist, env, n_local, K, W, spl, device, world, seed=1234 + rank) if S > 0 else None  # straight from idle
-    tele_before = tele.sample()
-    reps = measure(torch, dist, env, n_local, K, W, spl, device, world, seed=1234 + rank, settle_ms=S, repeats=max(1, args.repeats))
+    t_cold = measure(torch, dist, env, n_local, K, W, spl, device, world, seed=1234 + rank) if S > 0 and full else None  # straight from idle
+    tele_before = tele.sample() if full else None
+    last = {}
+    reps = measure(torch, dist, env, n_local, K, W, spl, device, world, seed=1234 + rank, settle_ms=S, repeats=args.repeats, outputs=last)
     reps = reps if isinstance(reps, list) else [reps]
-    tele_after = tele.sample()
+    tele_after = tele.sample() if full else None
     t = median_of(reps)
     kernel_desc = env.physical_system.last_launch()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["obs"], last["done"])
+    del last
 
     def rl(tm, traffic=None, source=None):
         return roofline_of(w, n_local, spl, tm.wall / K * 1e3, kernel_desc, args.workload, traffic=traffic, traffic_source=source, events_ms=tm.launch_ms)
@@ -630,12 +647,13 @@ def worker(args, rank, world, local_rank, backend):
                        "parallelism": f"env-sharded x{world}, no data-path collective", "world_size": world,
                        "backend": (backend if dist_on else None), "oversubscribed": bool(args.oversubscribe and world > ndev)},
             "roofline": rl(t),
-            "repeats": {"n": len(reps), "note": f"the timed region ({K} launches) run {len(reps)} times back to back; value / ms_per_step / roofline = the MEDIAN region",
-                        "values": [n_total * spl * K / r.wall for r in reps], "launch_ms": [r.wall / K * 1e3 for r in reps],
-                        "launch_ms_hip_events": [r.launch_ms for r in reps],
-                        "roofline_frac_min": min(rl(r)["frac"] for r in reps), "roofline_frac_max": max(rl(r)["frac"] for r in reps)},
-            "telemetry": dict(tele.describe(), before=tele_before, after=tele_after),
         }
+        if full:
+            out["repeats"] = {"n": len(reps), "note": f"the timed region ({K} launches) run {len(reps)} times back to back; value / ms_per_step / roofline = the MEDIAN region",
+                              "values": [n_total * spl * K / r.wall for r in reps], "launch_ms": [r.wall / K * 1e3 for r in reps],
+                              "launch_ms_hip_events": [r.launch_ms for r in reps],
+                              "roofline_frac_min": min(rl(r)["frac"] for r in reps), "roofline_frac_max": max(rl(r)["frac"] for r in reps)}
+            out["telemetry"] = dict(tele.describe(), before=tele_before, after=tele_after)
         if t_cold is not None:
             out["cold_start"] = {"value": n_total * spl * K / t_cold.wall, "unit": "env-steps/s", "ms_per_step": t_cold.wall / K * 1e3,
                                  "roofline_frac": rl(t_cold)["frac"],
@@ -652,7 +670,7 @@ def worker(args, rank, world, local_rank, backend):
 
             return {"error": repr(e), "leg": name, "trace": traceback.format_exc(limit=4)}
 
-    if args.workload == "pmsm" and args.envs_per_gpu is None and (args.config5 == "on" or (args.config5 == "auto" and world > 1)):
+    if full and args.workload == "pmsm" and args.envs_per_gpu is None and (args.config5 == "on" or (args.config5 == "auto" and world > 1)):
         def c5():
             env_s = make_env(ga, w, 32768, dev_index)
             try:
@@ -669,8 +687,8 @@ def worker(args, rank, world, local_rank, backend):
             out["config5"] = c5r
 
     gmode = args.gather
-    if gmode == "auto":  # the batched-return path is part of every multi-GPU line (bounded: a few launches), off on a lone GPU
-        gmode = "chunk" if world > 1 else "off"
+    if gmode == "auto":  # the batched-return path is part of every multi-GPU --full line (bounded: a few launches), off on a lone GPU
+        gmode = "chunk" if world > 1 and full else "off"
     if gmode != "off":
         if not dist_on:
             raise SystemExit("bench.py: --gather needs a process group: run under torchrun, with --gpus N > 1, or add --force-dist")
@@ -696,20 +714,20 @@ def worker(args, rank, world, local_rank, backend):
     env.close()
 
     if rank == 0:
-        if not args.no_pmc and world == 1:
+        if full and not args.no_pmc and world == 1:
             tr, note = guarded_pair(lambda: measure_traffic_pmc(args, args.workload, n_local))
             if tr is not None:
                 out["roofline"] = rl(t, traffic=tr, source=note)
             else:
                 out["roofline"]["traffic_source"] = f"{out['roofline'].get('traffic_source')}; in-run PMC pass unavailable: {note}"
-        if not args.no_extras and world == 1:
+        if full and not args.no_extras and world == 1:
             try:
                 extras(torch, dist, ga, args, w, n_local, spl, device, dev_index, out, tele)
             except Exception as e:  # an informational leg must not cost the headline
                 import traceback
 
                 out["extras_error"] = {"error": repr(e), "trace": traceback.format_exc(limit=6)}
-        elif not args.no_extras:
+        elif full and not args.no_extras:
             # N > 1: the CPU figure does not depend on the number of GPUs -- the same port on rank 0's host cores, on a shorter sample (the
             # other ranks wait at the shutdown barrier meanwhile; round 4 left this field None on every multi-GPU line)
             cb = guarded("cpu_baseline", lambda: cpu_baseline(w, budget_s=4.0))
@@ -853,6 +871,8 @@ def emit(out, args, defer=False):
     """Full record -> the side file (`--extras-file`, default bench_extras.json beside this script; a copy under gpurun_out/ when that
     directory exists, so that a gpurun call brings it home); ONE compact line -> stdout, last (defer: returned, the caller prints it
     after the process group's teardown)."""
+    if not (args.full or args.extras_file):  # a plain run writes the line alone (no side file unless one is named)
+        return print_line(compact_line(out), defer)
     path = args.extras_file or os.path.join(REPO, "bench_extras.json")
     written = None
     for p in [path] + ([os.path.join(REPO, "gpurun_out", os.path.basename(path))] if os.path.isdir(os.path.join(REPO, "gpurun_out")) else []):
@@ -862,12 +882,44 @@ def emit(out, args, defer=False):
             written = written or os.path.relpath(p, REPO)
         except OSError as e:  # a read-only checkout: the line still goes out
             print(f"bench.py: could not write {p}: {e!r}", file=sys.stderr)
-    line = compact_line(out, written)
+    return print_line(compact_line(out, written), defer)
+
+
+def print_line(line, defer):
+    """the line -> stdout, last, behind a flush of the C streams (defer: only returned, the caller prints it)"""
     if not defer:
         flush_c_streams()
         sys.stdout.flush()
         print(line, flush=True)
     return line
+
+
+def dump_outputs(d, obs, done, seed=0, limit=64 << 20):
+    """--dump-outputs DIR: what the timed path computed in its last launch, as a caller of that path receives it (obs [K, N, S_out],
+    done [K, N]), as float32 .npy files of at most `limit` bytes in all:
+        obs_last.npy, done_last.npy          the last control step of every env ([N, S_out], [N]); beyond 16 MB a seeded sample of envs
+        obs_sample.npy, done_sample.npy      all K control steps of a seeded sample of at most 512 envs ([K, n, S_out], [K, n])
+    The samples are fixed by `seed` and the shapes alone, so two builds run with the same arguments write comparable files."""
+    import numpy as np
+    import torch
+
+    K, n, s = obs.shape
+    rng = np.random.default_rng(seed)
+    row = (s + 1) * 4
+    n_last = min(n, (16 << 20) // row)
+    last = np.sort(rng.choice(n, n_last, replace=False)) if n_last < n else np.arange(n)
+    n_smp = max(1, min(n, 512, (40 << 20) // (K * row)))
+    smp = np.sort(rng.choice(n, n_smp, replace=False))
+    il, ism = (torch.as_tensor(i, device=obs.device) for i in (last, smp))
+    arrays = {"obs_last": obs[-1].index_select(0, il), "done_last": done[-1].index_select(0, il),
+              "obs_sample": obs.index_select(1, ism), "done_sample": done.index_select(1, ism)}
+    arrays = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (> {limit}): use fewer --steps-per-launch")
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
 
 
 def guarded_pair(fn):
@@ -1127,18 +1179,30 @@ def main():
                     help="allow more ranks than visible GPUs (ranks share GPUs, gloo control plane): functional check only")
     ap.add_argument("--settle-ms", type=float, default=60.0,
                     help="untimed launches of the same workload for this long before each leg's warm-up (clock governor; 0 = off)")
-    ap.add_argument("--no-extras", action="store_true", help="skip cpu_baseline / single_step / configs / at_scale legs")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps launches each; the median is reported, min / max beside it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run everything else the benchmark measures: cold start, repeats, telemetry, the in-run PMC "
+                         "passes, cpu_baseline / single_step / configs / at_scale legs, and for N > 1 the gather, rccl and config5 legs; "
+                         "writes the full record to the side file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (observation rows, done flags; seeded samples beyond "
+                         "16 MB) to DIR/<name>.npy as float32")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip cpu_baseline / single_step / configs / at_scale legs")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps launches each; the median is reported, min / max "
+                                                              "beside it (default: 1, with --full 3)")
     ap.add_argument("--sustain-s", type=float, default=1.0, help="length of the sustained legs (back-to-back launches, clocks / power sampled)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not measure roofline.traffic with rocprofv3 --pmc child runs (N = 1 only)")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: do not measure roofline.traffic with rocprofv3 --pmc child runs (N = 1 only)")
     ap.add_argument("--config5", choices=["auto", "on", "off"], default="auto",
-                    help="also measure BASELINE config 5's shard (32768 envs per GPU) on every rank and report it as `config5` (auto: at --gpus 8)")
+                    help="with --full: also measure BASELINE config 5's shard (32768 envs per GPU) on every rank and report it as `config5` "
+                         "(auto: at --gpus N > 1)")
     ap.add_argument("--extras-file", default=None, help="where the full record goes (default: bench_extras.json beside this script); stdout carries "
                                                          "one compact line (< 6 KB)")
     ap.add_argument("--dist-timeout", type=float, default=300.0, help="torch.distributed timeout in seconds (rendezvous, barriers, collectives)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0 or args.steps_per_launch < 2 or args.settle_ms < 0:
         raise SystemExit("bench.py: --steps >= 1, --warmup >= 0, --steps-per-launch >= 2, --settle-ms >= 0")
+    if not args.full and (args.gather not in ("auto", "off") or args.config5 == "on"):
+        raise SystemExit("bench.py: --gather chunk | step | both and --config5 on are legs of --full")
+    args.repeats = max(1, args.repeats if args.repeats is not None else (3 if args.full else 1))
 
     world_env = os.environ.get("WORLD_SIZE")
     backend = "gloo" if args.oversubscribe else "nccl"

@@ -2728,7 +2728,7 @@ def test_bench_multi_gpu_code_path_through_rccl_in_a_world_of_one():
     import tempfile
 
     side = os.path.join(tempfile.mkdtemp(prefix="gemx_bench_"), "extras.json")
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--gather", "chunk", "--config5", "on",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--gather", "chunk", "--config5", "on",
            "--no-extras", "--no-pmc", "--settle-ms", "5", "--repeats", "1", "--steps-per-launch", "200", "--extras-file", side]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -2748,6 +2748,42 @@ def test_bench_multi_gpu_code_path_through_rccl_in_a_world_of_one():
     assert rc["bytes_per_rank"] == 16384 * 200 * 57 and rc["GB_per_s"] > 0 and rc["ms"] > 0
     assert line["gather"]["chunk"]["value"] > 0 and "error" not in line["config5"] and line["config5"]["envs_per_gpu"] == 32768
     assert line["overrides"] == {k: v for k, v in os.environ.items() if k.startswith("GEMX_") and k != "GEMX_COVERAGE_FILE"}
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_the_same_outputs_every_time():
+    """A plain `bench.py` run (no --full) times its K launches once, prints the line with the contract's keys, writes no side file, and
+    `--dump-outputs DIR` writes the last timed launch's outputs as float32 .npy files (< 64 MB) -- bit for bit the same in two runs with
+    the same arguments (seeded actions, envs reset after the clock-bound settle launches), and equal to the launch's own rows."""
+    import json
+    import subprocess
+    import sys
+    import tempfile
+
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    tmp = tempfile.mkdtemp(prefix="gemx_dump_")
+    dumps = []
+    for i in range(2):
+        d = os.path.join(tmp, str(i))
+        cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--steps-per-launch", "200",
+               "--dump-outputs", d]
+        r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=140, cwd=tmp)
+        assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+        line = json.loads(r.stdout.rstrip("\n").splitlines()[-1])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in line, k
+        assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert "extras_file" not in line and "legs" not in line and "cpu_baseline" not in line
+        files = sorted(os.listdir(d))
+        assert files == ["done_last.npy", "done_sample.npy", "obs_last.npy", "obs_sample.npy"], files
+        arrs = {f: np.load(os.path.join(d, f)) for f in files}
+        assert all(a.dtype == np.float32 for a in arrs.values()) and sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert arrs["obs_last.npy"].shape == (16384, 14) and arrs["obs_sample.npy"].shape == (200, 512, 14)
+        assert np.isfinite(arrs["obs_sample.npy"]).all() and set(np.unique(arrs["done_last.npy"])) <= {0.0, 1.0}
+        dumps.append(arrs)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_rate_limiter_closed_loop_calibrates_and_never_changes_results(monkeypatch):
@@ -2822,7 +2858,7 @@ def test_two_ranks_on_two_gpus_through_rccl():
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-extras", "--no-pmc",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-extras", "--no-pmc",
            "--settle-ms", "5", "--repeats", "1", "--steps-per-launch", "200"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=840)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

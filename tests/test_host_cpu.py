@@ -659,6 +659,9 @@ def test_bench_cli_contract_without_a_gpu():
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "0"], capture_output=True, text=True, env=env)
     assert r.returncode != 0 and "--steps >= 1" in r.stderr
+    for extra in (["--gather", "chunk"], ["--config5", "on"]):  # the optional legs belong to --full: a plain run refuses them
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2"] + extra, capture_output=True, text=True, env=env)
+        assert r.returncode != 0 and "legs of --full" in r.stderr, extra
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"], capture_output=True, text=True,
                        env=dict(env, WORLD_SIZE="4", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr

@@ -11,7 +11,7 @@ rm -f $OUT/${TAG}_cov_*.txt
 cd $R
 GEMX_COVERAGE_FILE=$OUT/${TAG}_cov_tests.txt timeout 2400 python -m pytest tests -m gpu -q -n 4 > $OUT/${TAG}_gpu_tests_full.txt 2>&1
 tail -15 $OUT/${TAG}_gpu_tests_full.txt > $OUT/${TAG}_gpu_tests.txt
-GEMX_COVERAGE_FILE=$OUT/${TAG}_cov_bench.txt timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench.log 2>&1
+GEMX_COVERAGE_FILE=$OUT/${TAG}_cov_bench.txt timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench.log 2>&1
 tail -1 $OUT/${TAG}_bench.log > $OUT/${TAG}_bench_line.json
 cp bench_extras.json $OUT/${TAG}_bench_extras.json 2>/dev/null
 GEMX_COVERAGE_FILE=$OUT/${TAG}_cov_smoke.txt timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.txt 2>&1

@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$R/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $OUT/${TAG}_bench.log 2>&1   # exactly what the driver runs (HBM traffic measured in-run by its own --pmc child passes)
+python $R/bench.py --full > $OUT/${TAG}_bench.log 2>&1   # every leg of the benchmark (HBM traffic measured in-run by its own --pmc child passes)
 tail -1 $OUT/${TAG}_bench.log > $OUT/${TAG}_bench.json          # the compact stdout line (round 6: < 6 KB, printed last)
 cp $R/bench_extras.json $OUT/${TAG}_bench_extras.json 2>/dev/null  # ... and the full record beside it
 # (the runs under rocprofv3 below pass --no-pmc: no profiler inside the profiler)
@@ -58,4 +58,4 @@ python tools/bench_matrix.py --solver default --chunks 4 --half-actions --only "
 # (round 5: both scripts exit non-zero on any failed comparison, and the collection records it -- a FAIL cell used to be swallowed)
 python tests/parity_report.py > $OUT/${TAG}_parity.md 2>&1; echo "parity_report.py exit status $?" >> $OUT/${TAG}_gpu_tests.txt
 python tests/solver_scan.py > $OUT/${TAG}_solver_scan.md 2>/dev/null; echo "solver_scan.py exit status $?" >> $OUT/${TAG}_gpu_tests.txt
-python bench.py --gpus 2 --oversubscribe --gather chunk --steps 5 --warmup 2 --no-extras --no-pmc 2>&1 | tail -1 > $OUT/${TAG}_bench_gpus2_oversubscribe.json
+python bench.py --gpus 2 --oversubscribe --full --gather chunk --steps 5 --warmup 2 --no-extras --no-pmc 2>&1 | tail -1 > $OUT/${TAG}_bench_gpus2_oversubscribe.json

@@ -6,10 +6,10 @@ symbol's template arguments (gemx_capi.hip: gemx_cov_note -- the stepping kernel
 small kernels of libgemx.so by name).  This tool diffs the union of such files against the kernel symbols of the built libraries
 (gfx950 code objects of gym_electric_motor_amd/libgemx*.so) and prints the markdown report:
 
-    GEMX_COVERAGE_FILE=$PWD/gpurun_out/cov_tests.txt python -m pytest tests -m gpu -q
-    GEMX_COVERAGE_FILE=$PWD/gpurun_out/cov_bench.txt python bench.py
-    GEMX_COVERAGE_FILE=$PWD/gpurun_out/cov_matrix.txt python tools/bench_matrix.py ...
-    python tools/instantiation_coverage.py gpurun_out/cov_*.txt > profiles/r06_instantiation_coverage.md     (exit status 1 if a kernel is unreached)
+    GEMX_COVERAGE_FILE=$OUT/cov_tests.txt python -m pytest tests -m gpu -q
+    GEMX_COVERAGE_FILE=$OUT/cov_bench.txt python bench.py --full
+    GEMX_COVERAGE_FILE=$OUT/cov_matrix.txt python tools/bench_matrix.py ...
+    python tools/instantiation_coverage.py $OUT/cov_*.txt > profiles/r06_instantiation_coverage.md     (exit status 1 if a kernel is unreached)
 """
 import glob
 import importlib.util
