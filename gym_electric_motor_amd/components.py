@@ -430,7 +430,8 @@ class _ThreePhaseMotor(_ElectricMotor):
             return out
 
         self._update_limits(derive(self._limits), derive(self._nominal_values))
-        self._update_limits({"torque": self._torque_limit()})
+        # (a torque limit the user set is kept, so the derived one -- which need not exist, see PermanentMagnetSynchronousMotor -- is not asked for)
+        self._update_limits({} if self._limits.get("torque") else {"torque": self._torque_limit()})
 
 
 def _max_torque_d_current(flux, delta_l, i_max, root):
@@ -482,6 +483,10 @@ class PermanentMagnetSynchronousMotor(_ThreePhaseMotor):
             return self.torque([0, self._limits["i_sq"], 0])
         i_n = self._nominal_values["i"]
         i_d = _max_torque_d_current(mp["psi_p"], delta_l, i_n, root=1.0 if delta_l < 0 else -1.0)
+        if abs(i_d) > i_n:  # (the reference's torque limit is NaN here: np.sqrt of a negative number)
+            raise ValueError(f"no real maximum-torque operating point for l_d > l_q at these psi_p / nominal current: the stationary point "
+                             f"i_d = {i_d:.6g} A lies outside the nominal current circle |i| = {i_n:.6g} A (psi_p = {mp['psi_p']:g} Wb, "
+                             f"l_d - l_q = {delta_l:g} H); pass limit_values / nominal_values with an explicit torque")
         return self.torque([i_d, math.sqrt(i_n * i_n - i_d * i_d), 0])
 
     def torque_coefficients(self):

@@ -264,14 +264,14 @@ template <class R> static void fill_params(const gemx_handle &h, const double *m
     P.adaptive = (c.solver_flags & GEMX_SOLVER_ADAPTIVE) ? 1 : 0;
     P.rtol = (R)(c.solver_rtol > 0 ? c.solver_rtol : 1e-6);
     P.atol = (R)(c.solver_atol > 0 ? c.solver_atol : 1e-9);
-    P.atol_w = (R)(c.solver_atol_omega > 0 ? c.solver_atol_omega : (double)P.atol * c.limits[0]);  // (omega is state 0 and observation 0 of every system)
+    P.atol_w = (R)(c.solver_atol_omega > 0 ? c.solver_atol_omega : (double)P.atol * fabs(c.limits[0]));  // (omega is state 0 and observation 0 of every system)
     P.errw = nullptr;  // (set per launch: launch_advance_t)
     // (round 6: the error-controlled solver honours GEMX_SOLVER_SPLIT_KINKS -- every attempt on the smooth model system, dp5_adaptive)
     P.auto_reset = c.auto_reset;
     P.obs_layout = c.obs_layout;
     P.dc_thr[0] = P.dc_thr[1] = (R)INFINITY;
     if (!h.has_angle)
-        for (int cidx = 0; cidx < h.nd - 1 && cidx < 2; ++cidx) P.dc_thr[cidx] = viol_threshold<R>(P.inv_lim[2 + cidx]);
+        for (int cidx = 0; cidx < h.nd - 1 && cidx < 2; ++cidx) P.dc_thr[cidx] = viol_threshold<R>(fabs(P.inv_lim[2 + cidx]));
     // the env's default constraint gets the 3-instruction fast path (Stepper::default_done)
     const bool is_dc = !h.has_angle;
     const bool two_currents = c.system_kind == GEMX_SYS_DC_SHUNT || c.system_kind == GEMX_SYS_DC_EXTEX;
@@ -645,7 +645,9 @@ int gemx_create(const gemx_config *cfg, int64_t n_envs, int device, gemx_handle 
         h->conv_unit = c == GEMX_CONV_CONT_B6 ? CONV_CONT_B6_DQ : CONV_CONT_B6_4QC_DQ;
     }
     for (int i = 0; i < h->nout; ++i)
-        if (!(cfg->limits[i] > 0) || !std::isfinite(cfg->limits[i])) { delete h; return fail(GEMX_ERR_ARG, "limits[%d] must be positive and finite", i); }
+        // (any sign: the reference normalises by the signed limit -- a PMSM with l_d > l_q has a negative torque limit,
+        // permanent_magnet_synchronous_motor.py:121-132 --; every constraint path compares magnitudes, |x / limit|)
+        if (!(cfg->limits[i] != 0) || !std::isfinite(cfg->limits[i])) { delete h; return fail(GEMX_ERR_ARG, "limits[%d] must be non-zero and finite", i); }
     if ((cfg->limit_mask | cfg->squared_mask) >> h->nout) { delete h; return fail(GEMX_ERR_ARG, "constraint mask has bits beyond S_out=%d", h->nout); }
 
     double m[20] = {0}, pole = 0;

@@ -102,9 +102,9 @@ template <class R> struct DevParams {
     // rounding is monotonic -- the same done / reset decisions bit for bit, without the multiply on the step-to-step chain
     R dc_thr[2];
 };
-// smallest t >= 0 with fl(t * c) > 1 (c > 0): see DevParams::dc_thr
+// smallest t >= 0 with fl(t * c) > 1 (c > 0; the caller passes |1 / limit|, the limit may be negative): see DevParams::dc_thr
 template <class R> inline R viol_threshold(R c) {
-    if (!(c > R(0)) || !std::isfinite(c)) return (R)INFINITY;  // (no finite current violates such a limit; gemx_create rejects it anyway)
+    if (!(c > R(0)) || !std::isfinite(c)) return (R)INFINITY;  // (no finite current violates such a limit; gemx_create rejects a zero one)
     volatile R t = R(1) / c, p = t * c;
     while (p > R(1)) { t = std::nextafter((R)t, R(0)); p = t * c; }
     while (!(p > R(1))) { t = std::nextafter((R)t, (R)INFINITY); p = t * c; }

@@ -153,10 +153,44 @@ class _StepRecorder:
         pass
 
 
+def torque_kat(env, n=8, seed=0):
+    """The reference motor's torque(state) at `n` seeded motor-state vectors, scaled by the motor's current limits (and, for the
+    induction machines, by the flux the nominal magnetising current gives).  Doubly fed machines: also the system's rotor-current
+    reconstruction (physical_systems.py:954-966) at the same states."""
+    psys = env.physical_system.unwrapped
+    motor = psys.electrical_motor
+    rng = np.random.default_rng(seed)
+    n_motor = len(psys._motor_ode_idx)
+    lim = motor.limits
+    scale = np.ones(n_motor)
+    names = [c for c in motor.CURRENTS] + [f for f in getattr(motor, "FLUXES", [])]
+    for j, c in enumerate(names[: n_motor]):
+        if c in lim:
+            scale[j] = lim[c]
+        elif c.startswith("i_s"):
+            scale[j] = lim["i_sd"]
+        elif c.startswith("psi"):
+            scale[j] = motor.motor_parameter["l_m"] * lim["i_sd"]
+    states = rng.uniform(-1.0, 1.0, (n, n_motor)) * scale
+    if hasattr(motor, "EPSILON_IDX") or "epsilon" in psys.state_names:
+        states[:, -1] = rng.uniform(-np.pi, np.pi, n)
+    out = dict(states=states.tolist(), torque=[float(motor.torque(s)) for s in states])
+    if hasattr(psys, "calculate_rotor_current"):
+        full = np.zeros((n, len(psys._ode_solver.y) if psys._ode_solver.y is not None else n_motor + 1))
+        rc = []
+        for k in range(n):
+            full[k, psys._motor_ode_idx] = states[k]
+            rc.append([float(x) for x in psys.calculate_rotor_current(full[k])])
+        out["rotor_current"] = rc
+    return out
+
+
 def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1, action_frame="abc", dead_time_steps=0,
-             record_reward=False, dead_time_reset_action=None, **make_kwargs):
+             record_reward=False, dead_time_reset_action=None, record_overrides=False, **make_kwargs):
     """action_frame: 'abc' | 'dq' (system.control_space = 'dq') | 'dq_processor' (DqToAbcActionProcessor wrapper);
-    dead_time_steps > 0: DeadTimeProcessor(steps) wrapped INSIDE the dq processor, as the reference's processors expect."""
+    dead_time_steps > 0: DeadTimeProcessor(steps) wrapped INSIDE the dq processor, as the reference's processors expect.
+    record_overrides: store the make-kwargs `motor`, `supply`, `load` (dicts) and `tau` exactly as passed in meta["overrides"], and the
+    motor's torque known-answer table in meta["torque_kat"] (the `params` group)."""
     from gym_electric_motor.physical_system_wrappers import DeadTimeProcessor, DqToAbcActionProcessor
 
     kw = dict(make_kwargs)
@@ -208,6 +242,11 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
                 dead_time_steps=int(dead_time_steps))
     if dead_time_reset_action is not None:
         meta["dead_time_reset_action"] = [float(x) for x in dead_time_reset_action]
+    if record_overrides:
+        ov = {k: make_kwargs[k] for k in ("motor", "supply", "load", "tau") if k in make_kwargs}
+        assert all(isinstance(v, (dict, float)) for v in ov.values()), ov
+        meta["overrides"] = json.loads(json.dumps(ov))
+        meta["torque_kat"] = torque_kat(env, seed=seed)
     idx = np.arange(K)
     keep = idx[(idx % every == every - 1)] if every > 1 else idx
     extra = {}
@@ -391,6 +430,8 @@ def main(only=None):
         main_r02()
     if not only or "defaults" in only:
         main_defaults()
+    if not only or "params" in only:
+        main_params()
 
 
 ALL_ENV_IDS = [f"{a}-{c}-{m}-v0" for m in ("PermExDc", "SeriesDc", "ShuntDc", "ExtExDc", "PMSM", "SynRM", "SCIM", "EESM", "DFIM")
@@ -618,24 +659,28 @@ INIT_CASES = {
 INIT_CASES_R04 = ("scim_sc_uniform", "scim_cc_uniform", "scim_cc_negspeed_uniform", "dfim_cc_negspeed_interval_uniform")
 
 
-def init_samples(n=4000, only=None):
+def init_samples(n=4000, only=None, cases=None, fname="init_samples.npz", n_obs=None):
     """random initialisers.  The reference's numpy streams cannot be reproduced on a device, so the fixture holds
     SAMPLES of the initial ODE state the reference draws (physical_system.reset() n times) for distributional tests.
-    only: regenerate just these cases and keep the file's other entries (round 4 added the induction machines this way)."""
-    path = os.path.join(OUT, "init_samples.npz")
+    only: regenerate just these cases and keep the file's other entries (round 4 added the induction machines this way).
+    cases: {name: (env_id, motor_initializer, load_initializer[, load overrides[, motor overrides]])}, default INIT_CASES.
+    n_obs: keep the observations of the first n_obs resets only (the state -> observation map needs a few; the file stays small)."""
+    path = os.path.join(OUT, fname)
     out = {}
     if only is not None and os.path.exists(path):
         old = np.load(path)
         out = {k: old[k] for k in old.files}
-    for name, case in INIT_CASES.items():
+    for name, case in (INIT_CASES if cases is None else cases).items():
         if only is not None and name not in only:
             continue
         env_id, mi, li = case[:3]
         kw = dict(motor=dict(motor_initializer=mi))
         if li is not None:
             kw["load"] = dict(load_initializer=li)
-        if len(case) > 3:
+        if len(case) > 3 and case[3]:
             kw["load"] = dict(kw.get("load", {}), **case[3])
+        if len(case) > 4:
+            kw["motor"] = dict(kw["motor"], **case[4])
         np.random.seed(4021)  # InductionMotor._update_initial_limits draws its field angle from the GLOBAL numpy stream
         env = gem.make(env_id, **kw)
         env.reset(seed=123)
@@ -646,8 +691,11 @@ def init_samples(n=4000, only=None):
             ys.append(np.array(psys._ode_solver.y, dtype=float))
             obs.append(np.array(o, dtype=float))
         out[name + "_y"] = np.asarray(ys)
-        out[name + "_obs"] = np.asarray(obs)
-        out[name + "_meta"] = np.array(json.dumps(dict(describe(env), env_id=env_id, motor_initializer=mi, load_initializer=li)))
+        out[name + "_obs"] = np.asarray(obs)[:n_obs]
+        m = dict(describe(env), env_id=env_id, motor_initializer=mi, load_initializer=li)
+        if len(case) > 3:  # (the make-kwargs beside the initialisers, exactly as passed: motor parameters, load)
+            m["overrides"] = dict(load=dict(case[3] or {}), motor=dict(case[4] if len(case) > 4 else {}))
+        out[name + "_meta"] = np.array(json.dumps(m))
         print(f"init samples {name}: y mean {np.asarray(ys).mean(axis=0).round(3)} min {np.asarray(ys).min(axis=0).round(3)} max {np.asarray(ys).max(axis=0).round(3)}")
     np.savez_compressed(path, **out)
 
@@ -707,6 +755,95 @@ def main_supply():
     run_case("rc_eesm_cont_epi_held_euler", "Cont-CC-EESM-v0", "euler", K, 1508, "held", True, "box4", supply=rc(300.0))
     run_case("rc_dfim_fin_free_uniform_euler", "Finite-CC-DFIM-v0", "euler", K, 1509, "uniform", False, "mdisc88", supply=rc(420.0, 2.0))
     run_case("rc_series_cont_sc_free_held_euler", "Cont-SC-SeriesDc-v0", "euler", K, 1510, "held", False, "box1", supply=rc(60.0, 0.05))
+
+
+# Non-default motor parameter sets, one per motor class, chosen to break every coincidence of the reference's defaults: other pole pair
+# numbers, l_sigs != l_sigr for the induction machines, l_d > l_q (reversed saliency) and l_d == l_q for the PMSM, other DC resistances
+PARAM_SETS = dict(
+    permexdc=dict(r_a=0.05, l_a=4e-5, psi_e=0.3, j_rotor=0.01),
+    series=dict(r_a=0.03, l_a=3e-5, l_e=8e-3, l_e_prime=3e-3, j_rotor=4e-3, r_e=0.02),
+    shunt=dict(r_a=0.03, l_a=3e-5, l_e=8e-3, l_e_prime=3e-3, j_rotor=4e-3, r_e=0.9),
+    extex=dict(r_a=0.03, l_a=3e-5, l_e=8e-3, l_e_prime=3e-3, j_rotor=4e-3, r_e=0.3),
+    pmsm=dict(p=5, l_d=0.5e-3, l_q=0.9e-3, psi_p=0.1, r_s=0.04, j_rotor=0.01),
+    pmsm_nonsalient=dict(p=5, l_d=0.7e-3, l_q=0.7e-3, psi_p=0.1, r_s=0.04, j_rotor=0.01),
+    pmsm_reversed=dict(p=5, l_d=0.9e-3, l_q=0.6e-3, psi_p=0.02, r_s=0.04, j_rotor=0.01),
+    synrm=dict(p=2, l_d=20e-3, l_q=6e-3, r_s=0.9, j_rotor=2e-3),
+    eesm=dict(p=2, l_d=2.1e-3, l_q=0.9e-3, l_m=1.9e-3, l_e=2.3e-3, r_s=0.02, r_e=9e-3, k=50, j_rotor=0.2),
+    scim=dict(p=3, l_m=0.12, l_sigs=4e-3, l_sigr=9e-3, r_s=2.0, r_r=1.9, j_rotor=2e-3),
+    dfim=dict(p=3, l_m=0.25, l_sigs=20e-3, l_sigr=35e-3, r_s=4.0, r_r=2.5, j_rotor=0.01),
+)
+# every speed-control run: a PolynomialStaticLoad with the quadratic term on (c != 0) and a constant term `a` that puts a kink band
+# (|omega| < a tau_decay / J) on the way through zero speed
+# (with c large enough that switching the term off moves omega by > 1 % on a random action stream: tests/test_gpu_parity.py)
+PARAM_LOADS = dict(dc=dict(a=0.05, b=0.03, c=4e-3, j_load=2e-3), three_phase=dict(a=0.2, b=0.02, c=1e-3, j_load=2e-3),
+                   dfim=dict(a=0.2, b=0.02, c=4e-3, j_load=2e-3), eesm=dict(a=2.0, b=0.1, c=5e-3, j_load=0.05))
+
+
+def main_params():
+    """Non-default machine parameters (PARAM_SETS), supply voltages, limits / nominal values, control steps and loads.  The make-kwargs
+    of every run are recorded in meta["overrides"] exactly as passed, the reference motor's torque table in meta["torque_kat"]."""
+    S, L = PARAM_SETS, PARAM_LOADS
+
+    def run(name, env_id, solver, K, seed, mode, episodic, space_kind, mp, **kw):
+        motor = dict(motor_parameter=dict(mp), **kw.pop("motor", {}))
+        run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, record_overrides=True, motor=motor, **kw)
+
+    # --- DC machines ---------------------------------------------------------------------------------------------------------------
+    run("param_permexdc_cont_cc_free_held_euler", "Cont-CC-PermExDc-v0", "euler", 1000, 1600, "held", False, "box1", S["permexdc"])
+    run("param_permexdc_fin_cc_lim_epi_uniform_euler", "Finite-CC-PermExDc-v0", "euler", 1000, 1601, "uniform", True, "disc4", S["permexdc"],
+        motor=dict(limit_values=dict(i=90.0), nominal_values=dict(i=70.0)))
+    run("param_permexdc_cont_sc_u80_free_held_dopri5", "Cont-SC-PermExDc-v0", "dopri5", 1000, 1602, "held", False, "box1", S["permexdc"],
+        supply=dict(u_nominal=80.0), load=dict(load_parameter=dict(L["dc"])))
+    run("param_series_cont_cc_free_held_euler", "Cont-CC-SeriesDc-v0", "euler", 1000, 1603, "held", False, "box1", S["series"])
+    run("param_series_cont_sc_free_held_dopri5", "Cont-SC-SeriesDc-v0", "dopri5", 1000, 1604, "held", False, "box1", S["series"],
+        load=dict(load_parameter=dict(L["dc"])))
+    run("param_shunt_cont_cc_epi_held_euler", "Cont-CC-ShuntDc-v0", "euler", 1000, 1605, "held", True, "box1", S["shunt"])
+    run("param_shunt_cont_sc_free_held_dopri5", "Cont-SC-ShuntDc-v0", "dopri5", 1000, 1606, "held", False, "box1", S["shunt"],
+        load=dict(load_parameter=dict(L["dc"])))
+    run("param_extex_fin_cc_til_free_held_euler", "Finite-CC-ExtExDc-v0", "euler", 1000, 1607, "held", False, "mdisc44", S["extex"],
+        converter=ps.FiniteMultiConverter(subconverters=[ps.FiniteFourQuadrantConverter(interlocking_time=1e-6),
+                                                         ps.FiniteFourQuadrantConverter(interlocking_time=1e-6)]))
+    run("param_extex_cont_sc_free_held_dopri5", "Cont-SC-ExtExDc-v0", "dopri5", 1000, 1608, "held", False, "box2", S["extex"],
+        load=dict(load_parameter=dict(L["dc"])))
+    # --- synchronous machines ------------------------------------------------------------------------------------------------------
+    run("param_pmsm_fin_cc_lim_u350_epi_uniform_tau5e-5_euler", "Finite-CC-PMSM-v0", "euler", 800, 1610, "uniform", True, "disc8", S["pmsm"],
+        tau=5e-5, supply=dict(u_nominal=350.0), motor=dict(limit_values=dict(i=160.0), nominal_values=dict(i=120.0)))
+    run("param_pmsm_cont_sc_free_held_dopri5", "Cont-SC-PMSM-v0", "dopri5", 800, 1611, "held", False, "box3", S["pmsm"],
+        load=dict(load_parameter=dict(L["three_phase"])))
+    run("param_pmsm_cont_cc_negspeed_free_held_euler", "Cont-CC-PMSM-v0", "euler", 800, 1612, "held", False, "box3", S["pmsm"],
+        load=dict(omega_fixed=-250.0))
+    run("param_pmsm_nonsalient_fin_cc_free_held_euler", "Finite-CC-PMSM-v0", "euler", 800, 1613, "held", False, "disc8", S["pmsm_nonsalient"])
+    run("param_pmsm_reversed_cont_cc_free_held_euler", "Cont-CC-PMSM-v0", "euler", 800, 1614, "held", False, "box3", S["pmsm_reversed"])
+    # (at 420 V the free run drives this machine to 2x its current limit, where its torque is stiff enough to put even the split fixed
+    # steps 5e-4 away from the adaptive reference: a lower supply keeps the run inside the 1e-4 contract's domain)
+    run("param_pmsm_reversed_cont_sc_u120_free_held_dopri5", "Cont-SC-PMSM-v0", "dopri5", 800, 1615, "held", False, "box3", S["pmsm_reversed"],
+        supply=dict(u_nominal=120.0), load=dict(load_parameter=dict(L["three_phase"], c=1e-2)))
+    run("param_synrm_fin_cc_free_held_euler", "Finite-CC-SynRM-v0", "euler", 800, 1616, "held", False, "disc8", S["synrm"])
+    run("param_synrm_cont_sc_free_held_dopri5", "Cont-SC-SynRM-v0", "dopri5", 800, 1617, "held", False, "box3", S["synrm"],
+        load=dict(load_parameter=dict(L["three_phase"])))
+    run("param_eesm_cont_cc_epi_held_euler", "Cont-CC-EESM-v0", "euler", 800, 1618, "held", True, "box4", S["eesm"])
+    run("param_eesm_fin_cc_epi_held_euler", "Finite-CC-EESM-v0", "euler", 800, 1619, "held", True, "mdisc84", S["eesm"])
+    run("param_eesm_cont_sc_epi_held_dopri5", "Cont-SC-EESM-v0", "dopri5", 800, 1620, "held", True, "box4", S["eesm"],
+        load=dict(load_parameter=dict(L["eesm"])))
+    # --- induction machines --------------------------------------------------------------------------------------------------------
+    run("param_scim_cont_cc_free_held_euler", "Cont-CC-SCIM-v0", "euler", 800, 1621, "held", False, "box3", S["scim"])
+    run("param_scim_fin_cc_lim_epi_uniform_euler", "Finite-CC-SCIM-v0", "euler", 800, 1627, "uniform", True, "disc8", S["scim"],
+        motor=dict(limit_values=dict(i=3.5), nominal_values=dict(i=3.0)))
+    run("param_scim_cont_sc_free_held_dopri5", "Cont-SC-SCIM-v0", "dopri5", 800, 1623, "held", False, "box3", S["scim"],
+        load=dict(load_parameter=dict(L["three_phase"])))
+    run("param_scim_cont_cc_negspeed_free_held_euler", "Cont-CC-SCIM-v0", "euler", 800, 1624, "held", False, "box3", S["scim"],
+        load=dict(omega_fixed=-150.0))
+    run("param_dfim_cont_cc_free_held_euler", "Cont-CC-DFIM-v0", "euler", 600, 1625, "held", False, "box6", S["dfim"])
+    run("param_dfim_fin_cc_free_held_euler", "Finite-CC-DFIM-v0", "euler", 600, 1626, "held", False, "mdisc88", S["dfim"])
+    run("param_dfim_cont_sc_free_held_dopri5", "Cont-SC-DFIM-v0", "dopri5", 600, 1627, "held", False, "box6", S["dfim"],
+        load=dict(load_parameter=dict(L["dfim"])))
+    # --- random initial states of the induction machines at the non-default sets (flux bounds from l_m, l_sigs, l_sigr, r_s, r_r, p)
+    uni = dict(random_init="uniform")
+    init_samples(cases={
+        "scim_sc_uniform": ("Cont-SC-SCIM-v0", uni, None, None, dict(motor_parameter=dict(S["scim"]))),
+        "scim_cc_negspeed_uniform": ("Cont-CC-SCIM-v0", uni, None, dict(omega_fixed=-100.0), dict(motor_parameter=dict(S["scim"]))),
+        "dfim_cc_negspeed_uniform": ("Cont-CC-DFIM-v0", uni, None, dict(omega_fixed=-60.0), dict(motor_parameter=dict(S["dfim"]))),
+    }, fname="init_samples_params.npz", n_obs=32)
 
 
 def main_dfim():

@@ -79,7 +79,27 @@ def _make_from_meta(meta, n_envs, solver=None, dtype="float32", episodic=None, o
         kw["control_space"] = "dq"
     if meta["supply"] == "RCVoltageSupply":
         kw["supply"] = ga.RCVoltageSupply(u_nominal=meta["u_nominal"], supply_parameter=meta["supply_parameter"])
+    # make-kwargs the fixture was recorded with (oracle/make_golden.py:main_params), exactly as passed to the reference: motor
+    # parameters, limits and nominal values, an ideal supply's voltage, the load (the meta's own load rebuild above then gives way)
+    ov = meta.get("overrides", {})
+    for k in ("motor", "supply", "load"):
+        if k in ov:
+            kw[k] = json.loads(json.dumps(ov[k]))  # (a fresh copy: the components keep the dicts they are given)
+    if "tau" in ov:
+        assert kw["tau"] == ov["tau"]
     return ga.make(meta["env_id"], **kw)
+
+
+def _param_overrides(name, omega_fixed=False):
+    """The motor (and supply) make-kwargs a `param_*` fixture was recorded with, for tests that build their env from an env id;
+    omega_fixed: also its ConstantSpeedLoad."""
+    ov = _load(name)[1]["overrides"]
+    out = {k: json.loads(json.dumps(ov[k])) for k in ("motor", "supply") if k in ov}
+    if omega_fixed:
+        import gym_electric_motor_amd as ga
+
+        out["load"] = ga.ConstantSpeedLoad(omega_fixed=_load(name)[1]["omega_fixed"])
+    return out
 
 
 def _rel_err(got, ref, names, scale_ref=None):
@@ -473,7 +493,10 @@ def test_error_controlled_solver_fp64_against_the_reference_default_solver(name)
     assert rel < 2e-5, (rel, col, dmsg)
 
 
-@pytest.mark.parametrize("name", ["scim_epi_uniform_euler", "pmsm_sc_free_held_dopri5", "scim_free_held_dopri5", "permexdc_sc_free_held_dopri5"])
+@pytest.mark.parametrize("name", ["scim_epi_uniform_euler", "pmsm_sc_free_held_dopri5", "scim_free_held_dopri5", "permexdc_sc_free_held_dopri5",
+                                  # non-default machines, PolynomialStaticLoad with c != 0 (oracle/make_golden.py:main_params)
+                                  "param_scim_cont_sc_free_held_dopri5", "param_pmsm_cont_sc_free_held_dopri5", "param_permexdc_cont_sc_u80_free_held_dopri5",
+                                  "param_dfim_cont_sc_free_held_dopri5", "param_series_cont_sc_free_held_dopri5"])
 @pytest.mark.parametrize("split_kinks", [True, False])
 def test_error_controlled_solver_fp64_equals_its_cpu_restatement(name, split_kinks):
     """Round 6: the device's error controller -- carried proposal, first try = segment / ceil(0.9 segment / proposal), rejections cut by
@@ -574,7 +597,11 @@ def test_error_controlled_solver_raises_its_flag_at_the_floor():
 SCIM_POLY_DOPRI = [c for c in DOPRI if c.startswith("scim_") and "constspeed" not in c]
 
 
-@pytest.mark.parametrize("name", SCIM_POLY_DOPRI + ["pmsm_sc_free_held_dopri5", "permexdc_sc_free_held_dopri5", "refdata_cont_sc_permexdc_dopri5"])
+# the free-running non-default machines behind a PolynomialStaticLoad with its quadratic term on (c != 0)
+PARAM_POLY_DOPRI = [c for c in DOPRI if c.startswith("param_") and "_sc_" in c and "_epi_" not in c]
+
+
+@pytest.mark.parametrize("name", SCIM_POLY_DOPRI + ["pmsm_sc_free_held_dopri5", "permexdc_sc_free_held_dopri5", "refdata_cont_sc_permexdc_dopri5"] + PARAM_POLY_DOPRI)
 @pytest.mark.parametrize("solver", ["rk4k", "dp5k"])
 def test_split_kinks_tracks_the_reference_adaptive_solver(name, solver):
     """GEMX_SOLVER_SPLIT_KINKS (RK4Solver / DormandPrince5Solver(split_kinks=True)): steps cut at the PolynomialStaticLoad's kinks, the
@@ -586,7 +613,7 @@ def test_split_kinks_tracks_the_reference_adaptive_solver(name, solver):
     d, meta, obs, done = _run_golden(name, "float32", solver=solver)
     rel, _, col, dmsg = compare_trajectory(meta, d, obs, done)
     assert rel < 3e-5, (rel, col, dmsg)
-    if name.startswith("scim_free") or name.startswith("pmsm_sc"):
+    if name.startswith("scim_free") or name.startswith("pmsm_sc") or name.startswith("param_"):
         d, meta, obs64, _ = _run_golden(name, "float64", solver=solver)
         e = orc.OracleEnv(orc.params_from_meta(meta, solver={"rk4k": "rk4_kink", "dp5k": "dp5_kink"}[solver], episodic=False))
         e.reset()
@@ -843,7 +870,10 @@ def test_multi_converter_envs_per_env_actions_against_oracle(env_id, golden, til
                                   "permexdc_free_held_til_euler", "pmsm_free_uniform_10k_euler",
                                   "extex_fin_free_held_til_euler", "extex_cont_epi_held_euler", "eesm_fin_epi_held_tau1e-4_euler",
                                   "eesm_cont_free_uniform_euler", "dfim_fin_free_uniform_til_euler", "dfim_fin_epi_held_tau1e-4_euler",
-                                  "dfim_cont_sc_epi_held_euler"])
+                                  "dfim_cont_sc_epi_held_euler",
+                                  "param_pmsm_fin_cc_lim_u350_epi_uniform_tau5e-5_euler", "param_pmsm_reversed_cont_cc_free_held_euler",
+                                  "param_scim_fin_cc_lim_epi_uniform_euler", "param_permexdc_fin_cc_lim_epi_uniform_euler", "param_shunt_cont_cc_epi_held_euler",
+                                  "param_extex_fin_cc_til_free_held_euler", "param_eesm_fin_cc_epi_held_euler", "param_dfim_fin_cc_free_held_euler"])
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_two_wave_pipelined_kernel_matches_reference_and_single_wave_kernel(name, dtype, monkeypatch):
     """n_envs = 128 (full 64-env workgroups) takes the two-wave pipelined kernel; it must agree with the reference AND be
@@ -857,6 +887,82 @@ def test_two_wave_pipelined_kernel_matches_reference_and_single_wave_kernel(name
     assert (rel < 1e-4) if dtype == "float32" else (ab < 1e-9)
     if meta["episodic"]:
         _check_done(meta, d, done_p)
+
+
+def _variant_against_oracle(name, meta, solver, n=8):
+    """One device rollout (fp32, n lanes, each on its own seeded random action stream) of a fixture's env rebuilt from `meta` -- a
+    fixture's meta or a variant of it with other recorded overrides --, every lane checked against the fp64 oracle run of the SAME
+    variant (_lanes_against_oracle: 1e-4).  Returns the observations in PHYSICAL units [K, n, S_out]."""
+    import torch
+
+    import gym_electric_motor_amd as ga
+
+    d = _load(name)[0]
+    K = d["actions"].shape[0]
+    env = _make_from_meta(meta, n, solver=solver, auto_reset=True)
+    ps = env.physical_system
+    rng = np.random.default_rng(5)
+    if ps._discrete:  # (MultiDiscrete actions stay [K, N, 2]: rollout() packs them into the flat index)
+        nvec = [int(v) for v in ps.action_space.nvec] if hasattr(ps.action_space, "nvec") else [int(ps.action_space.n)]
+        a_np = np.stack([rng.integers(0, nv, (K, n)) for nv in nvec], axis=2).astype(np.uint8)
+        a = torch.as_tensor(a_np.reshape(K, n) if len(nvec) == 1 else a_np)
+    else:
+        a_np = rng.uniform(-1.0, 1.0, (K, n, ps._n_act))
+        a = torch.as_tensor(a_np)
+    obs, done = env.rollout(a.cuda())
+    obs, done = obs.double().cpu().numpy(), done.cpu().numpy().astype(bool)
+    lim = [float(x) for x in ps.limits]
+    sol_obj = ps._ode_solver
+    env.close()
+    worst = _lanes_against_oracle(name, dict(meta, limits=lim), a_np, obs, done, list(range(n)), sol_obj, "float32", 1 if a_np.shape[2] == 1 and ps._discrete else 2)
+    assert worst is not None
+    return obs * np.asarray(lim), worst
+
+
+@pytest.mark.parametrize("name", ["param_scim_cont_cc_free_held_euler", "param_dfim_cont_cc_free_held_euler", "param_scim_cont_sc_free_held_dopri5",
+                                  "param_dfim_fin_cc_free_held_euler"])
+def test_stator_rotor_leakage_swap_is_seen_at_the_recorded_points(name):
+    """The reference's default induction machines have l_sigs == l_sigr, so a stator / rotor mix-up anywhere (host constants, torque
+    coefficient, rotor-current reconstruction, the kernels' packed index tables) gives identical numbers at every default fixture.  At
+    the recorded non-default sets the swap must MOVE the device trajectory by more than 100x the 1e-4 contract -- and the recorded set
+    and the swapped one must each still match the fp64 oracle run of their own parameters."""
+    _, meta = _load(name)
+    mp = meta["overrides"]["motor"]["motor_parameter"]
+    assert mp["l_sigs"] != mp["l_sigr"]
+    sw = json.loads(json.dumps(meta))
+    sw["overrides"]["motor"]["motor_parameter"].update(l_sigs=mp["l_sigr"], l_sigr=mp["l_sigs"])
+    sw["motor_parameter"].update(l_sigs=mp["l_sigr"], l_sigr=mp["l_sigs"])
+    solver = "euler" if name.endswith("euler") else "rk4k"
+    a, wa = _variant_against_oracle(name, meta, solver)
+    b, wb = _variant_against_oracle(name, sw, solver)
+    scale = np.maximum(np.abs(a).max(axis=(0, 1)), 1e-30)
+    moved = (np.abs(a - b).max(axis=(0, 1)) / scale)
+    cols = [i for i, c in enumerate(meta["state_names"]) if c not in ("epsilon", "u_sup") and not c.startswith("u_")]
+    assert moved[cols].max() > 100 * 1e-4, (dict(zip(meta["state_names"], moved.round(6))), wa, wb)
+
+
+@pytest.mark.parametrize("name", ["param_scim_cont_sc_free_held_dopri5", "param_pmsm_cont_sc_free_held_dopri5", "param_permexdc_cont_sc_u80_free_held_dopri5",
+                                  "param_synrm_cont_sc_free_held_dopri5", "param_dfim_cont_sc_free_held_dopri5", "param_series_cont_sc_free_held_dopri5"])
+@pytest.mark.parametrize("solver", ["rk4k", "dp5k", "euler", "adaptive"])
+def test_quadratic_load_term_is_seen_at_the_recorded_points(name, solver):
+    """Every default speed-control env has c = 0 in its PolynomialStaticLoad, so the quadratic term c omega |omega| -- written out in
+    the scalar load ODE, the packed RHS, the kink-side branch, the fp64 stage solver and the adaptive solver -- was never compared on
+    the device.  At the recorded c != 0 points: switching the term off must move omega by more than 100x the 1e-4 contract, and both
+    variants must match the fp64 oracle run of their own load (fixed steps with kink splitting, Euler, and the error-controlled
+    solver, which the oracle restates as scipy's dopri5 at the same tolerance)."""
+    import gym_electric_motor_amd as ga
+
+    _, meta = _load(name)
+    assert meta["load_parameter"]["c"] != 0
+    off = json.loads(json.dumps(meta))
+    off["overrides"]["load"]["load_parameter"]["c"] = 0.0
+    off["load_parameter"]["c"] = 0.0
+    sol = ga.ScipyOdeSolver() if solver == "adaptive" else solver
+    a, _ = _variant_against_oracle(name, meta, sol)
+    b, _ = _variant_against_oracle(name, off, sol if isinstance(sol, str) else ga.ScipyOdeSolver())
+    w = meta["state_names"].index("omega")
+    moved = np.abs(a[..., w] - b[..., w]).max() / np.abs(a[..., w]).max()
+    assert moved > 100 * 1e-4, moved
 
 
 @pytest.mark.parametrize("env_id, wrappers, control_space", [
@@ -1030,17 +1136,23 @@ def test_fused_reward_fp64_and_soa_layout():
 
 
 INIT_SAMPLES = os.path.join(GOLDEN, "init_samples.npz")
+INIT_SAMPLES_PARAMS = os.path.join(GOLDEN, "init_samples_params.npz")  # (non-default motor parameters, recorded with their make-kwargs)
 
 
 def _init_env(case, n_envs, seed=7, **kw):
+    """case: a case of init_samples.npz, or 'params:<case>' of init_samples_params.npz."""
     import gym_electric_motor_amd as ga
 
-    d = np.load(INIT_SAMPLES)
+    path = INIT_SAMPLES
+    if case.startswith("params:"):
+        path, case = INIT_SAMPLES_PARAMS, case[7:]
+    d = np.load(path)
     meta = json.loads(str(d[case + "_meta"]))
     motor_cls = {"PermanentMagnetSynchronousMotor": ga.PermanentMagnetSynchronousMotor, "DcExternallyExcitedMotor": ga.DcExternallyExcitedMotor,
                  "ExternallyExcitedSynchronousMotor": ga.ExternallyExcitedSynchronousMotor, "DcPermanentlyExcitedMotor": ga.DcPermanentlyExcitedMotor,
                  "SquirrelCageInductionMotor": ga.SquirrelCageInductionMotor, "DoublyFedInductionMotor": ga.DoublyFedInductionMotor}[meta["motor"]]
-    mk = dict(motor=motor_cls(motor_initializer=meta["motor_initializer"]), seed=seed, n_envs=n_envs, **kw)
+    mkw = json.loads(json.dumps(meta.get("overrides", {}).get("motor", {})))
+    mk = dict(motor=motor_cls(motor_initializer=meta["motor_initializer"], **mkw), seed=seed, n_envs=n_envs, **kw)
     if meta["load_initializer"] is not None:
         mk["load"] = ga.PolynomialStaticLoad(load_parameter=meta["load_parameter"], load_initializer=meta["load_initializer"])
     elif meta["load"] == "ConstantSpeedLoad":
@@ -1094,7 +1206,9 @@ def test_random_uniform_initialisers_match_reference_distribution(case):
     env.close()
 
 
-@pytest.mark.parametrize("case", ["scim_sc_uniform", "scim_cc_uniform", "scim_cc_negspeed_uniform", "dfim_cc_negspeed_interval_uniform"])
+@pytest.mark.parametrize("case", ["scim_sc_uniform", "scim_cc_uniform", "scim_cc_negspeed_uniform", "dfim_cc_negspeed_interval_uniform",
+                                  # init_samples_params.npz: p = 3, l_sigs != l_sigr, other l_m / r_s / r_r (oracle/make_golden.py:main_params)
+                                  "params:scim_sc_uniform", "params:scim_cc_negspeed_uniform", "params:dfim_cc_negspeed_uniform"])
 def test_induction_machine_random_initialisers_match_reference_distribution(case):
     """SURVEY 8f rank 4, induction machines (round 4): the MOTOR initialiser of a SCIM / DFIM re-derives its flux bounds at every reset
     from a random field angle (induction_motor.py:174-185, 250-285; squirrel_cage_induction_motor.py:146-157) -- psi_d_max = l_m
@@ -1129,8 +1243,9 @@ def test_induction_machine_random_initialisers_match_reference_distribution(case
     mag, ref_mag = np.hypot(y[:, 3], y[:, 4]), np.hypot(ref_y[:, 3], ref_y[:, 4])
     if ref_mag.max() > 0:
         assert stats.ks_2samp(mag, ref_mag).pvalue > 1e-3
-        if case == "scim_sc_uniform":  # omega == 0: |psi| <= l_m i_sd,nominal (0.14375 H x 3.9 A)
-            assert mag.max() <= 0.14375 * 3.9 * (1 + 1e-6) and mag.max() > 0.9 * 0.14375 * 3.9
+        if case.endswith("scim_sc_uniform"):  # omega == 0: |psi| <= l_m i_sd,nominal (defaults: 0.14375 H x 3.9 A)
+            psi_max = meta["motor_parameter"]["l_m"] * meta["nominal_state"][meta["state_names"].index("i_sd")]
+            assert mag.max() <= psi_max * (1 + 1e-6) and mag.max() > 0.9 * psi_max
     else:
         assert mag.max() == 0.0
     # the first reset of an env reads the CONFIGURED currents (zeros): at omega != 0 that gives psi_d_max = 0.9 clip(., 0, |l_m 0|) = 0
@@ -1140,6 +1255,8 @@ def test_induction_machine_random_initialisers_match_reference_distribution(case
         assert np.abs(y1[:, 3:5]).max() == 0.0 and np.ptp(y1[:, 1]) > 1.0
         e1.close()
     gname = "scim_free_held_euler" if "scim" in case else "dfim_cont_free_held_euler"
+    if case.startswith("params:"):  # (the state -> observation map reads the motor parameters: a fixture of the same set)
+        gname = "param_scim_cont_cc_free_held_euler" if "scim" in case else "param_dfim_cont_cc_free_held_euler"
     _, gmeta = _load(gname)
     gmeta = dict(gmeta, action_frame="abc", limits=[float(x) for x in ps.limits], u_nominal=float(ps.supply.u_nominal), load=meta["load"])
     p = orc.params_from_meta(gmeta, episodic=False)
@@ -1412,7 +1529,11 @@ PARTIAL_CASES = ["pmsm_epi_held_tau1e-4_euler",            # finite B6: voltage 
                  "dfim_fin_epi_held_tau1e-4_euler",        # two bytes of leg state per env, 24-column rows
                  "pmsm_fin_dead1_til_free_uniform_euler",  # DeadTimeProcessor queue in HBM
                  "rc_pmsm_fin_til_epi_uniform_tau1e-4_euler",  # RCVoltageSupply: the FULL instantiation
-                 "init:pmsm_sc_uniform"]                   # random initialisers: reset counters per lane (FULL)
+                 "init:pmsm_sc_uniform",                   # random initialisers: reset counters per lane (FULL)
+                 # non-default machines (oracle/make_golden.py:main_params): custom limits + tau 5e-5, a negative torque limit,
+                 # l_sigs != l_sigr behind custom limits, a kink-band load with c != 0
+                 "param_pmsm_fin_cc_lim_u350_epi_uniform_tau5e-5_euler", "param_pmsm_reversed_cont_cc_free_held_euler",
+                 "param_scim_fin_cc_lim_epi_uniform_euler", "param_scim_cont_sc_free_held_dopri5"]
 
 
 @pytest.mark.parametrize("name", PARTIAL_CASES)
@@ -2307,7 +2428,11 @@ def test_masked_reset():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("env_id, K", [("Finite-CC-PMSM-v0", 96), ("Cont-CC-PMSM-v0", 53), ("Finite-CC-EESM-v0", 48), ("Finite-CC-SCIM-v0", 40)])
+@pytest.mark.parametrize("env_id, K", [("Finite-CC-PMSM-v0", 96), ("Cont-CC-PMSM-v0", 53), ("Finite-CC-EESM-v0", 48), ("Finite-CC-SCIM-v0", 40),
+                                       # the map linmap_kernel builds from p and omega, at p = 5 / 3 and a negative speed
+                                       ("Cont-CC-PMSM-v0:param_pmsm_cont_cc_negspeed_free_held_euler", 53),
+                                       ("Finite-CC-PMSM-v0:param_pmsm_reversed_cont_cc_free_held_euler", 96),
+                                       ("Finite-CC-SCIM-v0:param_scim_cont_cc_negspeed_free_held_euler", 40)])
 def test_one_step_map_equals_stage_solver_and_is_dropped_when_omega_differs(env_id, K, monkeypatch):
     """ConstantSpeedLoad + RK4: the electrical subsystem is stepped by the precomputed affine map x1 = Phi x0 + S g (integrate<LIN>).
     (1) Same rollout with GEMX_LINMAP=0 (RK4 stage by stage): equal up to fp32 rounding of the same polynomial (<= 2e-5 of each
@@ -2317,9 +2442,12 @@ def test_one_step_map_equals_stage_solver_and_is_dropped_when_omega_differs(env_
 
     import gym_electric_motor_amd as ga
 
+    env_id, _, golden = env_id.partition(":")
+    mk = _param_overrides(golden, omega_fixed=True) if golden else {}
+
     def run(linmap, perturb):
         monkeypatch.setenv("GEMX_LINMAP", linmap)
-        env = ga.make(env_id, n_envs=128, ode_solver=ga.RK4Solver(), constraints=())
+        env = ga.make(env_id, n_envs=128, ode_solver=ga.RK4Solver(), constraints=(), **mk)
         ps = env.physical_system
         env.reset()
         g = torch.Generator(device="cuda").manual_seed(7)
@@ -2352,7 +2480,11 @@ def test_one_step_map_equals_stage_solver_and_is_dropped_when_omega_differs(env_
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["pmsm_epi_held_tau1e-4_euler", "scim_epi_uniform_euler", "permexdc_epi_held_euler", "eesm_fin_epi_held_tau1e-4_euler",
-                                  "dfim_fin_epi_held_tau1e-4_euler", "extex_cont_epi_held_euler"])
+                                  "dfim_fin_epi_held_tau1e-4_euler", "extex_cont_epi_held_euler",
+                                  "param_pmsm_fin_cc_lim_u350_epi_uniform_tau5e-5_euler", "param_pmsm_reversed_cont_cc_free_held_euler",
+                                  "param_pmsm_nonsalient_fin_cc_free_held_euler", "param_synrm_fin_cc_free_held_euler", "param_scim_fin_cc_lim_epi_uniform_euler",
+                                  "param_scim_cont_cc_negspeed_free_held_euler", "param_permexdc_fin_cc_lim_epi_uniform_euler", "param_shunt_cont_cc_epi_held_euler",
+                                  "param_eesm_cont_cc_epi_held_euler", "param_dfim_cont_cc_free_held_euler", "param_dfim_fin_cc_free_held_euler"])
 def test_all_pipelined_shapes_are_bit_identical(name, monkeypatch):
     """<12 steps, 3 output waves>, <4, 2> and <2, 2> (chosen by N in production, forced here with GEMX_PIPE_SHAPE) and the single-wave
     kernel give the same bits on the same inputs; K of the fixtures is not a multiple of any D, so every shape runs a tail block."""
@@ -2413,7 +2545,11 @@ def test_single_step_launches_replay_from_a_hip_graph_bit_identically():
 
 
 @pytest.mark.parametrize("env_id", ["Cont-CC-PermExDc-v0", "Finite-CC-PermExDc-v0", "Cont-CC-SeriesDc-v0", "Finite-SC-SeriesDc-v0", "Cont-CC-ShuntDc-v0",
-                                    "Finite-CC-ShuntDc-v0", "Cont-CC-ExtExDc-v0", "Finite-CC-ExtExDc-v0"])
+                                    "Finite-CC-ShuntDc-v0", "Cont-CC-ExtExDc-v0", "Finite-CC-ExtExDc-v0",
+                                    # the non-default DC machines of oracle/make_golden.py:main_params (motor parameters; PermExDc: custom limits)
+                                    "Cont-CC-PermExDc-v0:param_permexdc_cont_cc_free_held_euler", "Finite-CC-PermExDc-v0:param_permexdc_fin_cc_lim_epi_uniform_euler",
+                                    "Cont-CC-SeriesDc-v0:param_series_cont_cc_free_held_euler", "Finite-CC-ShuntDc-v0:param_shunt_cont_cc_epi_held_euler",
+                                    "Cont-CC-ExtExDc-v0:param_extex_fin_cc_til_free_held_euler"])
 @pytest.mark.parametrize("solver", ["euler", "rk4", "rk4_nolinmap", "dp5", "euler_epw64", "rk4_epw64"])
 def test_dc_stream_kernel_is_bit_identical_to_the_pipelined_kernel(env_id, solver, monkeypatch):
     """Small batches of the DC machines behind a ConstantSpeedLoad take dc_stream_kernel (pre waves: converter + input term; integrator:
@@ -2427,6 +2563,8 @@ def test_dc_stream_kernel_is_bit_identical_to_the_pipelined_kernel(env_id, solve
     import gym_electric_motor_amd as ga
 
     n = 192
+    env_id, _, golden = env_id.partition(":")
+    motor = _param_overrides(golden)["motor"] if golden else None
     # (`_epw64`: the form with one env per lane, which the launcher takes from 4097 to 8192 envs; default here: 32 envs per workgroup)
     if solver.endswith("_epw64"):
         monkeypatch.setenv("GEMX_DCS_EPW", "64")
@@ -2441,7 +2579,7 @@ def test_dc_stream_kernel_is_bit_identical_to_the_pipelined_kernel(env_id, solve
             monkeypatch.setenv("GEMX_LINMAP", "0")
         else:
             monkeypatch.delenv("GEMX_LINMAP", raising=False)
-        env = ga.make(env_id, n_envs=n, ode_solver=sol(), tau=1e-4, load=ga.ConstantSpeedLoad(omega_fixed=60.0))
+        env = ga.make(env_id, n_envs=n, ode_solver=sol(), tau=1e-4, load=ga.ConstantSpeedLoad(omega_fixed=60.0), motor=json.loads(json.dumps(motor)))
         ps = env.physical_system
         env.reset()
         g = torch.Generator(device="cuda").manual_seed(23)

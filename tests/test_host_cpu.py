@@ -97,6 +97,110 @@ def test_host_metadata_matches_reference(env_id, golden):
     assert list(cfg.limits)[: len(meta["limits"])] == [float(x) for x in ps.limits]  # the config carries the system's limits verbatim
 
 
+PARAM_CASES = sorted(os.path.basename(f)[:-4] for f in os.listdir(GOLDEN) if f.startswith("param_") and f.endswith(".npz"))
+
+
+def _make_param(meta, **kw):
+    """A `param_*` fixture's env, built from the make-kwargs recorded with it (oracle/make_golden.py:main_params), without a device."""
+    ov = json.loads(json.dumps(meta["overrides"]))
+    return ga.make(meta["env_id"], n_envs=8, _defer_create=True, **{k: ov[k] for k in ("motor", "supply", "load", "tau") if k in ov}, **kw)
+
+
+def _torque_from_coefficients(meta, tc, x):
+    """The torque the kernels form from `torque_coef` (Elec<SYS>::torque) at motor ODE state x, restated."""
+    motor = meta["motor"]
+    if motor == "DcPermanentlyExcitedMotor":
+        return tc[0] * x[0]
+    if motor == "DcSeriesMotor":
+        return tc[0] * x[0] * x[0]
+    if motor in ("DcShuntMotor", "DcExternallyExcitedMotor"):
+        return tc[0] * x[0] * x[1]
+    if motor == "ExternallyExcitedSynchronousMotor":  # [i_sd, i_sq, i_e, epsilon]
+        return (tc[0] * x[2] + tc[1] * x[0]) * x[1]
+    if motor in ("PermanentMagnetSynchronousMotor", "SynchronousReluctanceMotor"):  # [i_sd, i_sq, epsilon]
+        return (tc[0] + tc[1] * x[0]) * x[1]
+    return tc[0] * (x[2] * x[1] - x[3] * x[0])  # induction machines: [i_salpha, i_sbeta, psi_ralpha, psi_rbeta, epsilon]
+
+
+def test_param_fixture_inventory():
+    """The non-default parameter group covers every motor class, and breaks the coincidences of the reference's defaults it is there for."""
+    metas = {n: _meta(n) for n in PARAM_CASES}
+    assert {m["motor"] for m in metas.values()} == {"DcPermanentlyExcitedMotor", "DcSeriesMotor", "DcShuntMotor", "DcExternallyExcitedMotor",
+                                                  "PermanentMagnetSynchronousMotor", "SynchronousReluctanceMotor", "ExternallyExcitedSynchronousMotor",
+                                                  "SquirrelCageInductionMotor", "DoublyFedInductionMotor"}
+    for n, m in metas.items():
+        assert n.endswith(("_euler", "_dopri5")) and "overrides" in m and "torque_kat" in m, n
+        if m["load"] == "PolynomialStaticLoad":  # the quadratic term, and a kink band on the way through zero speed
+            assert m["load_parameter"]["c"] != 0 and m["load_parameter"]["a"] > 0, n
+        if "InductionMotor" in m["motor"]:
+            assert m["motor_parameter"]["l_sigs"] != m["motor_parameter"]["l_sigr"] and m["motor_parameter"]["p"] != 2, n
+    assert sum("supply" in m["overrides"] for m in metas.values()) >= 2
+    # custom limits / nominal values on a three-phase machine, with terminations inside the run
+    assert any("limit_values" in m["overrides"]["motor"] and "epsilon" in m["state_names"] and np.load(os.path.join(GOLDEN, n + ".npz"))["terminated"].any()
+               for n, m in metas.items())
+    assert any(m["limits"][m["state_names"].index("torque")] < 0 for m in metas.values())  # the reversed-saliency PMSM
+    assert any(m.get("tau") == 5e-5 for m in metas.values())
+
+
+@pytest.mark.parametrize("name", PARAM_CASES)
+def test_host_metadata_at_non_default_parameters_matches_reference(name):
+    """Every `param_*` fixture: the env built from the recorded overrides has the reference's model constants (1e-15), limits and nominal
+    state (_check_limits), inertia, supply voltage, control step and load -- and the torque the kernels form from the configured torque
+    coefficients equals the reference motor's torque() on the recorded table (the doubly fed machine: its rotor-current reconstruction
+    too).  With l_sigs != l_sigr a stator / rotor swap in any of these fails here."""
+    meta = _meta(name)
+    ps = _make_param(meta).physical_system
+    assert list(ps.state_names) == meta["state_names"]
+    _check_limits(ps, meta)
+    ref_m = np.asarray(meta["model_constants"])
+    assert (np.abs(np.asarray(ps.electrical_motor._model_constants) - ref_m) <= 1e-15 * np.abs(ref_m)).all()
+    assert ps.mechanical_load.j_total == pytest.approx(meta["j_total"], rel=1e-15)
+    assert ps.tau == meta["tau"] and ps.supply.u_nominal == meta["u_nominal"]
+    cfg = ps._cfg
+    assert list(cfg.limits)[: len(meta["limits"])] == [float(x) for x in ps.limits]
+    if meta["load"] == "ConstantSpeedLoad":
+        assert cfg.init_state[0] == meta["omega_fixed"]
+    else:
+        lp = meta["load_parameter"]
+        assert (cfg.load_a, cfg.load_b, cfg.load_c, cfg.tau_decay) == (lp["a"], lp["b"], lp["c"], meta["tau_decay"])
+    tc = list(cfg.torque_coef)
+    kat = meta["torque_kat"]
+    for x, t in zip(kat["states"], kat["torque"]):
+        assert abs(_torque_from_coefficients(meta, tc, x) - t) <= 1e-13 * max(abs(t), 1e-3 * abs(meta["limits"][1])), (x, t)
+    if "rotor_current" in kat:  # i_r = psi_r / l_r - l_m / l_r i_s  (physical_systems.py:954-966): tc2, tc3
+        for x, i_r in zip(kat["states"], kat["rotor_current"]):
+            got = [tc[2] * x[2] - tc[3] * x[0], tc[2] * x[3] - tc[3] * x[1]]
+            assert np.allclose(got, i_r, rtol=1e-13, atol=1e-13 * max(abs(v) for v in x[:4])), (got, i_r)
+
+
+def test_reversed_saliency_pmsm_is_accepted_and_an_undefined_torque_limit_is_named():
+    """A PMSM with l_d > l_q: the reference's torque limit is NEGATIVE (-40.73 for the recorded set) and observations are normalised by
+    it; gemx_create accepts any finite non-zero limit (a zero one is still refused).  Where the reference's own limit is NaN the host
+    says why instead of 'math domain error' -- and a torque limit the user sets makes the motor usable again, as in the reference."""
+    meta = _meta("param_pmsm_reversed_cont_cc_free_held_euler")
+    ps = _make_param(meta).physical_system
+    assert ps.limits[1] < 0 and ps.limits[1] == pytest.approx(-40.73073764753616, rel=1e-13)
+    L = _lib.load()
+    h = C.c_void_p()
+    ok = _lib.GemxConfig.from_buffer_copy(ps._cfg)
+    rc = L.gemx_create(C.byref(ok), 4, 0, C.byref(h))  # (without a GPU: validation passes, the device step fails -- never on the limits)
+    if rc == 0:
+        L.gemx_destroy(h)
+    else:
+        assert b"limits" not in L.gemx_last_error(), L.gemx_last_error()
+    for v in (0.0, float("inf"), float("nan")):
+        bad = _lib.GemxConfig.from_buffer_copy(ps._cfg)
+        bad.limits[1] = v
+        assert L.gemx_create(C.byref(bad), 4, 0, C.byref(h)) == -1 and b"limits[1] must be non-zero and finite" in L.gemx_last_error()
+    mp = dict(meta["overrides"]["motor"]["motor_parameter"], psi_p=0.1)
+    with pytest.raises(ValueError, match=r"no real maximum-torque operating point for l_d > l_q at these psi_p / nominal current"):
+        ga.PermanentMagnetSynchronousMotor(motor_parameter=mp)
+    with pytest.raises(ValueError, match="no real maximum-torque operating point"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=2, motor=dict(motor_parameter=mp), _defer_create=True)
+    m = ga.PermanentMagnetSynchronousMotor(motor_parameter=mp, limit_values=dict(torque=50.0))
+    assert m.limits["torque"] == 50.0 and m.nominal_values["torque"] == 50.0
+
+
 ALL_ENV_IDS = [f"{a}-{c}-{m}-v0" for m in ("PermExDc", "SeriesDc", "ShuntDc", "ExtExDc", "PMSM", "SynRM", "SCIM", "EESM", "DFIM")
                for c in ("CC", "TC", "SC") for a in ("Cont", "Finite")]
 
@@ -327,6 +431,46 @@ def test_rc_supply_config():
         ga.make("Cont-CC-PermExDc-v0", n_envs=2, supply=AC1PhaseSupply(), _defer_create=True)
 
 
+def _check_induction_initialiser(d, case):
+    """An induction machine's random-initialiser config against 4000 resets of the live reference: static bounds for currents / angle,
+    the flux slots carry the interval only, init_flux what the per-reset flux bounds need (induction_motor.py:250-285), and the draw
+    RULE, restated in numpy from that config, passes KS tests against the reference's draws."""
+    from scipy import stats
+
+    meta, y = json.loads(str(d[case + "_meta"])), d[case + "_y"]
+    mcls = ga.SquirrelCageInductionMotor if "scim" in case else ga.DoublyFedInductionMotor
+    mkw = json.loads(json.dumps(meta.get("overrides", {}).get("motor", {})))  # (non-default parameter sets: init_samples_params.npz)
+    kw = dict(motor=mcls(motor_initializer=meta["motor_initializer"], **mkw), n_envs=2, seed=5, _defer_create=True)
+    if meta["load"] == "ConstantSpeedLoad":
+        kw["load"] = ga.ConstantSpeedLoad(omega_fixed=float(y[0, 0]))
+    c = ga.make(meta["env_id"], **kw).physical_system._cfg
+    mp = meta["motor_parameter"]
+    l_r = mp["l_m"] + mp["l_sigr"]
+    assert c.init_flux_mode == 1 and c.init_flux[1] == mp["p"] and abs(c.init_flux[5] - mp["l_m"] / l_r) < 1e-15 and c.init_flux[6] == mp["l_m"]
+    lo, hi, const, fl = (np.array(x[:8]) for x in (c.init_lo, c.init_hi, c.init_state, c.init_flux))
+    rng, prev, got = np.random.default_rng(3), None, np.zeros((4000, 6))
+    for k in range(4000):  # gemx_common.hpp:init_draw_all, operation by operation
+        u = rng.uniform(size=8)
+        v = np.array([lo[j] + (hi[j] - lo[j]) * u[j] if lo[j] < hi[j] and np.isfinite(lo[j]) else const[j] for j in range(8)])
+        eps = 2 * np.pi * u[7] - np.pi
+        ce, se, psi = np.cos(eps), np.sin(eps), fl[0]
+        if v[0] != 0:
+            ia, ib = (const[1], const[2]) if prev is None else (prev[1], prev[2])
+            i_d, i_q = ce * ia + se * ib, -se * ia + ce * ib
+            psi = 0.9 * min(max((fl[1] * v[0] * fl[2] * i_d + fl[3] * i_q + fl[4]) / (-fl[1] * v[0] * fl[5]), 0.0), abs(fl[6] * i_d))
+        for j, h in ((3, abs(psi * ce)), (4, abs(psi * se))):
+            a, b = max(-h, lo[j]), min(h, hi[j])
+            v[j] = a + (b - a) * u[j] if a < b else a
+        got[k], prev = v[:6], v
+    for j in range(6):
+        if np.ptp(y[:, j]) == 0:
+            assert np.ptp(got[:, j]) == 0 and got[0, j] == y[0, j]
+        else:
+            assert stats.ks_2samp(got[:, j], y[:, j]).pvalue > 1e-3, (case, j)
+    assert stats.ks_2samp(np.hypot(got[:, 3], got[:, 4]), np.hypot(y[:, 3], y[:, 4])).pvalue > 1e-3, case
+    return meta, c
+
+
 def test_random_initialiser_bounds_match_reference_support():
     """motor_initializer / load_initializer with random_init: the per-ODE-state sampling bounds (nominal value x state-space low,
     clipped to `interval`) cover exactly the support of 4000 resets of the live reference (tests/golden/init_samples.npz)."""
@@ -349,39 +493,8 @@ def test_random_initialiser_bounds_match_reference_support():
                 assert lo <= y[:, j].min() < lo + 0.01 * (hi - lo) and hi - 0.01 * (hi - lo) < y[:, j].max() <= hi
     # induction machines (round 4): static bounds for currents / angle, the flux slots carry the interval only, and init_flux what the
     # per-reset flux bounds need (induction_motor.py:250-285); the draw RULE, restated in numpy, passes KS tests against the reference
-    from scipy import stats
-
     for case in ("scim_sc_uniform", "scim_cc_negspeed_uniform", "dfim_cc_negspeed_interval_uniform"):
-        meta, y = json.loads(str(d[case + "_meta"])), d[case + "_y"]
-        mcls = ga.SquirrelCageInductionMotor if "scim" in case else ga.DoublyFedInductionMotor
-        kw = dict(motor=mcls(motor_initializer=meta["motor_initializer"]), n_envs=2, seed=5, _defer_create=True)
-        if meta["load"] == "ConstantSpeedLoad":
-            kw["load"] = ga.ConstantSpeedLoad(omega_fixed=float(y[0, 0]))
-        c = ga.make(meta["env_id"], **kw).physical_system._cfg
-        mp = meta["motor_parameter"]
-        l_r = mp["l_m"] + mp["l_sigr"]
-        assert c.init_flux_mode == 1 and c.init_flux[1] == mp["p"] and abs(c.init_flux[5] - mp["l_m"] / l_r) < 1e-15 and c.init_flux[6] == mp["l_m"]
-        lo, hi, const, fl = (np.array(x[:8]) for x in (c.init_lo, c.init_hi, c.init_state, c.init_flux))
-        rng, prev, got = np.random.default_rng(3), None, np.zeros((4000, 6))
-        for k in range(4000):  # gemx_common.hpp:init_draw_all, operation by operation
-            u = rng.uniform(size=8)
-            v = np.array([lo[j] + (hi[j] - lo[j]) * u[j] if lo[j] < hi[j] and np.isfinite(lo[j]) else const[j] for j in range(8)])
-            eps = 2 * np.pi * u[7] - np.pi
-            ce, se, psi = np.cos(eps), np.sin(eps), fl[0]
-            if v[0] != 0:
-                ia, ib = (const[1], const[2]) if prev is None else (prev[1], prev[2])
-                i_d, i_q = ce * ia + se * ib, -se * ia + ce * ib
-                psi = 0.9 * min(max((fl[1] * v[0] * fl[2] * i_d + fl[3] * i_q + fl[4]) / (-fl[1] * v[0] * fl[5]), 0.0), abs(fl[6] * i_d))
-            for j, h in ((3, abs(psi * ce)), (4, abs(psi * se))):
-                a, b = max(-h, lo[j]), min(h, hi[j])
-                v[j] = a + (b - a) * u[j] if a < b else a
-            got[k], prev = v[:6], v
-        for j in range(6):
-            if np.ptp(y[:, j]) == 0:
-                assert np.ptp(got[:, j]) == 0 and got[0, j] == y[0, j]
-            else:
-                assert stats.ks_2samp(got[:, j], y[:, j]).pvalue > 1e-3, (case, j)
-        assert stats.ks_2samp(np.hypot(got[:, 3], got[:, 4]), np.hypot(y[:, 3], y[:, 4])).pvalue > 1e-3, case
+        _check_induction_initialiser(d, case)
     # validation in gemx_create: induction-motor states need the flux mode, and a constant-speed omega cannot be random
     L = _lib.load()
     h = C.c_void_p()
@@ -394,6 +507,25 @@ def test_random_initialiser_bounds_match_reference_support():
     assert L.gemx_create(C.byref(bad), 4, 0, C.byref(h)) == -1 and b"ConstantSpeedLoad" in L.gemx_last_error()
     with pytest.raises(NotImplementedError):
         ga.DcPermanentlyExcitedMotor(motor_initializer=dict(random_init="cauchy"))
+
+
+@pytest.mark.parametrize("case", ["scim_sc_uniform", "scim_cc_negspeed_uniform", "dfim_cc_negspeed_uniform"])
+def test_induction_machine_initialiser_at_non_default_parameters(case):
+    """The flux bounds of the induction machines' random initialiser depend on l_m, l_sigs, l_sigr, r_s, r_r and p: at the non-default
+    sets of tests/golden/init_samples_params.npz (l_sigs != l_sigr, p = 3) every init_flux entry equals its formula evaluated on the
+    reference's recorded parameters and nominal state (induction_motor.py:250-285; doubly_fed_induction_motor.py:158-163), and the
+    restated draw rule passes the KS tests against the reference's resets."""
+    d = np.load(os.path.join(GOLDEN, "init_samples_params.npz"))
+    meta, c = _check_induction_initialiser(d, case)
+    mp, names, nom = meta["motor_parameter"], meta["state_names"], meta["nominal_state"]
+    assert mp["l_sigs"] != mp["l_sigr"] and mp["p"] == 3
+    l_s, l_r = mp["l_m"] + mp["l_sigs"], mp["l_m"] + mp["l_sigr"]
+    l_mr = mp["l_m"] / l_r
+    u_rq = nom[names.index("u_rq")] if "u_rq" in names else 0.0
+    want = [mp["l_m"] * nom[names.index("i_sd")], mp["p"], (l_s * l_r - mp["l_m"] ** 2) / l_r, mp["r_s"] + mp["r_r"] * l_mr ** 2,
+            nom[names.index("u_sq")] + l_mr * u_rq, l_mr, mp["l_m"], 0.0]
+    got = list(c.init_flux)[:8]
+    assert np.allclose(got, want, rtol=1e-14, atol=0), (got, want)
 
 
 def test_wiener_generator_margins_match_reference():
