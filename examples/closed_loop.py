@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Closed-loop use of the batched stepper: N current-controlled PMSM drives, device-side Wiener references, fused reward, a
-trivial proportional dq controller as the "policy" -- everything stays on the GPU, one launch per control step.
+trivial proportional dq controller as the "policy" -- everything stays on the GPU.
 
-    python examples/closed_loop.py [--envs 16384] [--steps 2000]
+    python examples/closed_loop.py [--envs 16384] [--steps 2000]                        # generator and reward wired by hand
+    python examples/closed_loop.py --complete [--bind | --graph 64]                     # the same loop through the complete env
+
+Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
+step per control step.  `--complete`: `ga.make(..., reference_generator="default")` does the wiring -- two launches per control step (physics +
+reward, then the fused generator step), `--bind` with everything resolved once (`env.bind_step`), `--graph S` with S control steps per HIP graph.
 
 The same loop with the reference package is `env.step(policy(obs))` on ONE env per Python call (reference: core.py:329-372).
 """
@@ -18,7 +23,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=16384)
     ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--complete", action="store_true", help="run the loop through the complete env of make(..., reference_generator='default')")
+    ap.add_argument("--bind", action="store_true", help="--complete: the pre-bound stepper (env.bind_step)")
+    ap.add_argument("--graph", type=int, default=0, metavar="S", help="--complete: S control steps per HIP graph")
     args = ap.parse_args()
+    if args.complete:
+        return complete(args)
     import torch
 
     import gym_electric_motor_amd as ga
@@ -47,11 +57,72 @@ def main():
         ref = gen.rollout(1)[0]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(f"{n} envs x {args.steps} closed-loop steps in {dt:.2f} s = {n * args.steps / dt / 1e6:.1f} M env-steps/s; "
+    print(f"hand-wired: {n} envs x {args.steps} closed-loop steps in {dt:.3f} s = {n * args.steps / dt / 1e6:.1f} M env-steps/s ({dt / args.steps * 1e6:.1f} us/step); "
           f"mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
     assert torch.isfinite(ret).all()
     env.close()
     gen.close()
+
+
+def complete(args):
+    import torch
+
+    import gym_electric_motor_amd as ga
+
+    n = args.envs
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),),
+                  reference_generator="default", seed=1)  # default generators (i_sd, i_sq) and reward weights (0.5, 0.5) of the env id
+    ps = env.physical_system
+    cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
+    gain = torch.tensor(8.0, device="cuda")
+    ret = torch.zeros(n, device="cuda")
+    action = torch.zeros((n, 2), device="cuda")
+    mode = "eager"
+    if args.bind or args.graph:
+        mode = "bind_step"
+        stream = torch.cuda.Stream() if args.graph else None
+        step, (state, ref), reward, done = env.bind_step(action, stream=stream)
+
+        def control_step():
+            torch.clamp(gain * (ref - state.index_select(1, cols)), -1, 1, out=action)
+            step()
+            ret.add_(reward)
+    (state, ref), _ = env.reset()
+    reps = args.steps
+    if args.graph:
+        mode = f"HIP graph of {args.graph} steps"
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            for _ in range(3):
+                control_step()
+            env.reset()
+            ret.zero_()
+        torch.cuda.current_stream().wait_stream(stream)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            for _ in range(args.graph):
+                control_step()
+        reps = args.steps // args.graph
+        run_one = graph.replay
+    elif args.bind:
+        run_one = control_step
+    else:
+        def run_one():
+            nonlocal state, ref
+            torch.clamp(gain * (ref - state.index_select(1, cols)), -1, 1, out=action)
+            (state, ref), reward, terminated, _, _ = env.step(action)
+            ret.add_(reward)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        run_one()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = reps * (args.graph or 1)
+    print(f"complete env ({mode}): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
+          f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
+    assert torch.isfinite(ret).all()
+    env.close()
 
 
 if __name__ == "__main__":

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""Policy in the loop, captured in a HIP graph: S control steps of (policy -> one gemx_step launch) are recorded once with
-torch.cuda.CUDAGraph (hipGraph on ROCm) and replayed, which removes the per-step Python and launch overhead of the closed loop.
+"""Policy in the loop, captured in a HIP graph: S control steps of (policy -> physics + reward launch -> reference generator launch) of
+the complete env are recorded once with torch.cuda.CUDAGraph (hipGraph on ROCm) and replayed, which removes the per-step Python and launch
+overhead of the closed loop.  The Wiener reference generators and the reward are inside the captured region: all generator state, the
+step index of its random draws included, lives in device memory, so every replay continues the reference processes.
 
     python examples/hip_graph_closed_loop.py [--envs 16384] [--steps 4096] [--capture 64]
 
-`simulate()` enqueues exactly one kernel on the current stream and never synchronises, so it can be captured as it is (no
-DeadTimeProcessor here: its queue position is a host-side launch argument).  The state lives in the handle's device buffers, so
-replays continue the simulation; observations go to the system's internal buffer, which the policy reads in place.
+`env.step()` enqueues exactly two kernels on the current stream and never synchronises, so it can be captured as it is (no
+DeadTimeProcessor here: its queue position is a host-side launch argument).  The state lives in the handles' device buffers, so
+replays continue the simulation; states, references and rewards go to the env's internal buffers, which the policy reads in place.
 """
 import argparse
 import os
@@ -27,27 +29,23 @@ def main():
     import gym_electric_motor_amd as ga
 
     n, S = args.envs, args.capture
-    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),))
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),),
+                  reference_generator="default", seed=1)    # Wiener references for (i_sd, i_sq), WeightedSumOfErrors reward: the env id's defaults
     ps = env.physical_system
-    isd, isq = ps.state_positions["i_sd"], ps.state_positions["i_sq"]
-    cols = torch.tensor([isd, isq], device="cuda")            # (device-resident index: no host -> device copy inside the capture)
-    target = torch.tensor([0.0, 0.3], device="cuda")         # constant dq current reference (normalised)
+    cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")  # (device-resident index: no host -> device copy inside the capture)
     gain = torch.tensor(8.0, device="cuda")
     action = torch.zeros((n, 2), device="cuda")               # static buffers: graph replays reuse these addresses
     cost = torch.zeros(n, device="cuda")
+    (state, ref), _ = env.reset()                             # the env's internal buffers [N, S_out], [N, n_ref]: every step rewrites them
 
-    def control_step(obs):
-        err = target - obs.index_select(1, cols)
-        torch.clamp(gain * err, -1, 1, out=action)            # "policy": proportional current controller in dq
-        cost.add_((err * err).sum(dim=1))
-        return ps.simulate(action)                            # ONE kernel launch, observations in ps's internal buffer
-
-    obs_buf, _ = env.reset()                                  # the system's internal observation buffer [N, S_out]: every step rewrites it
+    def control_step():
+        torch.clamp(gain * (ref - state.index_select(1, cols)), -1, 1, out=action)  # "policy": proportional current controller in dq
+        _, reward, _, _, _ = env.step(action)                 # TWO kernel launches: physics + reward, then the generators
+        cost.sub_(reward)
 
     def run_eager(steps):
-        obs = obs_buf
         for _ in range(steps):
-            obs = control_step(obs)
+            control_step()
 
     run_eager(8)                                              # warm-up (also builds the one-step map of the handle)
     torch.cuda.synchronize()

@@ -10,8 +10,12 @@
 // clipped random walk is the reference's.  Randomness: counter-based Philox4x32-10 (gemx_common.hpp) indexed by
 // (seed; env, generator, draw kind, draw index), so chunked == one-shot generation and no RNG state is stored.
 //
-// Two kernels per call: (1) all K*N*n_ref standard normals in parallel, written into the output tensor; (2) one lane per
+// Two kernels per rollout: (1) all K*N*n_ref standard normals in parallel, written into the output tensor; (2) one lane per
 // (env, generator) walks its K steps sequentially: scale by the sub-episode's sigma, accumulate, clip, restart on `done`.
+// One kernel per env-shell step (gemx_refgen_step): one lane per env resets its generators on `done`, draws the step's normal inline and
+// advances every generator by one step -- the same draws, the same double arithmetic, hence the same bits as a rollout.
+// The step index of the normal draws lives on the device, per (generator, env) like the other counters (every lane advances its own:
+// no lane reads a counter another lane writes), so a replayed HIP graph of steps advances the streams.
 #include "gemx_common.hpp"
 
 void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
@@ -24,7 +28,7 @@ struct gemx_refgen {
     double *value = nullptr, *sigma = nullptr;
     int32_t *left = nullptr;
     uint32_t *n_sub = nullptr, *n_reset = nullptr;
-    unsigned long long t_total = 0;  // steps generated so far (index of the per-step normal draws)
+    uint64_t *t = nullptr;  // steps generated so far (index of the per-step normal draws)
 };
 
 namespace {
@@ -44,19 +48,24 @@ __device__ inline void refgen_block(uint64_t seed, int64_t env, int gen, int kin
     for (int i = 0; i < 4; ++i) r[i] = c[i];
 }
 
-// (1) standard normals for steps t0 .. t0+K-1 of every (env, generator): Box-Muller on two Philox words
+// the standard normal of step t of (env, generator): Box-Muller on two Philox words, rounded to the tensor's type
+template <class R> __device__ inline R step_normal(uint64_t seed, int64_t global_env, int g, uint64_t t) {
+    uint32_t r[4];
+    refgen_block(seed, global_env, g, DRAW_STEP, t, r);  // (the GLOBAL env index keys the stream)
+    const double u1 = gemx::Philox::u01(r[0]), u2 = gemx::Philox::u01(r[1]);
+    return (R)(sqrt(-2.0 * log(u1)) * cos(gemx::kTwoPi * u2));
+}
+
+// (1) standard normals for steps t .. t+K-1 of every (env, generator), t = the (generator, env)'s step counter
 template <class R>
-__global__ void refgen_normals_kernel(R *out, int64_t N, int n_ref, int K, uint64_t seed, uint64_t t0, int64_t env_base) {
+__global__ void refgen_normals_kernel(R *out, int64_t N, int n_ref, int K, uint64_t seed, const uint64_t *t, int64_t env_base) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t total = (int64_t)K * N * n_ref;
     if (idx >= total) return;
     const int g = (int)(idx % n_ref);
     const int64_t env = (idx / n_ref) % N;
     const int64_t k = idx / ((int64_t)n_ref * N);
-    uint32_t r[4];
-    refgen_block(seed, env_base + env, g, DRAW_STEP, t0 + (uint64_t)k, r);  // (the GLOBAL env index keys the stream)
-    const double u1 = gemx::Philox::u01(r[0]), u2 = gemx::Philox::u01(r[1]);
-    out[idx] = (R)(sqrt(-2.0 * log(u1)) * cos(gemx::kTwoPi * u2));
+    out[idx] = step_normal<R>(seed, env_base + env, g, t[(int64_t)g * N + env] + (uint64_t)k);
 }
 
 struct RefgenDev {
@@ -95,7 +104,7 @@ __device__ inline double walk_step(const RefgenDev &G, int g, double value, doub
 // generators are reset before the reference of step k+1 is produced (env.reset() -> reference_generator.reset(), core.py:312-313).
 template <class R>
 __global__ void refgen_walk_kernel(R *out, const uint8_t *done, const uint8_t *reset_mask, int reset_all, int64_t N, int K, RefgenDev G,
-                                   double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset) {
+                                   double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset, uint64_t *t) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= N * G.n_ref) return;
     const int g = (int)(idx % G.n_ref);
@@ -116,6 +125,44 @@ __global__ void refgen_walk_kernel(R *out, const uint8_t *done, const uint8_t *r
         if (done != nullptr && done[(int64_t)k * N + env]) reset_generator(G, env, g, nr, ns, lf, sg, v);
     }
     value[si] = v; sigma[si] = sg; left[si] = lf; n_sub[si] = ns; n_reset[si] = nr;
+    if (K > 0) t[si] += (uint64_t)K;
+}
+
+// (3) one env-shell step, one lane per env: reset on done, then advance every generator by one step; row [n_ref] of `out` written at once
+// (VEC: n_ref in {2, 4} and an aligned tensor -> one vector store per lane)
+template <class R, int VEC>
+__global__ void refgen_step_kernel(R *out, const uint8_t *done, int64_t N, RefgenDev G, double *value, double *sigma, int32_t *left,
+                                   uint32_t *n_sub, uint32_t *n_reset, uint64_t *t) {
+    const int64_t env = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (env >= N) return;
+    const bool dn = done != nullptr && done[env];
+    R row[GEMX_MAX_REF];
+#pragma unroll
+    for (int g = 0; g < GEMX_MAX_REF; ++g) {
+        if (g >= G.n_ref) break;
+        const int64_t si = (int64_t)g * N + env;
+        double v = value[si], sg = sigma[si];
+        int32_t lf = left[si];
+        uint32_t ns = n_sub[si], nr = n_reset[si];
+        const uint64_t ti = t[si];
+        if (dn) reset_generator(G, env, g, nr, ns, lf, sg, v);
+        if (lf <= 0) new_subepisode(G, env, g, ns, lf, sg);
+        v = walk_step(G, g, v, sg, (double)step_normal<R>(G.seed, G.env_base + env, g, ti));
+        --lf;
+        value[si] = v; sigma[si] = sg; left[si] = lf; n_sub[si] = ns; n_reset[si] = nr; t[si] = ti + 1;
+        row[g] = (R)v;
+    }
+    if constexpr (VEC == 2) {
+        struct alignas(2 * sizeof(R)) V2 { R a, b; };
+        reinterpret_cast<V2 *>(out)[env] = V2{row[0], row[1]};
+    } else if constexpr (VEC == 4) {
+        struct alignas(sizeof(R) == 4 ? 16 : 32) V4 { R a, b, c, d; };
+        reinterpret_cast<V4 *>(out)[env] = V4{row[0], row[1], row[2], row[3]};
+    } else {
+#pragma unroll
+        for (int g = 0; g < GEMX_MAX_REF; ++g)
+            if (g < G.n_ref) out[env * G.n_ref + g] = row[g];
+    }
 }
 
 RefgenDev make_dev(const gemx_refgen_config &c) {
@@ -133,7 +180,23 @@ template <class R> int walk(gemx_refgen *r, void *out, const uint8_t *done, cons
     const int64_t lanes = r->n * r->cfg.n_ref;
     gemx_cov_note(sizeof(R) == 4 ? "refgen_walk_kernel<float>" : "refgen_walk_kernel<double>");
     hipLaunchKernelGGL(refgen_walk_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done, mask, reset_all, r->n, K, make_dev(r->cfg),
-                       r->value, r->sigma, r->left, r->n_sub, r->n_reset);
+                       r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t);
+    GEMX_HIP_TRY(hipGetLastError());
+    return GEMX_OK;
+}
+
+template <class R> int step(gemx_refgen *r, void *out, const uint8_t *done, hipStream_t st) {
+    const int n_ref = r->cfg.n_ref;
+    // one vector store per row where the rows are 2 or 4 wide and the tensor is aligned to them
+    const int vec = ((n_ref == 2 || n_ref == 4) && (uintptr_t)out % (n_ref * sizeof(R)) == 0) ? n_ref : 1;
+    gemx_cov_note(sizeof(R) == 4 ? "refgen_step_kernel<float>" : "refgen_step_kernel<double>");
+    const dim3 grid((unsigned)((r->n + 255) / 256)), block(256);
+    const RefgenDev G = make_dev(r->cfg);
+#define GEMX_REFGEN_STEP(V) hipLaunchKernelGGL((refgen_step_kernel<R, V>), grid, block, 0, st, (R *)out, done, r->n, G, r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t)
+    if (vec == 2) GEMX_REFGEN_STEP(2);
+    else if (vec == 4) GEMX_REFGEN_STEP(4);
+    else GEMX_REFGEN_STEP(1);
+#undef GEMX_REFGEN_STEP
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
 }
@@ -165,12 +228,12 @@ int gemx_refgen_create(const gemx_refgen_config *cfg, int64_t n_envs, int device
     const size_t m = (size_t)n_envs * cfg->n_ref;
     if (hipMalloc((void **)&r->value, m * 8) != hipSuccess || hipMalloc((void **)&r->sigma, m * 8) != hipSuccess ||
         hipMalloc((void **)&r->left, m * 4) != hipSuccess || hipMalloc((void **)&r->n_sub, m * 4) != hipSuccess ||
-        hipMalloc((void **)&r->n_reset, m * 4) != hipSuccess) {
+        hipMalloc((void **)&r->n_reset, m * 4) != hipSuccess || hipMalloc((void **)&r->t, m * 8) != hipSuccess) {
         gemx_refgen_destroy(r);
         return gemx::fail(GEMX_ERR_ALLOC, "hipMalloc(refgen) failed");
     }
     (void)hipMemset(r->value, 0, m * 8); (void)hipMemset(r->sigma, 0, m * 8); (void)hipMemset(r->left, 0, m * 4);
-    (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4);
+    (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4); (void)hipMemset(r->t, 0, m * 8);
     *out = r;
     return GEMX_OK;
 }
@@ -183,6 +246,7 @@ int gemx_refgen_destroy(gemx_refgen *r) {
     if (r->left) (void)hipFree(r->left);
     if (r->n_sub) (void)hipFree(r->n_sub);
     if (r->n_reset) (void)hipFree(r->n_reset);
+    if (r->t) (void)hipFree(r->t);
     delete r;
     return GEMX_OK;
 }
@@ -206,13 +270,23 @@ int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void
     gemx_cov_note(r->f64 ? "refgen_normals_kernel<double>" : "refgen_normals_kernel<float>");
     if (r->f64)
         hipLaunchKernelGGL(refgen_normals_kernel<double>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (double *)refs_out_dev, r->n, r->cfg.n_ref, K,
-                           r->cfg.seed, (uint64_t)r->t_total, r->cfg.env_base);
+                           r->cfg.seed, r->t, r->cfg.env_base);
     else
         hipLaunchKernelGGL(refgen_normals_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)refs_out_dev, r->n, r->cfg.n_ref, K,
-                           r->cfg.seed, (uint64_t)r->t_total, r->cfg.env_base);
+                           r->cfg.seed, r->t, r->cfg.env_base);
     GEMX_HIP_TRY(hipGetLastError());
-    r->t_total += (unsigned long long)K;
+    // (the walk kernel advances the step counters by K)
     return r->f64 ? walk<double>(r, refs_out_dev, done_dev, nullptr, 0, K, st) : walk<float>(r, refs_out_dev, done_dev, nullptr, 0, K, st);
+}
+
+// One env-shell step in ONE launch: the generators of envs with done_dev[env] != 0 (NULL: none) are reset, then every generator advances
+// by one step (core.py:351, get_reference_observation); refs_dev [N, n_ref] receives the new values.  K calls with the masks done[k-1]
+// give the rows of one gemx_refgen_rollout(K, done), bit for bit.  Nothing is kept on the host: a captured launch replays correctly.
+int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, void *stream) {
+    if (!r || !refs_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    gemx::DeviceGuard guard(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    return r->f64 ? step<double>(r, refs_dev, done_dev, st) : step<float>(r, refs_dev, done_dev, st);
 }
 
 // debug / test access: per (generator, env) arrays [n_ref][N]: value (double), sigma (double), steps left (int32)

@@ -12,15 +12,29 @@ reference env classes (supply voltage, converter, motor, load, tau, constraints)
     {Finite,Cont}-{CC,TC,SC}-DFIM-v0                          envs/gym_im/doubly_fed_induction_motor_envs/*.py (MultiConverter 2 x B6)
 (all 54 env ids of the reference.)
 
-Only the physical system + constraint monitor (done mask) are device-resident.  Reference generators, reward
-functions and visualisation are outside the accelerated path: `step()` returns
-`reward=None`.  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
-`physical_system=` to the reference's own `ElectricMotorEnvironment`.
+`make(env_id, n_envs=N)` alone gives the physical system + constraint monitor (done mask): `step()` returns `reward=None` and an
+observation without a reference.  Naming `reference_generator=` and / or `reward_function=` gives the COMPLETE env, with the per-id
+defaults of the reference's env classes (`default_env_modules`): device-side Wiener reference generators, the fused
+WeightedSumOfErrors reward, and the reference's shell semantics (core.py:300-371):
+
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator="default", seed=3)
+    (state, ref), _ = env.reset()                       # ref [N, n_ref]: initial value advanced once (core.py:313, 485-505)
+    (state, ref), reward, terminated, _, _ = env.step(actions)
+
+    step k:  launch 1  physics + reward against the references the PREVIOUS observation showed     (core.py:344-349)
+             launch 2  generators of terminated envs restart, every generator advances, `ref` rewritten  (core.py:351)
+
+Two kernel launches per step, no host round trip; `bind_step` resolves everything once and can be captured in a HIP graph.
+`state_filter`, visualisation and the reference's other generator kinds are outside the accelerated path.  For a full single-env GEM
+environment pass a `BatchedSCMLSystem(n_envs=1)` as `physical_system=` to the reference's own `ElectricMotorEnvironment`
+(INTEGRATION.md).
 """
 import re
 
+from .spaces import Box
 from . import components as comp
 from . import physical_systems as bps
+from .reference_generators import ReplayReferenceGenerator
 
 _ID = re.compile(r"^(Finite|Cont)-(CC|TC|SC)-(PermExDc|SeriesDc|ShuntDc|ExtExDc|PMSM|SynRM|SCIM|EESM|DFIM)-v0$")
 
@@ -112,6 +126,52 @@ def default_components(env_id):
     return d
 
 
+# Wiener generators whose arguments differ from WienerProcessReferenceGenerator's defaults (sigma_range (1e-3, 1e-1), limit_margin None =
+# nominal / limit): cont_cc_permex_dc_env.py:164, finite_cc_permex_dc_env.py:164, cont_tc_permex_dc_env.py:165, finite_tc_permex_dc_env.py:164,
+# cont_sc_permex_dc_env.py:169, finite_sc_permex_dc_env.py:170, cont_sc_series_dc_env.py:167, finite_sc_series_dc_env.py:167,
+# cont_sc_shunt_dc_env.py:169, finite_sc_shunt_dc_env.py:169, cont_sc_synrm_env.py:163, finite_sc_synrm_env.py:169, cont_sc_scim_env.py:171,
+# finite_sc_scim_env.py:176, cont_sc_dfim_env.py:181, finite_sc_dfim_env.py:181
+_SIGMA_RANGE = {
+    "Cont-CC-PermExDc-v0": (1e-2, 1e-1), "Finite-CC-PermExDc-v0": (1e-2, 1e-1), "Cont-TC-PermExDc-v0": (1e-2, 1e-1), "Finite-TC-PermExDc-v0": (1e-2, 1e-1),
+    "Cont-SC-PermExDc-v0": (1e-3, 5e-2), "Finite-SC-PermExDc-v0": (1e-3, 5e-3), "Cont-SC-SeriesDc-v0": (1e-3, 2e-2), "Finite-SC-SeriesDc-v0": (1e-3, 5e-3),
+    "Cont-SC-ShuntDc-v0": (1e-3, 3e-2), "Finite-SC-ShuntDc-v0": (1e-3, 5e-3), "Cont-SC-SynRM-v0": (1e-3, 1e-2), "Finite-SC-SynRM-v0": (1e-3, 1e-2),
+    "Cont-SC-SCIM-v0": (1e-3, 1e-2), "Finite-SC-SCIM-v0": (1e-3, 1e-2), "Cont-SC-DFIM-v0": (1e-3, 1e-2), "Finite-SC-DFIM-v0": (1e-3, 1e-2),
+}
+# cont_cc_eesm_env.py:153 (the excitation current's reference stays positive), cont_tc_shunt_dc_env.py:164
+_LIMIT_MARGIN = {"Cont-CC-EESM-v0": dict(i_e=(0, 1)), "Cont-TC-ShuntDc-v0": dict(torque=(0, 0.8))}
+
+
+def default_env_modules(env_id):
+    """Per-id defaults of the reference generator and the reward function, read off the reference env classes the way
+    `default_components` is (e.g. cont_cc_pmsm_env.py:146-152, cont_cc_eesm_env.py:149-156, cont_cc_extex_dc_env.py:149-155,
+    cont_tc_pmsm_env.py:151, cont_sc_pmsm_env.py:151): CC envs reference the current(s) with one WienerProcessReferenceGenerator each
+    (MultipleReferenceGenerator), TC envs the torque, SC envs omega; WeightedSumOfErrors with equal weights over the referenced
+    states, gamma 0.9, power 1, no bias, the derived violation reward.
+    -> dict(reference_states, generator=dict(BatchedWienerProcessReferenceGenerator arguments), reward=dict(set_reward keywords))."""
+    m = _ID.match(env_id)
+    if not m:
+        default_components(env_id)  # (raises the KeyError that names the supported ids)
+    _, control, motor = m.groups()
+    if control == "TC":
+        states = ("torque",)
+    elif control == "SC":
+        states = ("omega",)
+    elif motor in ("PermExDc", "SeriesDc"):
+        states = ("i",)
+    elif motor == "ShuntDc":
+        states = ("i_a",)
+    elif motor == "ExtExDc":
+        states = ("i_a", "i_e")
+    elif motor == "EESM":
+        states = ("i_sd", "i_sq", "i_e")
+    else:
+        states = ("i_sd", "i_sq")
+    gen = dict(sigma_range=_SIGMA_RANGE.get(env_id, (1e-3, 1e-1)), episode_lengths=(500, 2000), limit_margin=_LIMIT_MARGIN.get(env_id), initial_range=None)
+    reward = dict(reward_weights={s: 1.0 / len(states) for s in states}, gamma=0.9, reward_power=1, bias=0.0, violation_reward=None,
+                  normed_reward_weights=False)
+    return dict(reference_states=states, generator=gen, reward=reward)
+
+
 def default_ode_solver(env_id, tau=None, load=None):
     """The solver `make(env_id)` uses when the caller names none.  The reference's default is scipy's ADAPTIVE dopri5 (rtol 1e-6,
     solvers.py:139-184); the device integrates with fixed steps, so the default is chosen per env such that the fp32 trajectories stay
@@ -177,13 +237,141 @@ class BatchedElectricMotorEnv:
         self.physical_system.close()
 
 
+class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
+    """The batched counterpart of the reference's ElectricMotorEnvironment shell (core.py:197-371): physical system + constraint
+    monitor + reference generator + reward function, all on the device.  Observations are `(state [N, S_out], ref [N, n_ref])`;
+    both and `reward` / `terminated` are internal buffers that the next call overwrites, as `simulate()`'s are.
+
+    The reward of step k is computed against the references the agent saw before acting; then the generators advance and the
+    observation carries the advanced values.  An env that terminated in step k shows the first reference of its fresh generator: under
+    auto-reset its next step starts from the reset state, and that is the reference its reward will use."""
+
+    _REWARD_KEYS = ("reward_weights", "gamma", "reward_power", "bias", "violation_reward", "normed_reward_weights")
+
+    def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False):
+        super().__init__(physical_system)
+        ps = physical_system
+        d = default_modules or dict(reference_states=(), reward=dict())
+        if getattr(ps, "_obs_layout", "aos") != "aos":
+            raise ValueError("the complete env needs obs_layout='aos' (states [N, S_out])")
+        rf = dict(d["reward"]) if reward_function in (None, "default") else dict(reward_function)
+        unknown = sorted(set(rf) - set(self._REWARD_KEYS))
+        if unknown:
+            raise TypeError(f"reward_function: unknown keywords {unknown}; known: {list(self._REWARD_KEYS)}")
+        gen = reference_generator
+        if isinstance(gen, ReplayReferenceGenerator):  # its columns are the env id's referenced states unless it names its own
+            gen.set_modules(ps, _defer_create=_defer_create, default_states=d["reference_states"])
+        elif not gen.is_set:  # (a generator the caller has already announced to this system is taken as it is)
+            gen.set_modules(ps, _defer_create=_defer_create)
+        if gen.n_envs != ps.n_envs:
+            raise ValueError(f"the reference generator serves {gen.n_envs} envs, the physical system {ps.n_envs}")
+        self.reference_generator = gen
+        self.reference_names = list(gen.reference_names)
+        if isinstance(rf.get("reward_weights"), dict):  # weights on states the system does not have ('i_sum' of the shunt envs) cannot be served
+            missing = sorted(set(rf["reward_weights"]) - set(ps.state_names))
+            if missing:
+                raise ValueError(f"reward_weights name {missing}, which are not states of the physical system {list(ps.state_names)}")
+        self.reward_config = ps.set_reward(referenced_states=self.reference_names, **rf)
+        self.reward_range = ps.reward_range
+        lo, hi = gen.reference_space
+        self.reference_space = Box(lo, hi, dtype=float)
+        self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
+        self._bound = None
+        if _defer_create:
+            return
+        torch = bps._torch()
+        self._reward = torch.zeros((1, ps.n_envs), dtype=ps._tdtype, device=ps._tdev)
+        ps._reward_buf = self._reward  # (`physical_system.reward` shows the same buffer)
+        self._refs = gen.references
+        self._obs = (ps._obs, self._refs)
+
+    def reset(self, seed=None, options=None):
+        """All envs to the initial state, all generators restarted and advanced once (core.py:312-313, 485-505).
+        -> ((state, ref), {})."""
+        ps, gen = self.physical_system, self.reference_generator
+        ps.reset()
+        gen.reset()
+        gen.step(None)
+        return self._obs, {}
+
+    def _launchers(self, action_ptr, stream):
+        """The two launches of a step with everything resolved: physics + fused reward reading the generator's buffer, then the
+        generator step on the fresh done mask writing that same buffer."""
+        import ctypes as C
+
+        ps, gen = self.physical_system, self.reference_generator
+        L, check = ps._L, bps._lib.check
+        n_ref = int(self.reward_config.n_ref)
+        args = (C.c_void_p(action_ptr), 1, C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr),
+                C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
+        gen_step = gen.bind_step(ps._done, stream=stream)
+        call = L.gemx_rollout_reward
+
+        def physics(_args=args, _call=call):
+            rc = _call(ps._handle, *_args)
+            if rc:
+                check(rc)
+            ps._k += 1
+
+        return physics, gen_step
+
+    def step(self, actions, references=None):
+        """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches."""
+        if references is not None:
+            raise TypeError("the complete env generates its references: step(actions)")
+        ps = self.physical_system
+        torch = bps._torch()
+        a = ps._actions_to_device(actions, (ps._n_envs,))
+        stream = torch.cuda.current_stream(ps._tdev)
+        key = (a.data_ptr(), stream.cuda_stream)
+        if self._bound is None or self._bound[0] != key:  # (a loop that reuses its action tensor and stream resolves the launches once)
+            self._bound = (key, self._launchers(a.data_ptr(), stream), a, stream)
+        physics, gen_step = self._bound[1]
+        physics()
+        gen_step()
+        return self._obs, self._reward[0], ps._done, False, {}
+
+    def bind_step(self, action_buffer, stream=None):
+        """A zero-argument `step()` for a closed loop that reuses ONE action tensor: -> `(step, (state, ref), reward, done)`; `step()`
+        enqueues the two launches and returns `(state, ref)`.  Nothing is looked up, allocated or synchronised per call, and no step
+        index lives on the host, so `step` can be captured with `torch.cuda.graph` (a linear graph) and replayed -- with the Wiener
+        generators; a ReplayReferenceGenerator keeps its row index on the host and refuses to step while a stream is capturing."""
+        ps = self.physical_system
+        torch = bps._torch()
+        a = action_buffer
+        if not (torch.is_tensor(a) and a.device == ps._tdev and a.is_contiguous() and a.dtype is ps._want_dtype and a.numel() == ps._act_numel):
+            raise ValueError(f"bind_step needs a contiguous {ps._want_dtype} tensor of {ps._act_numel} elements on {ps._tdev}")
+        stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
+        physics, gen_step = self._launchers(a.data_ptr(), stream)
+        obs = self._obs
+
+        def step(_keep=(a, stream)):
+            physics()
+            gen_step()
+            return obs
+
+        return step, obs, self._reward[0], ps._done
+
+    def close(self):
+        self.reference_generator.close()
+        super().close()
+
+
 def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, load=None, ode_solver=None, tau=None,
-         constraints=None, dtype="float32", auto_reset=None, obs_layout="aos", physical_system_wrappers=(), **kwargs):
+         constraints=None, dtype="float32", auto_reset=None, obs_layout="aos", physical_system_wrappers=(), reference_generator=None,
+         reward_function=None, state_filter=None, **kwargs):
     """Build a batched env.  Component arguments follow the reference's env-arg convention (instance | dict | None).
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
-    (or the reference's own instances); they are folded into the kernel's action stage."""
+    (or the reference's own instances); they are folded into the kernel's action stage.
+    reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | ReplayReferenceGenerator;
+    reward_function: None | 'default' | dict of `set_reward` keywords.  Naming either one selects the complete env
+    (CompleteBatchedElectricMotorEnv), the other then takes the env id's default (`default_env_modules`); `seed` keys the default
+    generators like every other device random stream.  Both None: the physics-only env."""
     from .physical_system_wrappers import fold_wrappers
 
+    if state_filter is not None:
+        raise NotImplementedError("state_filter is outside the accelerated path: select the columns of the returned state tensor "
+                                  "(`physical_system.state_positions`) instead")
     if physical_system_wrappers:
         kwargs = dict(kwargs, **fold_wrappers(physical_system_wrappers))
     d = default_components(env_id)
@@ -207,4 +395,17 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         obs_layout=obs_layout,
         **kwargs,
     )
-    return BatchedElectricMotorEnv(system)
+    if reference_generator is None and reward_function is None:
+        return BatchedElectricMotorEnv(system)
+    from .reference_generators import BatchedWienerProcessReferenceGenerator
+
+    modules = default_env_modules(env_id)
+    if reference_generator is None or (isinstance(reference_generator, str) and reference_generator == "default"):
+        reference_generator = BatchedWienerProcessReferenceGenerator(reference_states=modules["reference_states"], seed=kwargs.get("seed", 0),
+                                                                     **modules["generator"])
+    elif isinstance(reference_generator, (str, type)):
+        raise ValueError("reference_generator: 'default', a BatchedWienerProcessReferenceGenerator or a ReplayReferenceGenerator instance")
+    if not (reward_function is None or isinstance(reward_function, dict) or (isinstance(reward_function, str) and reward_function == "default")):
+        raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
+    return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,
+                                           _defer_create=bool(kwargs.get("_defer_create", False)))

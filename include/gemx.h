@@ -28,13 +28,15 @@
 extern "C" {
 #endif
 
-#define GEMX_ABI_VERSION 7 /* 2: GEMX_MAX_OUT 16 -> 24 (DFIM system, 24 states); 3: gemx_config.solver_flags; 4: solver_rtol / solver_atol; 5: init_flux_mode / init_flux;
+#define GEMX_ABI_VERSION 8 /* 2: GEMX_MAX_OUT 16 -> 24 (DFIM system, 24 states); 3: gemx_config.solver_flags; 4: solver_rtol / solver_atol; 5: init_flux_mode / init_flux;
                             * 6: gemx_get_aux_state / gemx_set_aux_state / gemx_aux_state_bytes, gemx_reset_again; reset counters stay at 1 after gemx_create;
                             *    + gemx_rollout_synthetic / gemx_synthetic_actions, gemx_set_rate_limiter (new entry points only);
                             * 7: gemx_config.env_base / gemx_refgen_config.env_base: every device random stream is keyed by the GLOBAL env index
                             *    env_base + i (shards of one job draw what the unsharded job draws); gemx_rollout_half; gemx_config.solver_atol_omega; GEMX_SOLVER_ADAPTIVE
                             *    honours GEMX_SOLVER_SPLIT_KINKS; the initial-state streams are Threefry-4x32-12 (were Philox4x32-10: other draws from
-                            *    the same seed, same distributions); one unit library per (system, converter, dtype), loaded by gemx_create */
+                            *    the same seed, same distributions); one unit library per (system, converter, dtype), loaded by gemx_create;
+                            * 8: gemx_refgen_step (new entry point: one fused generator step per launch); the generators' step index moved from the host
+                            *    into device memory (gemx_refgen_rollout: same bits) */
 #define GEMX_MAX_ODE 8  /* ODE state length incl. omega and the angle      */
 #define GEMX_MAX_OUT 24 /* system-state (observation) length               */
 #define GEMX_MODEL_ROWS 5
@@ -306,7 +308,13 @@ int gemx_rollout_reward(gemx_handle *h, const void *actions_dev, int32_t K, cons
  * chunked generation == one-shot generation; parity with the reference's numpy streams is distributional.
  *   gemx_refgen_rollout(r, done, K, refs): refs[k, env, j] = reference the reward of control step k is computed against (what the agent
  *   saw as "next reference" before acting); done[k, env] != 0 (optional, the physics rollout's done tensor) resets that env's generators
- *   after step k, as `if terminated: env.reset()` does.  The tensor feeds gemx_rollout_reward directly. */
+ *   after step k, as `if terminated: env.reset()` does.  The tensor feeds gemx_rollout_reward directly.
+ *   gemx_refgen_step(r, done, refs) (ABI 8): one env-shell step of the generators in ONE launch -- the generators of envs with
+ *   done[env] != 0 (NULL: none) are reset, then every generator advances by one step; refs [N, n_ref] (R) receives the new values.  K calls
+ *   with the masks done[k-1] (none for the first) produce, row for row and bit for bit, what one gemx_refgen_rollout(K, done) of an
+ *   identically configured and seeded handle produces, and the two may be mixed on one handle in any order.  All generator state, the step
+ *   index of the draws included, lives in device memory: the call allocates nothing, never synchronises and can be captured in a HIP graph
+ *   whose replays advance the streams.  gemx_refgen_reset(NULL) + one gemx_refgen_step(NULL) is the env shell's reset() (core.py:485-505). */
 typedef struct gemx_refgen_config {
     int32_t struct_size; /* = sizeof(gemx_refgen_config) */
     int32_t n_ref;       /* 1..GEMX_MAX_REF sub-generators */
@@ -322,6 +330,7 @@ int gemx_refgen_create(const gemx_refgen_config *cfg, int64_t n_envs, int device
 int gemx_refgen_destroy(gemx_refgen *r);
 int gemx_refgen_reset(gemx_refgen *r, const uint8_t *mask_dev, void *stream);
 int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
+int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, void *stream);
 int gemx_refgen_get_state(gemx_refgen *r, double *value_out_dev, double *sigma_out_dev, int32_t *left_out_dev, void *stream);
 
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the

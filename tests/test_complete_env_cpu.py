@@ -1,0 +1,143 @@
+"""The complete env of `make(env_id, reference_generator=..., reward_function=...)` without a GPU: the per-id defaults of the reference
+generator and the reward function (`default_env_modules`) against what the reference's own 54 env classes resolve to
+(tests/golden/env_defaults.json, recorded by tools/record_env_defaults.py), and the argument handling of `make`.
+
+Integers and names compare exactly; doubles to 1e-12 relative, the tolerance of the other host-derived reference quantities."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
+REF = os.environ.get("GEM_REFERENCE", "/root/reference")
+RTOL = 1e-12
+
+with open(os.path.join(GOLDEN, "env_defaults.json")) as _f:
+    DEFAULTS = json.load(_f)
+
+
+def _close(got, want):
+    return np.allclose(np.asarray(got, dtype=float), np.asarray(want, dtype=float), rtol=RTOL, atol=0.0)
+
+
+def test_recorded_defaults_cover_the_54_env_ids():
+    import gym_electric_motor_amd as ga
+
+    assert len(DEFAULTS) == 54
+    for env_id in DEFAULTS:
+        ga.default_components(env_id)  # (every id is on the accelerated path)
+
+
+@pytest.mark.parametrize("env_id", sorted(DEFAULTS))
+def test_default_modules_match_the_reference_env_class(env_id):
+    """Referenced states and their order, every generator's margins / initial range / sigma range / episode lengths (the
+    gemx_refgen_config the env would create), the reward config by state name and the reward range."""
+    import gym_electric_motor_amd as ga
+
+    want = DEFAULTS[env_id]
+    env = ga.make(env_id, n_envs=8, reference_generator="default", _defer_create=True)
+    ps = env.physical_system
+    # the shunt envs' 'i_sum' column (CurrentSumProcessor) stays outside the accelerated path; everything else is matched by state name
+    ref_names = [n for n in want["state_names"] if n != "i_sum"]
+    assert ("i_sum" in want["state_names"]) == ("ShuntDc" in env_id)
+    assert list(ps.state_names) == ref_names
+    # MultipleReferenceGenerator concatenates its sub-generators in the order given, which is the state order for every env class
+    assert list(env.reference_names) == want["reference_names"]
+    assert [n for n, r in zip(want["state_names"], want["referenced_states"]) if r] == list(env.reference_names)
+    cfg = env.reference_generator._cfg
+    assert cfg.n_ref == len(want["generators"])
+    for j, (name, g) in enumerate(zip(env.reference_names, want["generators"])):
+        assert g["kind"] == "WienerProcessReferenceGenerator" and g["reference_state"] == name
+        assert [cfg.episode_len_lo, cfg.episode_len_hi] == g["episode_len_range"]
+        assert _close([cfg.margin_lo[j], cfg.margin_hi[j]], g["limit_margin"]), (name, cfg.margin_lo[j], cfg.margin_hi[j], g["limit_margin"])
+        assert _close([cfg.initial_lo[j], cfg.initial_hi[j]], g["initial_range"])
+        assert _close([cfg.sigma_lo[j], cfg.sigma_hi[j]], g["sigma_range"])
+    low, high = env.reference_space.low, env.reference_space.high
+    assert _close(low, want["reference_space"]["low"]) and _close(high, want["reference_space"]["high"])
+    assert env.observation_space[0] is env.state_space and env.observation_space[1] is env.reference_space
+    rc, rw = env.reward_config, want["reward"]
+    assert rc.n_ref == len(env.reference_names)
+    assert [ps.state_names[rc.ref_index[j]] for j in range(rc.n_ref)] == list(env.reference_names)
+    for i, name in enumerate(ps.state_names):
+        k = want["state_names"].index(name)
+        assert _close(rc.weight[i], rw["_reward_weights"][k]), name
+        assert rc.power[i] == rw["_n"][k], name
+    if "i_sum" in want["state_names"]:
+        assert rw["_reward_weights"][want["state_names"].index("i_sum")] == 0.0  # (nothing of the reward is lost with that column)
+    assert rc.bias == rw["_bias"]
+    assert _close(rc.violation_reward, rw["_violation_reward"])
+    assert ga.default_env_modules(env_id)["reward"]["gamma"] == rw["_gamma"]
+    assert _close(env.reward_range, rw["reward_range"])
+
+
+@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="needs the reference package (recording side)")
+def test_recorder_reproduces_the_committed_defaults(tmp_path):
+    out = tmp_path / "env_defaults.json"
+    env = dict(os.environ, MPLBACKEND="Agg", GEM_REFERENCE=REF)
+    subprocess.run([sys.executable, os.path.join(REPO, "tools", "record_env_defaults.py"), "--out", str(out)], check=True, cwd=REPO, env=env,
+                   stdout=subprocess.DEVNULL)
+    assert json.load(open(out)) == DEFAULTS
+
+
+def test_make_argument_handling():
+    import gym_electric_motor_amd as ga
+
+    with pytest.raises(NotImplementedError, match="state_filter"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=8, state_filter=["i_sd", "i_sq"], _defer_create=True)
+    with pytest.raises(NotImplementedError, match="state_filter"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator="default", state_filter=["omega"], _defer_create=True)
+    # neither named: today's physics-only env
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator=None, reward_function=None, _defer_create=True)
+    assert type(env) is ga.BatchedElectricMotorEnv and not hasattr(env, "reference_generator")
+    # naming one selects the complete env, the other takes its default
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=8, reward_function=dict(reward_weights=dict(i_sd=0.25, i_sq=0.75), gamma=0.5), _defer_create=True)
+    assert isinstance(env, ga.CompleteBatchedElectricMotorEnv) and env.reference_names == ["i_sd", "i_sq"]
+    ps = env.physical_system
+    assert env.reward_config.weight[ps.state_positions["i_sq"]] == 0.75 and env.reward_config.violation_reward == -2.0
+    with pytest.raises(TypeError, match="unknown keywords"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=8, reward_function=dict(weights=1.0), _defer_create=True)
+    with pytest.raises(ValueError, match="reference_generator"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator="wiener", _defer_create=True)
+    # the generator as an instance: per-generator settings by state name
+    gen = ga.BatchedWienerProcessReferenceGenerator(reference_states=("i_sq", "i_sd"), limit_margin=dict(i_sq=(0, 0.5)), sigma_range=dict(i_sd=(1e-2, 1e-1)))
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator=gen, _defer_create=True)
+    c = gen._cfg
+    assert env.reference_names == ["i_sd", "i_sq"]
+    assert (c.margin_lo[1], c.margin_hi[1]) == (0.0, 0.5) and _close([c.margin_lo[0], c.margin_hi[0]], [-0.6, 0.6])
+    assert (c.sigma_lo[0], c.sigma_hi[0]) == (1e-2, 1e-1) and (c.sigma_lo[1], c.sigma_hi[1]) == (1e-3, 1e-1)
+    assert (c.initial_lo[1], c.initial_hi[1]) == (0.0, 0.5)
+    with pytest.raises(ValueError, match="limit_margin"):
+        ga.BatchedWienerProcessReferenceGenerator(reference_states=("i_sd", "i_sq"), limit_margin=dict(i_e=(0, 1)))
+    with pytest.raises(ValueError, match="sigma_range"):
+        ga.BatchedWienerProcessReferenceGenerator(reference_states=("i_sd",), sigma_range=dict(omega=(1e-3, 1e-2)))
+    # replayed profiles: the env id's referenced states unless named; the column count must fit
+    rep = ga.ReplayReferenceGenerator(np.zeros((5, 2)))
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator=rep, _defer_create=True)
+    assert env.reference_names == ["i_sd", "i_sq"] and np.array_equal(env.reference_space.low, [-1.0, -1.0])
+    with pytest.raises(ValueError, match="columns"):
+        ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator=ga.ReplayReferenceGenerator(np.zeros((5, 3))), _defer_create=True)
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=8, reference_generator=ga.ReplayReferenceGenerator(np.zeros((5, 1)), reference_states="torque"), _defer_create=True)
+    assert env.reference_names == ["torque"]
+
+
+def test_physics_only_step_still_returns_no_reward_signature():
+    """`make()` without the new keywords is the env it was: same class, same step signature."""
+    import inspect
+
+    import gym_electric_motor_amd as ga
+
+    env = ga.make("Finite-CC-PMSM-v0", n_envs=4, _defer_create=True)
+    assert type(env) is ga.BatchedElectricMotorEnv
+    assert list(inspect.signature(env.step).parameters) == ["actions", "references"]
+
+
+def test_abi_lists_the_fused_generator_step():
+    from gym_electric_motor_amd import _lib
+
+    assert "gemx_refgen_step" in _lib.EXPORTS
+    header = open(os.path.join(REPO, "include", "gemx.h")).read()
+    assert "int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, void *stream);" in header
