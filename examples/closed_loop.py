@@ -4,6 +4,7 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
 
     python examples/closed_loop.py [--envs 16384] [--steps 2000]                        # generator and reward wired by hand
     python examples/closed_loop.py --complete [--bind | --graph 64]                     # the same loop through the complete env
+    python examples/closed_loop.py --complete --graph 64 --reference step               # ... on step (sinusoidal, ...) profiles
 
 Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
 step per control step.  `--complete`: `ga.make(..., reference_generator="default")` does the wiring -- two launches per control step (physics +
@@ -19,6 +20,11 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+# --reference KIND -> the holder class of the reference's generator of that kind ('wiener': the env id's default generators)
+REFERENCES = dict(wiener=None, sinusoidal="SinusoidalReferenceGenerator", step="StepReferenceGenerator", triangular="TriangularReferenceGenerator",
+                  sawtooth="SawtoothReferenceGenerator", laplace="LaplaceProcessReferenceGenerator", constant="ConstReferenceGenerator")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=16384)
@@ -26,7 +32,11 @@ def main():
     ap.add_argument("--complete", action="store_true", help="run the loop through the complete env of make(..., reference_generator='default')")
     ap.add_argument("--bind", action="store_true", help="--complete: the pre-bound stepper (env.bind_step)")
     ap.add_argument("--graph", type=int, default=0, metavar="S", help="--complete: S control steps per HIP graph")
+    ap.add_argument("--reference", default="wiener", metavar="KIND", choices=sorted(REFERENCES),
+                    help="--complete: the kind of the i_sd / i_sq reference generators: " + ", ".join(sorted(REFERENCES)))
     args = ap.parse_args()
+    if args.reference != "wiener" and not args.complete:
+        ap.error("--reference needs --complete")
     if args.complete:
         return complete(args)
     import torch
@@ -70,8 +80,13 @@ def complete(args):
     import gym_electric_motor_amd as ga
 
     n = args.envs
+    generator = "default"  # default generators (i_sd, i_sq) and reward weights (0.5, 0.5) of the env id
+    if args.reference != "wiener":  # one holder per referenced state; the columns of one device handle
+        holder = getattr(ga, REFERENCES[args.reference])
+        kw = dict() if args.reference in ("laplace", "constant") else dict(frequency_range=(5, 50), amplitude_range=(0.1, 0.4))
+        generator = [holder(reference_state=s, **kw) for s in ("i_sd", "i_sq")]
     env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),),
-                  reference_generator="default", seed=1)  # default generators (i_sd, i_sq) and reward weights (0.5, 0.5) of the env id
+                  reference_generator=generator, seed=1)
     ps = env.physical_system
     cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
     gain = torch.tensor(8.0, device="cuda")
@@ -119,7 +134,7 @@ def complete(args):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     steps = reps * (args.graph or 1)
-    print(f"complete env ({mode}): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
+    print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
           f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
     assert torch.isfinite(ret).all()
     env.close()

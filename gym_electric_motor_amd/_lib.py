@@ -6,7 +6,7 @@ import os
 from . import build as _build
 
 MAX_ODE, MAX_OUT, MODEL_ROWS, MODEL_COLS = 8, 24, 5, 11
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 SYS_DC_PERMEX, SYS_SYNC, SYS_SCIM, SYS_DC_SERIES, SYS_DC_SHUNT, SYS_DC_EXTEX, SYS_EESM, SYS_DFIM = 0, 1, 2, 3, 4, 5, 6, 7
 CONV_CONT_4QC, CONV_FINITE_B6, CONV_CONT_B6, CONV_FINITE_4QC = 0, 1, 2, 3
@@ -79,10 +79,29 @@ class GemxRefgenConfig(C.Structure):
     ]
 
 
+REF_WIENER, REF_LAPLACE, REF_SINUS, REF_STEP, REF_TRIANGULAR, REF_SAWTOOTH, REF_CONST = range(7)  # GEMX_REF_*
+
+
+class GemxRefgenKindsConfig(C.Structure):
+    """Mirror of `gemx_refgen_kinds_config` (include/gemx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_ref", C.c_int32), ("seed", C.c_uint64), ("env_base", C.c_int64), ("tau", C.c_double),
+        ("kind", C.c_int32 * MAX_REF), ("episode_len_lo", C.c_int32 * MAX_REF), ("episode_len_hi", C.c_int32 * MAX_REF),
+        ("margin_lo", C.c_double * MAX_REF), ("margin_hi", C.c_double * MAX_REF),
+        ("sigma_lo", C.c_double * MAX_REF), ("sigma_hi", C.c_double * MAX_REF),
+        ("initial_lo", C.c_double * MAX_REF), ("initial_hi", C.c_double * MAX_REF),
+        ("amplitude_lo", C.c_double * MAX_REF), ("amplitude_hi", C.c_double * MAX_REF),
+        ("frequency_lo", C.c_double * MAX_REF), ("frequency_hi", C.c_double * MAX_REF),
+        ("offset_lo", C.c_double * MAX_REF), ("offset_hi", C.c_double * MAX_REF),
+        ("reference_value", C.c_double * MAX_REF),
+    ]
+
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
-    "gemx_refgen_rollout", "gemx_refgen_get_state", "gemx_refgen_step",
+    "gemx_refgen_rollout", "gemx_refgen_get_state", "gemx_refgen_step", "gemx_refgen_create_kinds", "gemx_refgen_get_params",
     "gemx_reset", "gemx_step", "gemx_rollout", "gemx_rollout_half", "gemx_get_state", "gemx_set_state", "gemx_get_switch_state",
     "gemx_set_switch_state", "gemx_aux_state_bytes", "gemx_get_aux_state", "gemx_set_aux_state", "gemx_reset_again", "gemx_rollout_synthetic", "gemx_synthetic_actions", "gemx_set_rate_limiter", "gemx_set_steps_per_block", "gemx_last_launch", "gemx_error_flags", "gemx_debug_read",
 )
@@ -131,6 +150,8 @@ def load():
     L.gemx_rollout_half.argtypes = [vp, vp, i32, vp, vp, vp]
     L.gemx_set_reward.argtypes = [vp, C.POINTER(GemxRewardConfig)]
     L.gemx_refgen_create.argtypes = [C.POINTER(GemxRefgenConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_refgen_create_kinds.argtypes = [C.POINTER(GemxRefgenKindsConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_refgen_get_params.argtypes = [vp, vp, vp, vp]
     L.gemx_refgen_destroy.argtypes = [vp]
     L.gemx_refgen_reset.argtypes = [vp, vp, vp]
     L.gemx_refgen_rollout.argtypes = [vp, vp, i32, vp, vp]

@@ -16,6 +16,11 @@
 // advances every generator by one step -- the same draws, the same double arithmetic, hence the same bits as a rollout.
 // The step index of the normal draws lives on the device, per (generator, env) like the other counters (every lane advances its own:
 // no lane reads a counter another lane writes), so a replayed HIP graph of steps advances the streams.
+//
+// The reference's other kinds (gemx_refgen_create_kinds; second half of this file): Laplace walk, sinusoidal, step, triangular, sawtooth
+// and constant columns, freely mixed with Wiener columns.  ONE kernel (refgen_kinds_kernel) serves reset, rollout and step: one lane per
+// (env, column) keeps the sub-episode's drawn parameters in SoA arrays and evaluates its waveform in closed form at its step index --
+// nothing is tabulated.  A Wiener column there makes the draws and the arithmetic of the kernels above: the same bits.
 #include "gemx_common.hpp"
 
 void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
@@ -29,6 +34,13 @@ struct gemx_refgen {
     int32_t *left = nullptr;
     uint32_t *n_sub = nullptr, *n_reset = nullptr;
     uint64_t *t = nullptr;  // steps generated so far (index of the per-step normal draws)
+    // handles of gemx_refgen_create_kinds: a kind per column (`cfg` then holds the Wiener view of the columns; `mixed`: the handle runs
+    // refgen_kinds_kernel, else its columns are all Wiener and it runs the kernels above) and, per (column, env), the sub-episode's
+    // length, the waveform's parameters par[6][n_ref][N] (amplitude, frequency, offset, phase, width | ratio, roll)
+    gemx_refgen_kinds_config kcfg;
+    int has_kinds = 0, mixed = 0;
+    int32_t *len = nullptr;
+    double *par = nullptr;
 };
 
 namespace {
@@ -201,7 +213,236 @@ template <class R> int step(gemx_refgen *r, void *out, const uint8_t *done, hipS
     return GEMX_OK;
 }
 
+// ---- the other generator kinds (paths relative to reference_generators/) ----------------------------------------------------------------
+// Draw layout of a column, all blocks keyed (seed; global env, column, draw kind, index):
+//   DRAW_STEP  index t      word 0, 1: the step's normal (Wiener)          | word 0: the step's Laplace increment (Laplace)
+//   DRAW_SUB   index n_sub  word 0: sub-episode length (every kind)        | word 1: sigma (Wiener, Laplace) or amplitude; word 2: frequency;
+//                           word 3: offset
+//   DRAW_SUB2  index n_sub  word 0: phase (sinus, triangular, sawtooth) or the high/low ratio (step); word 1: width (triangular) or the
+//                           roll's phase (step)
+//   DRAW_RESET index n_reset word 0: initial value (Wiener only; the other kinds restart from 0 and draw nothing)
+enum { DRAW_SUB2 = 3 };
+enum { PAR_AMP = 0, PAR_FREQ = 1, PAR_OFF = 2, PAR_PHASE = 3, PAR_WIDTH = 4, PAR_ROLL = 5, N_PAR = 6 };
+
+struct RefgenKindsDev {
+    int32_t n_ref;
+    uint64_t seed;
+    int64_t env_base;
+    double tau;
+    int32_t kind[GEMX_MAX_REF], len_lo[GEMX_MAX_REF], len_hi[GEMX_MAX_REF];
+    double log_sig_lo[GEMX_MAX_REF], log_sig_hi[GEMX_MAX_REF], m_lo[GEMX_MAX_REF], m_hi[GEMX_MAX_REF], i_lo[GEMX_MAX_REF], i_hi[GEMX_MAX_REF];
+    double a_lo[GEMX_MAX_REF], a_hi[GEMX_MAX_REF], f_lo[GEMX_MAX_REF], f_hi[GEMX_MAX_REF], o_lo[GEMX_MAX_REF], o_hi[GEMX_MAX_REF], c[GEMX_MAX_REF];
+};
+
+struct KindLane {  // the state of one (column, env), in registers
+    double v, sg, amp, freq, off, phase, width, roll;
+    int32_t lf, len;
+    uint32_t ns, nr;
+    uint64_t t;
+};
+
+__device__ inline double clip(double x, double a, double b) { return fmin(fmax(x, a), b); }  // np.clip: min(max(x, a), b), also for a > b
+__device__ inline double uniform(double lo, double hi, uint32_t w) { return (hi - lo) * gemx::Philox::u01(w) + lo; }  // _get_current_value, 112-119
+
+// scipy.signal.sawtooth(x, w), restated: m = x mod 2 pi; rising from -1 to 1 on [0, 2 pi w), falling back on [2 pi w, 2 pi)
+__device__ inline double sawtooth(double x, double w) {
+    const double m = fmod(x, gemx::kTwoPi);  // (x >= 0: fmod is numpy's mod)
+    return m < gemx::kTwoPi * w ? m / (gemx::kPi * w) - 1.0 : (gemx::kPi * (w + 1.0) - m) / (gemx::kPi * (1.0 - w));
+}
+
+// get_reference_observation, subepisoded_reference_generator.py:93-99, and the kinds' _reset_reference: length, then the parameters in the
+// reference's order (amplitude, frequency, offset, extras)
+__device__ inline void kinds_new_subepisode(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
+    uint32_t r[4], q[4];
+    const int kind = G.kind[g];
+    refgen_block(G.seed, G.env_base + env, g, DRAW_SUB, s.ns, r);
+    s.len = (int32_t)((double)(G.len_hi[g] - G.len_lo[g]) * gemx::Philox::u01(r[0]) + (double)G.len_lo[g]);
+    s.lf = s.len;
+    if (kind == GEMX_REF_WIENER || kind == GEMX_REF_LAPLACE) {  // wiener ... :31, laplace ... :27
+        s.sg = pow(10.0, (G.log_sig_hi[g] - G.log_sig_lo[g]) * gemx::Philox::u01(r[1]) + G.log_sig_lo[g]);
+    } else {
+        refgen_block(G.seed, G.env_base + env, g, DRAW_SUB2, s.ns, q);
+        s.amp = uniform(G.a_lo[g], G.a_hi[g], r[1]);
+        s.freq = uniform(G.f_lo[g], G.f_hi[g], r[2]);
+        // sinusoidal ... :53-57 (triangle, sawtooth alike): [-m_hi + A, m_hi - A]; step_reference_generator.py:41-45: [m_lo + A, m_hi - A]
+        const double lo = (kind == GEMX_REF_STEP ? G.m_lo[g] : -G.m_hi[g]) + s.amp, hi = G.m_hi[g] - s.amp;
+        s.off = uniform(clip(G.o_lo[g], lo, hi), clip(G.o_hi[g], lo, hi), r[3]);
+        const double u0 = gemx::Philox::u01(q[0]), u1 = gemx::Philox::u01(q[1]);
+        s.phase = 0.0; s.width = 1.0; s.roll = 0.0;
+        if (kind == GEMX_REF_STEP) {
+            s.width = u0 < 0.5 ? sqrt(0.5 * u0) : 1.0 - sqrt(0.5 * (1.0 - u0));  // Triangular(0, 0.5, 1) by its inverse distribution function
+            s.roll = floor(fmin(1.0 / s.freq / G.tau * u1, 2147483647.0));      // int(steps_per_period * phase), :56-58
+        } else {
+            s.phase = u0 * 2.0 * gemx::kPi;
+            if (kind == GEMX_REF_TRIANGULAR) s.width = u1;
+        }
+    }
+    ++s.ns;
+}
+
+// reset(): Wiener draws its initial value (wiener ... :43-49), every other sub-episoded kind restarts from 0 (subepisoded ... :80-86);
+// a new sub-episode starts with the next step.  (Constant columns never get here: refgen_kinds_kernel writes their value and returns.)
+__device__ inline void kinds_reset(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
+    const int kind = G.kind[g];
+    if (kind == GEMX_REF_WIENER) {
+        uint32_t r[4];
+        refgen_block(G.seed, G.env_base + env, g, DRAW_RESET, s.nr++, r);
+        s.v = (G.i_hi[g] - G.i_lo[g]) * gemx::Philox::u01(r[0]) + G.i_lo[g];
+    } else {
+        s.v = 0.0;
+    }
+    s.lf = 0;
+}
+
+template <class R> __device__ inline double kinds_advance(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
+    const int kind = G.kind[g];
+    if (s.lf <= 0) kinds_new_subepisode(G, env, g, s);
+    const int32_t k = s.len - s.lf;  // index inside the sub-episode
+    const double m_lo = G.m_lo[g], m_hi = G.m_hi[g];
+    double v;
+    if (kind == GEMX_REF_WIENER) {  // (walk_step's arithmetic on step_normal's draw: the bits of the all-Wiener kernels)
+        v = s.v + s.sg * (double)step_normal<R>(G.seed, G.env_base + env, g, s.t);
+        if (v > m_hi) v = m_hi;
+        if (v < m_lo) v = m_lo;
+    } else if (kind == GEMX_REF_LAPLACE) {  // laplace ... :28-37; numpy's laplace(0, b): b log(2U) below the median, -b log(2(1 - U)) above
+        uint32_t r[4];
+        refgen_block(G.seed, G.env_base + env, g, DRAW_STEP, s.t, r);
+        const double u = gemx::Philox::u01(r[0]);
+        v = s.v + s.sg * (u < 0.5 ? log(2.0 * u) : -log(2.0 * (1.0 - u)));
+        if (v > m_hi) v = m_hi;
+        if (v < m_lo) v = m_lo;
+    } else if (kind == GEMX_REF_STEP) {  // step ... :47-61
+        const int64_t L = s.len;
+        int64_t j = ((int64_t)k - (int64_t)s.roll) % L;
+        if (j < 0) j += L;
+        const double x = s.freq * fmod((double)j * G.tau, 1.0 / s.freq) - s.width;
+        v = clip(s.amp * (double)((x > 0.0) - (x < 0.0)) + s.off, m_lo, m_hi);
+    } else {
+        const double x = gemx::kTwoPi * s.freq * ((double)k * G.tau) + s.phase;
+        const double w = kind == GEMX_REF_SINUS ? sin(x) : sawtooth(x, s.width);
+        v = clip(s.amp * w + s.off, m_lo, m_hi);
+    }
+    s.v = v;
+    --s.lf;
+    ++s.t;
+    return v;
+}
+
+// reset (K = 0: the envs of reset_mask, or all), rollout (K steps, reset AFTER step k where done_post[k][env]) and step (K = 1, reset
+// BEFORE the step where done_pre[env]): out[k][env][g], adjacent lanes write adjacent columns.
+template <class R>
+__global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
+                                    int K, RefgenKindsDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
+                                    uint64_t *t, int32_t *len, double *par) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= N * G.n_ref) return;
+    const int g = (int)(idx % G.n_ref);
+    const int64_t env = idx / G.n_ref;
+    const int64_t si = (int64_t)g * N + env, stride = (int64_t)G.n_ref * N;
+    const int kind = G.kind[g];
+    if (kind == GEMX_REF_CONST) {  // no state at all
+        for (int k = 0; k < K; ++k) out[((int64_t)k * N + env) * G.n_ref + g] = (R)G.c[g];
+        return;
+    }
+    // the waveform's parameters are read by the waveform kinds only, and -- like sigma and the length -- written back only by a lane that
+    // started a sub-episode in this launch (one launch in hundreds): a step moves ~50 B per lane instead of ~180
+    const bool wave = kind != GEMX_REF_WIENER && kind != GEMX_REF_LAPLACE;
+    KindLane s;
+    s.v = value[si]; s.sg = sigma[si]; s.lf = left[si]; s.ns = n_sub[si]; s.nr = n_reset[si]; s.t = t[si]; s.len = len[si];
+    s.amp = s.freq = s.off = s.phase = s.roll = 0.0; s.width = 1.0;
+    if (wave) {
+        s.amp = par[PAR_AMP * stride + si]; s.freq = par[PAR_FREQ * stride + si]; s.off = par[PAR_OFF * stride + si];
+        s.phase = par[PAR_PHASE * stride + si]; s.width = par[PAR_WIDTH * stride + si]; s.roll = par[PAR_ROLL * stride + si];
+    }
+    const uint32_t ns0 = s.ns, nr0 = s.nr;
+    if (K == 0) {
+        if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, s);
+    } else if (done_pre != nullptr && done_pre[env]) {
+        kinds_reset(G, env, g, s);
+    }
+    for (int k = 0; k < K; ++k) {
+        out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, s);
+        if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, s);
+    }
+    value[si] = s.v; left[si] = s.lf; t[si] = s.t;
+    if (s.nr != nr0) n_reset[si] = s.nr;
+    if (s.ns != ns0) {
+        n_sub[si] = s.ns; sigma[si] = s.sg; len[si] = s.len;
+        if (wave) {
+            par[PAR_AMP * stride + si] = s.amp; par[PAR_FREQ * stride + si] = s.freq; par[PAR_OFF * stride + si] = s.off;
+            par[PAR_PHASE * stride + si] = s.phase; par[PAR_WIDTH * stride + si] = s.width; par[PAR_ROLL * stride + si] = s.roll;
+        }
+    }
+}
+
+RefgenKindsDev make_kinds_dev(const gemx_refgen_kinds_config &c) {
+    RefgenKindsDev G;
+    memset(&G, 0, sizeof(G));
+    G.n_ref = c.n_ref; G.seed = c.seed; G.env_base = c.env_base; G.tau = c.tau;
+    for (int g = 0; g < c.n_ref; ++g) {
+        G.kind[g] = c.kind[g]; G.len_lo[g] = c.episode_len_lo[g]; G.len_hi[g] = c.episode_len_hi[g];
+        G.m_lo[g] = c.margin_lo[g]; G.m_hi[g] = c.margin_hi[g]; G.c[g] = c.reference_value[g];
+        if (c.kind[g] == GEMX_REF_WIENER || c.kind[g] == GEMX_REF_LAPLACE) {
+            G.log_sig_lo[g] = log10(c.sigma_lo[g]); G.log_sig_hi[g] = log10(c.sigma_hi[g]);
+            G.i_lo[g] = c.initial_lo[g]; G.i_hi[g] = c.initial_hi[g];
+        } else {  // the reference's set_modules (e.g. sinusoidal ... :42-48): amplitudes within half the margin's width, offsets within the margin
+            const double half = (c.margin_hi[g] - c.margin_lo[g]) / 2;
+            G.a_lo[g] = fmin(fmax(c.amplitude_lo[g], 0.0), half); G.a_hi[g] = fmin(fmax(c.amplitude_hi[g], 0.0), half);
+            G.o_lo[g] = fmin(fmax(c.offset_lo[g], c.margin_lo[g]), c.margin_hi[g]); G.o_hi[g] = fmin(fmax(c.offset_hi[g], c.margin_lo[g]), c.margin_hi[g]);
+            G.f_lo[g] = c.frequency_lo[g]; G.f_hi[g] = c.frequency_hi[g];
+        }
+    }
+    return G;
+}
+
+template <class R>
+int kinds_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+    const int64_t lanes = r->n * r->kcfg.n_ref;
+    gemx_cov_note(sizeof(R) == 4 ? "refgen_kinds_kernel<float>" : "refgen_kinds_kernel<double>");
+    hipLaunchKernelGGL(refgen_kinds_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
+                       make_kinds_dev(r->kcfg), r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par);
+    GEMX_HIP_TRY(hipGetLastError());
+    return GEMX_OK;
+}
+int kinds(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+    return r->f64 ? kinds_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
+                  : kinds_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
+}
+
+// small kernel of gemx_refgen_get_params: kind / step index / length per (column, env)
+__global__ void refgen_kinds_index_kernel(int32_t *out, int64_t N, int n_ref, int mixed, RefgenKindsDev G, const int32_t *left, const int32_t *len) {
+    const int64_t si = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = N * n_ref;
+    if (si >= m) return;
+    out[si] = G.kind[si / N];
+    out[m + si] = mixed ? len[si] - left[si] : -1;
+    out[2 * m + si] = mixed ? len[si] : -1;
+}
+
 }  // namespace
+
+// the handle and its zeroed per-(column, env) arrays; kcfg != NULL: a gemx_refgen_create_kinds handle (cfg: the Wiener view of its columns)
+static int gemx_refgen_alloc(const gemx_refgen_config &cfg, const gemx_refgen_kinds_config *kcfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
+    gemx::DeviceGuard guard(device);
+    gemx_refgen *r = new (std::nothrow) gemx_refgen();
+    if (!r) return gemx::fail(GEMX_ERR_ALLOC, "out of host memory");
+    r->cfg = cfg; r->n = n_envs; r->device = device; r->f64 = dtype == GEMX_F64;
+    memset(&r->kcfg, 0, sizeof(r->kcfg));
+    if (kcfg) { r->kcfg = *kcfg; r->has_kinds = 1; }
+    const size_t m = (size_t)n_envs * cfg.n_ref;
+    if (hipMalloc((void **)&r->value, m * 8) != hipSuccess || hipMalloc((void **)&r->sigma, m * 8) != hipSuccess ||
+        hipMalloc((void **)&r->left, m * 4) != hipSuccess || hipMalloc((void **)&r->n_sub, m * 4) != hipSuccess ||
+        hipMalloc((void **)&r->n_reset, m * 4) != hipSuccess || hipMalloc((void **)&r->t, m * 8) != hipSuccess ||
+        (kcfg && (hipMalloc((void **)&r->len, m * 4) != hipSuccess || hipMalloc((void **)&r->par, m * 8 * N_PAR) != hipSuccess))) {
+        gemx_refgen_destroy(r);
+        return gemx::fail(GEMX_ERR_ALLOC, "hipMalloc(refgen) failed");
+    }
+    (void)hipMemset(r->value, 0, m * 8); (void)hipMemset(r->sigma, 0, m * 8); (void)hipMemset(r->left, 0, m * 4);
+    (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4); (void)hipMemset(r->t, 0, m * 8);
+    if (kcfg) { (void)hipMemset(r->len, 0, m * 4); (void)hipMemset(r->par, 0, m * 8 * N_PAR); }
+    *out = r;
+    return GEMX_OK;
+}
 
 extern "C" {
 
@@ -221,21 +462,50 @@ int gemx_refgen_create(const gemx_refgen_config *cfg, int64_t n_envs, int device
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
     if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
-    gemx::DeviceGuard guard(device);
-    gemx_refgen *r = new (std::nothrow) gemx_refgen();
-    if (!r) return gemx::fail(GEMX_ERR_ALLOC, "out of host memory");
-    r->cfg = *cfg; r->n = n_envs; r->device = device; r->f64 = dtype == GEMX_F64;
-    const size_t m = (size_t)n_envs * cfg->n_ref;
-    if (hipMalloc((void **)&r->value, m * 8) != hipSuccess || hipMalloc((void **)&r->sigma, m * 8) != hipSuccess ||
-        hipMalloc((void **)&r->left, m * 4) != hipSuccess || hipMalloc((void **)&r->n_sub, m * 4) != hipSuccess ||
-        hipMalloc((void **)&r->n_reset, m * 4) != hipSuccess || hipMalloc((void **)&r->t, m * 8) != hipSuccess) {
-        gemx_refgen_destroy(r);
-        return gemx::fail(GEMX_ERR_ALLOC, "hipMalloc(refgen) failed");
+    return gemx_refgen_alloc(*cfg, nullptr, n_envs, device, dtype, out);
+}
+
+int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
+    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(gemx_refgen_kinds_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_kinds_config size mismatch");
+    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
+    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
+    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
+    if (!(cfg->tau > 0)) return gemx::fail(GEMX_ERR_ARG, "tau must be positive");
+    gemx_refgen_config w;  // the Wiener view: what gemx_refgen_create would be given for these columns
+    memset(&w, 0, sizeof(w));
+    w.struct_size = (int32_t)sizeof(w); w.n_ref = cfg->n_ref; w.seed = cfg->seed; w.env_base = cfg->env_base;
+    w.episode_len_lo = cfg->episode_len_lo[0]; w.episode_len_hi = cfg->episode_len_hi[0];
+    int all_wiener = 1;
+    for (int g = 0; g < cfg->n_ref; ++g) {
+        const int kind = cfg->kind[g];
+        if (kind < GEMX_REF_WIENER || kind > GEMX_REF_CONST) return gemx::fail(GEMX_ERR_ARG, "column %d: unknown generator kind %d", g, kind);
+        w.margin_lo[g] = cfg->margin_lo[g]; w.margin_hi[g] = cfg->margin_hi[g]; w.sigma_lo[g] = cfg->sigma_lo[g]; w.sigma_hi[g] = cfg->sigma_hi[g];
+        w.initial_lo[g] = cfg->initial_lo[g]; w.initial_hi[g] = cfg->initial_hi[g];
+        if (kind != GEMX_REF_WIENER || cfg->episode_len_lo[g] != w.episode_len_lo || cfg->episode_len_hi[g] != w.episode_len_hi) all_wiener = 0;
+        if (kind == GEMX_REF_CONST) continue;
+        if (cfg->episode_len_lo[g] < 1 || cfg->episode_len_hi[g] < cfg->episode_len_lo[g]) return gemx::fail(GEMX_ERR_ARG, "episode lengths %d must satisfy 1 <= lo <= hi", g);
+        if (cfg->margin_hi[g] < cfg->margin_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty margin %d", g);
+        if (kind == GEMX_REF_WIENER || kind == GEMX_REF_LAPLACE) {
+            if (!(cfg->sigma_lo[g] > 0) || cfg->sigma_hi[g] < cfg->sigma_lo[g]) return gemx::fail(GEMX_ERR_ARG, "sigma range %d must satisfy 0 < lo <= hi", g);
+            if (kind == GEMX_REF_WIENER && cfg->initial_hi[g] < cfg->initial_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty initial range %d", g);
+        } else {
+            if (!(cfg->frequency_lo[g] >= 0) || cfg->frequency_hi[g] < cfg->frequency_lo[g] || !(cfg->frequency_hi[g] < HUGE_VAL))
+                return gemx::fail(GEMX_ERR_ARG, "frequency range %d must satisfy 0 <= lo <= hi < inf", g);
+            if (kind == GEMX_REF_STEP && !(cfg->frequency_lo[g] > 0)) return gemx::fail(GEMX_ERR_ARG, "frequency range %d of a step generator must be positive", g);
+            if (cfg->amplitude_lo[g] != cfg->amplitude_lo[g] || cfg->amplitude_hi[g] != cfg->amplitude_hi[g] || cfg->offset_lo[g] != cfg->offset_lo[g] ||
+                cfg->offset_hi[g] != cfg->offset_hi[g])
+                return gemx::fail(GEMX_ERR_ARG, "amplitude / offset range %d is not a number", g);
+        }
     }
-    (void)hipMemset(r->value, 0, m * 8); (void)hipMemset(r->sigma, 0, m * 8); (void)hipMemset(r->left, 0, m * 4);
-    (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4); (void)hipMemset(r->t, 0, m * 8);
-    *out = r;
-    return GEMX_OK;
+    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
+    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
+    const int rc = gemx_refgen_alloc(w, cfg, n_envs, device, dtype, out);
+    if (rc == GEMX_OK) (*out)->mixed = !all_wiener;  // all Wiener, one length range: the kernels (and bits) of a gemx_refgen_create handle
+    return rc;
 }
 
 int gemx_refgen_destroy(gemx_refgen *r) {
@@ -247,6 +517,8 @@ int gemx_refgen_destroy(gemx_refgen *r) {
     if (r->n_sub) (void)hipFree(r->n_sub);
     if (r->n_reset) (void)hipFree(r->n_reset);
     if (r->t) (void)hipFree(r->t);
+    if (r->len) (void)hipFree(r->len);
+    if (r->par) (void)hipFree(r->par);
     delete r;
     return GEMX_OK;
 }
@@ -258,6 +530,7 @@ int gemx_refgen_reset(gemx_refgen *r, const uint8_t *mask_dev, void *stream) {
     gemx::DeviceGuard guard(r->device);
     hipStream_t st = (hipStream_t)stream;
     const int all = mask_dev == nullptr;
+    if (r->mixed) return kinds(r, nullptr, nullptr, nullptr, mask_dev, all, 0, st);
     return r->f64 ? walk<double>(r, nullptr, nullptr, mask_dev, all, 0, st) : walk<float>(r, nullptr, nullptr, mask_dev, all, 0, st);
 }
 
@@ -266,6 +539,7 @@ int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void
     if (K < 1) return gemx::fail(GEMX_ERR_ARG, "K must be >= 1");
     gemx::DeviceGuard guard(r->device);
     hipStream_t st = (hipStream_t)stream;
+    if (r->mixed) return kinds(r, refs_out_dev, nullptr, done_dev, nullptr, 0, K, st);
     const int64_t total = (int64_t)K * r->n * r->cfg.n_ref;
     gemx_cov_note(r->f64 ? "refgen_normals_kernel<double>" : "refgen_normals_kernel<float>");
     if (r->f64)
@@ -286,6 +560,7 @@ int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, vo
     if (!r || !refs_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
     gemx::DeviceGuard guard(r->device);
     hipStream_t st = (hipStream_t)stream;
+    if (r->mixed) return kinds(r, refs_dev, done_dev, nullptr, nullptr, 0, 1, st);
     return r->f64 ? step<double>(r, refs_dev, done_dev, st) : step<float>(r, refs_dev, done_dev, st);
 }
 
@@ -298,6 +573,21 @@ int gemx_refgen_get_state(gemx_refgen *r, double *value_out_dev, double *sigma_o
     if (value_out_dev) GEMX_HIP_TRY(hipMemcpyAsync(value_out_dev, r->value, m * 8, hipMemcpyDeviceToDevice, st));
     if (sigma_out_dev) GEMX_HIP_TRY(hipMemcpyAsync(sigma_out_dev, r->sigma, m * 8, hipMemcpyDeviceToDevice, st));
     if (left_out_dev) GEMX_HIP_TRY(hipMemcpyAsync(left_out_dev, r->left, m * 4, hipMemcpyDeviceToDevice, st));
+    return GEMX_OK;
+}
+
+int gemx_refgen_get_params(gemx_refgen *r, int32_t *kind_index_len_out_dev, double *params_out_dev, void *stream) {
+    if (!r) return gemx::fail(GEMX_ERR_ARG, "null handle");
+    if (!r->has_kinds) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_get_params needs a gemx_refgen_create_kinds handle");
+    gemx::DeviceGuard guard(r->device);
+    const int64_t m = r->n * r->kcfg.n_ref;
+    hipStream_t st = (hipStream_t)stream;
+    if (kind_index_len_out_dev) {
+        hipLaunchKernelGGL(refgen_kinds_index_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, kind_index_len_out_dev, r->n, r->kcfg.n_ref, r->mixed,
+                           make_kinds_dev(r->kcfg), r->left, r->len);
+        GEMX_HIP_TRY(hipGetLastError());
+    }
+    if (params_out_dev) GEMX_HIP_TRY(hipMemcpyAsync(params_out_dev, r->par, (size_t)m * 8 * N_PAR, hipMemcpyDeviceToDevice, st));
     return GEMX_OK;
 }
 

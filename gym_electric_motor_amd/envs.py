@@ -25,7 +25,9 @@ WeightedSumOfErrors reward, and the reference's shell semantics (core.py:300-371
              launch 2  generators of terminated envs restart, every generator advances, `ref` rewritten  (core.py:351)
 
 Two kernel launches per step, no host round trip; `bind_step` resolves everything once and can be captured in a HIP graph.
-`state_filter`, visualisation and the reference's other generator kinds are outside the accelerated path.  For a full single-env GEM
+The reference's other generator kinds (sinusoidal, step, triangular, sawtooth, Laplace process, constant) run on the same path: pass a
+holder named after the reference's class, a list of them or a `BatchedMultipleReferenceGenerator` as `reference_generator=`.
+`state_filter`, visualisation and `SwitchedReferenceGenerator` are outside the accelerated path.  For a full single-env GEM
 environment pass a `BatchedSCMLSystem(n_envs=1)` as `physical_system=` to the reference's own `ElectricMotorEnvironment`
 (INTEGRATION.md).
 """
@@ -335,7 +337,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         """A zero-argument `step()` for a closed loop that reuses ONE action tensor: -> `(step, (state, ref), reward, done)`; `step()`
         enqueues the two launches and returns `(state, ref)`.  Nothing is looked up, allocated or synchronised per call, and no step
         index lives on the host, so `step` can be captured with `torch.cuda.graph` (a linear graph) and replayed -- with the Wiener
-        generators; a ReplayReferenceGenerator keeps its row index on the host and refuses to step while a stream is capturing."""
+        and the other device generators; a ReplayReferenceGenerator keeps its row index on the host and refuses to step while a stream is capturing."""
         ps = self.physical_system
         torch = bps._torch()
         a = action_buffer
@@ -363,10 +365,12 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     """Build a batched env.  Component arguments follow the reference's env-arg convention (instance | dict | None).
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
     (or the reference's own instances); they are folded into the kernel's action stage.
-    reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | ReplayReferenceGenerator;
+    reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
+    StepReferenceGenerator(...) or a list of holders (one per referenced state; the reference's own generator instances are read the
+    same way) | ReplayReferenceGenerator;
     reward_function: None | 'default' | dict of `set_reward` keywords.  Naming either one selects the complete env
     (CompleteBatchedElectricMotorEnv), the other then takes the env id's default (`default_env_modules`); `seed` keys the default
-    generators like every other device random stream.  Both None: the physics-only env."""
+    generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env."""
     from .physical_system_wrappers import fold_wrappers
 
     if state_filter is not None:
@@ -397,14 +401,20 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     )
     if reference_generator is None and reward_function is None:
         return BatchedElectricMotorEnv(system)
-    from .reference_generators import BatchedWienerProcessReferenceGenerator
+    from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators
 
     modules = default_env_modules(env_id)
     if reference_generator is None or (isinstance(reference_generator, str) and reference_generator == "default"):
         reference_generator = BatchedWienerProcessReferenceGenerator(reference_states=modules["reference_states"], seed=kwargs.get("seed", 0),
                                                                      **modules["generator"])
     elif isinstance(reference_generator, (str, type)):
-        raise ValueError("reference_generator: 'default', a BatchedWienerProcessReferenceGenerator or a ReplayReferenceGenerator instance")
+        raise ValueError("reference_generator: 'default', a BatchedWienerProcessReferenceGenerator, a BatchedMultipleReferenceGenerator, generator "
+                         "holders (e.g. StepReferenceGenerator(...), or a list of them) or a ReplayReferenceGenerator instance")
+    elif type(reference_generator).__name__ == "SwitchedReferenceGenerator":
+        raise NotImplementedError(SWITCHED_REFUSAL)
+    elif not isinstance(reference_generator, (_DeviceGenerators, ReplayReferenceGenerator)):
+        # holders, a list of them, or the reference's own instances: one handle, columns in state order
+        reference_generator = BatchedMultipleReferenceGenerator(reference_generator, seed=kwargs.get("seed", 0))
     if not (reward_function is None or isinstance(reward_function, dict) or (isinstance(reward_function, str) and reward_function == "default")):
         raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
     return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,

@@ -15,6 +15,14 @@ Closed loop, one launch per control step (what `ga.make(env_id, reference_genera
 then per control step `ref = gen.step(done)` -- terminated envs restart their generators, every generator advances, `ref [N, n_ref]` is
 rewritten in place.  K x `step(done[k-1])` equals `rollout(K, done)` bit for bit, and the two can be mixed.
 
+The reference's other generator kinds -- sinusoidal, step, triangular, sawtooth, Laplace process, constant -- are parameter holders named
+after the reference's classes, mixed per state by `BatchedMultipleReferenceGenerator` (MultipleReferenceGenerator's counterpart), on the
+same kernels' handle and with the same surface and invariants:
+
+    gen = ga.BatchedMultipleReferenceGenerator([ga.SinusoidalReferenceGenerator(reference_state="i_sd", frequency_range=(5, 50)),
+                                                ga.StepReferenceGenerator(reference_state="i_sq", amplitude_range=(0.1, 0.4))], seed=3)
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator=gen)
+
 The numpy PCG64 streams of the reference cannot be reproduced on a device; the generated process is the same in distribution
 (tests/test_gpu_parity.py), chunked generation equals one-shot generation bit for bit (counter-based Philox).
 """
@@ -25,89 +33,39 @@ import numpy as np
 from . import _lib
 
 
-class BatchedWienerProcessReferenceGenerator:
-    def __init__(self, reference_states=("omega",), sigma_range=(1e-3, 1e-1), episode_lengths=(500, 2000), limit_margin=None,
-                 initial_range=None, seed=0, env_base=None):
-        self._reference_states = tuple(s.lower() for s in ([reference_states] if isinstance(reference_states, str) else reference_states))
-        if not 1 <= len(self._reference_states) <= _lib.MAX_REF:
-            raise ValueError(f"1..{_lib.MAX_REF} reference states")
-        self._sigma_range = sigma_range
-        self._episode_lengths = (int(episode_lengths), int(episode_lengths)) if np.ndim(episode_lengths) == 0 else tuple(int(x) for x in episode_lengths)
-        self._limit_margin = limit_margin
-        self._initial_range = initial_range
-        self._seed = int(seed) & (2**64 - 1)
-        self._env_base = None if env_base is None else int(env_base)  # None: the physical system's (a shard's generators follow its envs)
-        self._handle = None
-        self._refs = None
-        for what, v in (("limit_margin", limit_margin), ("sigma_range", sigma_range), ("initial_range", initial_range)):
-            if isinstance(v, dict):  # per generator, by state name; states not named take the default
-                unknown = sorted(set(k.lower() for k in v) - set(self._reference_states))
-                if unknown:
-                    raise ValueError(f"{what} names {unknown}, which are not among the reference states {list(self._reference_states)}")
+def _limit_margins(ps, name, limit_margin):
+    """subepisoded_reference_generator.py:45-64 (set_modules): None (nominal / limit) | number | (lower, upper), factors of the state
+    space's bounds."""
+    i = ps.state_positions[name]
+    low, high = ps.state_space.low[i], ps.state_space.high[i]
+    if limit_margin is None:
+        f = ps.nominal_state[i] / ps.limits[i]
+        return f * low, f * high
+    if isinstance(limit_margin, (float, int)):
+        return limit_margin * low, limit_margin * high
+    if isinstance(limit_margin, tuple):
+        return limit_margin[0] * low, limit_margin[1] * high
+    raise Exception("Unknown type for the limit margin.")
+
+
+class _DeviceGenerators:
+    """What every generator that owns a gemx_refgen handle offers the env shell; the subclasses derive the handle's config."""
 
     reference_names = property(lambda self: self._ordered)
     n_envs = property(lambda self: self._n_envs)
     is_set = property(lambda self: hasattr(self, "_cfg"), doc="set_modules has run")
 
-    @staticmethod
-    def _for_state(value, name, default):
-        """A setting given for all generators, or as a dict by state name (states not named: the default)."""
-        if isinstance(value, dict):
-            return {k.lower(): v for k, v in value.items()}.get(name, default)
-        return value
-
-    def _margins(self, ps, name):
-        """subepisoded_reference_generator.py:66-84."""
-        i = ps.state_positions[name]
-        low, high = ps.state_space.low[i], ps.state_space.high[i]
-        lm = self._for_state(self._limit_margin, name, None)
-        if lm is None:
-            f = ps.nominal_state[i] / ps.limits[i]
-            return f * low, f * high
-        if isinstance(lm, (float, int)):
-            return lm * low, lm * high
-        if isinstance(lm, tuple):
-            return lm[0] * low, lm[1] * high
-        raise Exception("Unknown type for the limit margin.")
-
-    def set_modules(self, physical_system, _defer_create=False):
-        ps = physical_system
-        # the fused reward's reference tensor follows the state order of the physical system
-        self._ordered = tuple(sorted(self._reference_states, key=lambda n: ps.state_positions[n]))
-        self._n_envs = ps.n_envs
-        cfg = _lib.GemxRefgenConfig()
-        cfg.struct_size = C.sizeof(_lib.GemxRefgenConfig)
-        cfg.n_ref = len(self._ordered)
-        cfg.seed = self._seed
-        cfg.env_base = self._env_base if self._env_base is not None else int(getattr(ps, "env_base", 0))
-        cfg.episode_len_lo, cfg.episode_len_hi = self._episode_lengths
-        for j, name in enumerate(self._ordered):
-            lo, hi = self._margins(ps, name)
-            cfg.margin_lo[j], cfg.margin_hi[j] = float(lo), float(hi)
-            ir = self._for_state(self._initial_range, name, None)
-            ir = ir if ir is not None else (lo, hi)  # wiener_process_reference_generator.py:25-28
-            cfg.initial_lo[j], cfg.initial_hi[j] = float(ir[0]), float(ir[1])
-            sr = self._for_state(self._sigma_range, name, (1e-3, 1e-1))
-            cfg.sigma_lo[j], cfg.sigma_hi[j] = (float(sr), float(sr)) if np.ndim(sr) == 0 else (float(sr[0]), float(sr[1]))
-        self._cfg = cfg
-        if _defer_create:
-            return self
+    def _create(self, ps, create, cfg):
         import torch
 
         self._L = _lib.load()
         self._tdev = ps._tdev
         self._tdtype = ps._tdtype
         h = C.c_void_p()
-        _lib.check(self._L.gemx_refgen_create(C.byref(cfg), self._n_envs, ps.device, _lib.F64 if self._tdtype == torch.float64 else _lib.F32, C.byref(h)))
+        _lib.check(getattr(self._L, create)(C.byref(cfg), self._n_envs, ps.device, _lib.F64 if self._tdtype == torch.float64 else _lib.F32, C.byref(h)))
         self._handle = h
         self._refs = torch.zeros((self._n_envs, int(cfg.n_ref)), dtype=self._tdtype, device=self._tdev)  # step()'s own buffer
         return self
-
-    @property
-    def reference_space(self):
-        """(low, high) arrays [n_ref]: the generators' limit margins (MultipleReferenceGenerator.reference_space)."""
-        n = int(self._cfg.n_ref)
-        return np.array(self._cfg.margin_lo[:n], dtype=float), np.array(self._cfg.margin_hi[:n], dtype=float)
 
     @property
     def references(self):
@@ -182,6 +140,78 @@ class BatchedWienerProcessReferenceGenerator:
         d = done if done.dim() == 1 else done.any(dim=0)
         self.reset(mask=d.to(torch.uint8))
 
+    def close(self):
+        if self._handle is not None:
+            self._L.gemx_refgen_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchedWienerProcessReferenceGenerator(_DeviceGenerators):
+    def __init__(self, reference_states=("omega",), sigma_range=(1e-3, 1e-1), episode_lengths=(500, 2000), limit_margin=None,
+                 initial_range=None, seed=0, env_base=None):
+        self._reference_states = tuple(s.lower() for s in ([reference_states] if isinstance(reference_states, str) else reference_states))
+        if not 1 <= len(self._reference_states) <= _lib.MAX_REF:
+            raise ValueError(f"1..{_lib.MAX_REF} reference states")
+        self._sigma_range = sigma_range
+        self._episode_lengths = (int(episode_lengths), int(episode_lengths)) if np.ndim(episode_lengths) == 0 else tuple(int(x) for x in episode_lengths)
+        self._limit_margin = limit_margin
+        self._initial_range = initial_range
+        self._seed = int(seed) & (2**64 - 1)
+        self._env_base = None if env_base is None else int(env_base)  # None: the physical system's (a shard's generators follow its envs)
+        self._handle = None
+        self._refs = None
+        for what, v in (("limit_margin", limit_margin), ("sigma_range", sigma_range), ("initial_range", initial_range)):
+            if isinstance(v, dict):  # per generator, by state name; states not named take the default
+                unknown = sorted(set(k.lower() for k in v) - set(self._reference_states))
+                if unknown:
+                    raise ValueError(f"{what} names {unknown}, which are not among the reference states {list(self._reference_states)}")
+
+    @staticmethod
+    def _for_state(value, name, default):
+        """A setting given for all generators, or as a dict by state name (states not named: the default)."""
+        if isinstance(value, dict):
+            return {k.lower(): v for k, v in value.items()}.get(name, default)
+        return value
+
+    def _margins(self, ps, name):
+        return _limit_margins(ps, name, self._for_state(self._limit_margin, name, None))
+
+    def set_modules(self, physical_system, _defer_create=False):
+        ps = physical_system
+        # the fused reward's reference tensor follows the state order of the physical system
+        self._ordered = tuple(sorted(self._reference_states, key=lambda n: ps.state_positions[n]))
+        self._n_envs = ps.n_envs
+        cfg = _lib.GemxRefgenConfig()
+        cfg.struct_size = C.sizeof(_lib.GemxRefgenConfig)
+        cfg.n_ref = len(self._ordered)
+        cfg.seed = self._seed
+        cfg.env_base = self._env_base if self._env_base is not None else int(getattr(ps, "env_base", 0))
+        cfg.episode_len_lo, cfg.episode_len_hi = self._episode_lengths
+        for j, name in enumerate(self._ordered):
+            lo, hi = self._margins(ps, name)
+            cfg.margin_lo[j], cfg.margin_hi[j] = float(lo), float(hi)
+            ir = self._for_state(self._initial_range, name, None)
+            ir = ir if ir is not None else (lo, hi)  # wiener_process_reference_generator.py:25-28
+            cfg.initial_lo[j], cfg.initial_hi[j] = float(ir[0]), float(ir[1])
+            sr = self._for_state(self._sigma_range, name, (1e-3, 1e-1))
+            cfg.sigma_lo[j], cfg.sigma_hi[j] = (float(sr), float(sr)) if np.ndim(sr) == 0 else (float(sr[0]), float(sr[1]))
+        self._cfg = cfg
+        if _defer_create:
+            return self
+        return self._create(ps, "gemx_refgen_create", cfg)
+
+    @property
+    def reference_space(self):
+        """(low, high) arrays [n_ref]: the generators' limit margins (MultipleReferenceGenerator.reference_space)."""
+        n = int(self._cfg.n_ref)
+        return np.array(self._cfg.margin_lo[:n], dtype=float), np.array(self._cfg.margin_hi[:n], dtype=float)
+
     def state(self):
         """(value, sigma, steps_left) per (generator, env), for tests / inspection."""
         import torch
@@ -194,16 +224,226 @@ class BatchedWienerProcessReferenceGenerator:
         torch.cuda.current_stream(self._tdev).synchronize()
         return v, s, l_
 
-    def close(self):
-        if self._handle is not None:
-            self._L.gemx_refgen_destroy(self._handle)
-            self._handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _pair(value, what):
+    """A range as (lo, hi); a plain number is that number (`_get_current_value`, subepisoded_reference_generator.py:109-119)."""
+    if np.ndim(value) == 0:
+        return float(value), float(value)
+    if len(value) != 2:
+        raise ValueError(f"{what}: a number or (low, high), not {value!r}")
+    return float(value[0]), float(value[1])
+
+
+class _SubGenerator:
+    """Parameter holder of one sub-generator: the keyword arguments and defaults of the reference's class of the same name.  Holders
+    generate nothing; a BatchedMultipleReferenceGenerator turns them into the columns of one device handle."""
+
+    kind = None
+    keywords = ("reference_state", "episode_lengths", "limit_margin")
+
+    def __init__(self, reference_state="omega", episode_lengths=(500, 2000), limit_margin=None):
+        self.reference_state = str(reference_state).lower()
+        self.episode_lengths = tuple(int(x) for x in _pair(episode_lengths, "episode_lengths"))
+        if isinstance(limit_margin, list):
+            limit_margin = tuple(limit_margin)
+        if isinstance(limit_margin, dict):  # by state name, as the env ids' defaults are kept: this holder's own state, else None
+            limit_margin = {k.lower(): v for k, v in limit_margin.items()}.get(self.reference_state)
+        self.limit_margin = limit_margin
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{k}={v!r}' for k, v in vars(self).items())})"
+
+
+class WienerProcessReferenceGenerator(_SubGenerator):
+    """wiener_process_reference_generator.py:11-23."""
+
+    kind = _lib.REF_WIENER
+    keywords = _SubGenerator.keywords + ("sigma_range", "initial_range")
+
+    def __init__(self, sigma_range=(1e-3, 1e-1), initial_range=None, **kwargs):
+        super().__init__(**kwargs)
+        self.sigma_range = _pair(sigma_range, "sigma_range")
+        self.initial_range = None if initial_range is None else _pair(initial_range, "initial_range")
+
+
+class LaplaceProcessReferenceGenerator(_SubGenerator):
+    """laplace_process_reference_generator.py:15-22."""
+
+    kind = _lib.REF_LAPLACE
+    keywords = _SubGenerator.keywords + ("sigma_range",)
+
+    def __init__(self, sigma_range=(1e-3, 1e-1), **kwargs):
+        super().__init__(**kwargs)
+        self.sigma_range = _pair(sigma_range, "sigma_range")
+
+
+class _WaveformGenerator(_SubGenerator):
+    keywords = _SubGenerator.keywords + ("amplitude_range", "frequency_range", "offset_range")
+
+    def __init__(self, amplitude_range=None, frequency_range=(1, 10), offset_range=None, **kwargs):
+        super().__init__(**kwargs)
+        # `amplitude_range or (0, np.inf)`, `offset_range or (-np.inf, np.inf)` (e.g. sinusoidal_reference_generator.py:36-38): cut to the
+        # limit margin in set_modules
+        self.amplitude_range = _pair(amplitude_range if amplitude_range is not None else (0.0, np.inf), "amplitude_range")
+        self.frequency_range = _pair(frequency_range, "frequency_range")
+        self.offset_range = _pair(offset_range if offset_range is not None else (-np.inf, np.inf), "offset_range")
+
+
+class SinusoidalReferenceGenerator(_WaveformGenerator):
+    """sinusoidal_reference_generator.py:16-38."""
+
+    kind = _lib.REF_SINUS
+
+
+class StepReferenceGenerator(_WaveformGenerator):
+    """step_reference_generator.py:15-26."""
+
+    kind = _lib.REF_STEP
+
+
+class TriangularReferenceGenerator(_WaveformGenerator):
+    """triangle_reference_generator.py:14-37."""
+
+    kind = _lib.REF_TRIANGULAR
+
+
+class SawtoothReferenceGenerator(_WaveformGenerator):
+    """sawtooth_reference_generator.py:17-29."""
+
+    kind = _lib.REF_SAWTOOTH
+
+
+class ConstReferenceGenerator(_SubGenerator):
+    """const_reference_generator.py:11-22: always `reference_value`; no sub-episodes, no margin."""
+
+    kind = _lib.REF_CONST
+    keywords = ("reference_state", "reference_value")
+
+    def __init__(self, reference_state="omega", reference_value=0.5):
+        super().__init__(reference_state=reference_state)
+        self.reference_value = float(reference_value)
+
+
+_HOLDERS = {c.__name__: c for c in (WienerProcessReferenceGenerator, LaplaceProcessReferenceGenerator, SinusoidalReferenceGenerator,
+                                    StepReferenceGenerator, TriangularReferenceGenerator, SawtoothReferenceGenerator, ConstReferenceGenerator)}
+# the private attributes the reference's instances keep their constructor arguments in -> the holders' keywords
+_REFERENCE_ATTRIBUTES = dict(_reference_state="reference_state", _episode_len_range="episode_lengths", _limit_margin="limit_margin",
+                             _sigma_range="sigma_range", _initial_range="initial_range", _amplitude_range="amplitude_range",
+                             _frequency_range="frequency_range", _offset_range="offset_range", _reference_value="reference_value")
+SWITCHED_REFUSAL = "SwitchedReferenceGenerator is outside the accelerated path: it switches between whole generators per super-episode, and the device handle fixes one kind per column."
+
+
+def as_sub_generators(generator):
+    """-> list of holders.  A holder, a list / tuple of them, or the reference's own generator instances as constructed, recognised by
+    class name with the settings read from the instance -- the way `fold_wrappers` treats the reference's wrapper instances; a
+    MultipleReferenceGenerator instance contributes its sub-generators.  An instance that has been through its own `set_modules` is
+    refused: its margins and ranges are no longer the constructor's.  Nothing of the reference is imported."""
+    if isinstance(generator, (list, tuple)):
+        return [h for g in generator for h in as_sub_generators(g)]
+    if isinstance(generator, _SubGenerator):
+        return [generator]
+    name = type(generator).__name__
+    if name == "SwitchedReferenceGenerator":
+        raise NotImplementedError(SWITCHED_REFUSAL)
+    if name == "MultipleReferenceGenerator" and hasattr(generator, "_sub_generators"):
+        return as_sub_generators(list(generator._sub_generators))
+    if name not in _HOLDERS or not hasattr(generator, "_reference_state"):
+        raise TypeError(f"{name} is not a reference generator of the accelerated path; known kinds: {sorted(_HOLDERS)}")
+    if getattr(generator, "_physical_system", None) is not None or getattr(generator, "_referenced_states", None) is not None:
+        # (both None as constructed, core.py:425-429.)  Its set_modules has run: `_limit_margin` now holds absolute margins and the
+        # amplitude / offset ranges are already cut to them (subepisoded_reference_generator.py:45-64, e.g.
+        # sinusoidal_reference_generator.py:40-48), which would be read here as factors and constructor arguments
+        raise ValueError(f"this {name} has already been through set_modules; pass an instance as constructed, or a holder with its keyword arguments")
+    holder = _HOLDERS[name]
+    kw = {key: getattr(generator, attr) for attr, key in _REFERENCE_ATTRIBUTES.items() if key in holder.keywords and hasattr(generator, attr)}
+    for key in ("amplitude_range", "offset_range", "sigma_range", "episode_lengths", "initial_range"):  # (numpy arrays -> tuples)
+        if key in kw and kw[key] is not None and np.ndim(kw[key]) == 1:
+            kw[key] = tuple(float(x) for x in kw[key])
+    return [holder(**kw)]
+
+
+class BatchedMultipleReferenceGenerator(_DeviceGenerators):
+    """The batched MultipleReferenceGenerator (multiple_reference_generator.py:9-92) over the reference's sub-episoded and constant
+    generator kinds: one holder per referenced state, any mix of kinds, ONE device handle (gemx_refgen_create_kinds).  The columns follow
+    the state order of the physical system.  Surface and invariants are the Wiener generator's: `reset`, `step`, `rollout`, `bind_step`
+    (graph-capturable), `apply_done`; K x step == rollout(K), chunked == one-shot, shards by `env_base`.  A Wiener column draws exactly
+    what the same column of a BatchedWienerProcessReferenceGenerator with the same seed draws."""
+
+    def __init__(self, sub_generators, seed=0, env_base=None):
+        self._subs = as_sub_generators(sub_generators)
+        if not 1 <= len(self._subs) <= _lib.MAX_REF:
+            raise ValueError(f"1..{_lib.MAX_REF} sub-generators (columns of the reference tensor), not {len(self._subs)}")
+        states = [h.reference_state for h in self._subs]
+        if len(set(states)) != len(states):  # multiple_reference_generator.py:54-56
+            raise ValueError(f"every state is referenced by at most one sub-generator: {states}")
+        self._seed = int(seed) & (2**64 - 1)
+        self._env_base = None if env_base is None else int(env_base)
+        self._handle = None
+        self._refs = None
+
+    sub_generators = property(lambda self: tuple(self._subs), doc="the holders, in the order given")
+
+    def set_modules(self, physical_system, _defer_create=False):
+        ps = physical_system
+        missing = [h.reference_state for h in self._subs if h.reference_state not in ps.state_positions]
+        if missing:
+            raise ValueError(f"reference states {missing} are not states of the physical system {list(ps.state_names)}")
+        subs = sorted(self._subs, key=lambda h: ps.state_positions[h.reference_state])
+        self._ordered = tuple(h.reference_state for h in subs)
+        self._columns = tuple(subs)
+        self._n_envs = ps.n_envs
+        cfg = _lib.GemxRefgenKindsConfig()
+        cfg.struct_size = C.sizeof(_lib.GemxRefgenKindsConfig)
+        cfg.n_ref = len(subs)
+        cfg.seed = self._seed
+        cfg.env_base = self._env_base if self._env_base is not None else int(getattr(ps, "env_base", 0))
+        cfg.tau = float(ps.tau)
+        space_lo, space_hi = [], []
+        for j, h in enumerate(subs):
+            cfg.kind[j] = h.kind
+            if h.kind == _lib.REF_CONST:  # its reference space is the single point (const_reference_generator.py:20)
+                cfg.reference_value[j] = h.reference_value
+                space_lo.append(h.reference_value)
+                space_hi.append(h.reference_value)
+                continue
+            cfg.episode_len_lo[j], cfg.episode_len_hi[j] = h.episode_lengths
+            lo, hi = (float(x) for x in _limit_margins(ps, h.reference_state, h.limit_margin))
+            cfg.margin_lo[j], cfg.margin_hi[j] = lo, hi
+            space_lo.append(lo)
+            space_hi.append(hi)
+            if h.kind in (_lib.REF_WIENER, _lib.REF_LAPLACE):
+                cfg.sigma_lo[j], cfg.sigma_hi[j] = h.sigma_range
+                ir = getattr(h, "initial_range", None)
+                cfg.initial_lo[j], cfg.initial_hi[j] = ir if ir is not None else (lo, hi)  # wiener_process_reference_generator.py:25-28
+            else:  # e.g. sinusoidal_reference_generator.py:40-48: amplitudes within half the margin's width, offsets within the margin
+                cfg.amplitude_lo[j], cfg.amplitude_hi[j] = (float(x) for x in np.clip(h.amplitude_range, 0, (hi - lo) / 2))
+                cfg.offset_lo[j], cfg.offset_hi[j] = (float(x) for x in np.clip(h.offset_range, lo, hi))
+                cfg.frequency_lo[j], cfg.frequency_hi[j] = h.frequency_range
+        self._cfg = cfg
+        self._space = (np.array(space_lo, dtype=float), np.array(space_hi, dtype=float))
+        if _defer_create:
+            return self
+        return self._create(ps, "gemx_refgen_create_kinds", cfg)
+
+    reference_space = property(lambda self: self._space, doc="(low, high) arrays [n_ref]: the limit margins; a constant column: its value")
+
+    def state(self):
+        """dict of [n_ref, N] tensors, for tests / inspection: value, sigma, left (steps left in the sub-episode), kind, index (step index
+        inside the sub-episode), length, amplitude, frequency, offset, phase, width (a step column: its high / low ratio), roll."""
+        import torch
+
+        n = (int(self._cfg.n_ref), self._n_envs)
+        v = torch.empty(n, dtype=torch.float64, device=self._tdev)
+        s = torch.empty(n, dtype=torch.float64, device=self._tdev)
+        l_ = torch.empty(n, dtype=torch.int32, device=self._tdev)
+        kil = torch.empty((3,) + n, dtype=torch.int32, device=self._tdev)
+        par = torch.empty((6,) + n, dtype=torch.float64, device=self._tdev)
+        _lib.check(self._L.gemx_refgen_get_state(self._handle, C.c_void_p(v.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(l_.data_ptr()), self._stream()))
+        _lib.check(self._L.gemx_refgen_get_params(self._handle, C.c_void_p(kil.data_ptr()), C.c_void_p(par.data_ptr()), self._stream()))
+        torch.cuda.current_stream(self._tdev).synchronize()
+        out = dict(value=v, sigma=s, left=l_, kind=kil[0], index=kil[1], length=kil[2])
+        out.update(zip(("amplitude", "frequency", "offset", "phase", "width", "roll"), par))
+        return out
 
 
 class ReplayReferenceGenerator:

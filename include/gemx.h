@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GEMX_ABI_VERSION 8 /* 2: GEMX_MAX_OUT 16 -> 24 (DFIM system, 24 states); 3: gemx_config.solver_flags; 4: solver_rtol / solver_atol; 5: init_flux_mode / init_flux;
+#define GEMX_ABI_VERSION 9 /* 2: GEMX_MAX_OUT 16 -> 24 (DFIM system, 24 states); 3: gemx_config.solver_flags; 4: solver_rtol / solver_atol; 5: init_flux_mode / init_flux;
                             * 6: gemx_get_aux_state / gemx_set_aux_state / gemx_aux_state_bytes, gemx_reset_again; reset counters stay at 1 after gemx_create;
                             *    + gemx_rollout_synthetic / gemx_synthetic_actions, gemx_set_rate_limiter (new entry points only);
                             * 7: gemx_config.env_base / gemx_refgen_config.env_base: every device random stream is keyed by the GLOBAL env index
@@ -36,7 +36,9 @@ extern "C" {
                             *    honours GEMX_SOLVER_SPLIT_KINKS; the initial-state streams are Threefry-4x32-12 (were Philox4x32-10: other draws from
                             *    the same seed, same distributions); one unit library per (system, converter, dtype), loaded by gemx_create;
                             * 8: gemx_refgen_step (new entry point: one fused generator step per launch); the generators' step index moved from the host
-                            *    into device memory (gemx_refgen_rollout: same bits) */
+                            *    into device memory (gemx_refgen_rollout: same bits);
+                            * 9: gemx_refgen_kinds_config / gemx_refgen_create_kinds / gemx_refgen_get_params (new struct and entry points only: a kind per
+                            *    generator column -- Wiener, Laplace, sinusoidal, step, triangular, sawtooth, constant; gemx_refgen_config handles: same bits) */
 #define GEMX_MAX_ODE 8  /* ODE state length incl. omega and the angle      */
 #define GEMX_MAX_OUT 24 /* system-state (observation) length               */
 #define GEMX_MODEL_ROWS 5
@@ -332,6 +334,47 @@ int gemx_refgen_reset(gemx_refgen *r, const uint8_t *mask_dev, void *stream);
 int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
 int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, void *stream);
 int gemx_refgen_get_state(gemx_refgen *r, double *value_out_dev, double *sigma_out_dev, int32_t *left_out_dev, void *stream);
+
+/* The reference's other generator kinds behind the same handle (ABI 9): every column of a gemx_refgen_create_kinds handle has a kind of
+ * its own, freely mixed as MultipleReferenceGenerator mixes its sub-generators (files under reference_generators/):
+ *   WIENER     wiener_process_reference_generator.py    as above; the column draws what column j of a gemx_refgen_create handle draws
+ *   LAPLACE    laplace_process_reference_generator.py   the clipped walk with Laplace(0, b) increments, b = 10 ** U(log10 sigma range)
+ *   SINUS      sinusoidal_reference_generator.py        A sin(2 pi f t_k + phi) + o,       phi = 2 pi U
+ *   STEP       step_reference_generator.py              A sign(f (t_j mod 1/f) - r) + o,   r ~ Triangular(0, 0.5, 1), j = (k - roll) mod L,
+ *                                                       roll = int(U / (f tau)): numpy's roll over the sub-episode of L steps
+ *   TRIANGULAR triangle_reference_generator.py          A saw(2 pi f t_k + phi, w) + o,    w = U   (saw: scipy.signal.sawtooth)
+ *   SAWTOOTH   sawtooth_reference_generator.py          A saw(2 pi f t_k + phi, 1) + o
+ *   CONST      const_reference_generator.py             reference_value, always; reset and done do nothing
+ * with t_k = k * tau, k the step index inside the sub-episode (subepisoded_reference_generator.py:93-119; sub-episode lengths are per
+ * column here).  Per sub-episode the waveform kinds draw amplitude, frequency, offset (in this order) and their extra parameters; the
+ * offset range is clipped per sub-episode to [-margin_hi + A, margin_hi - A] (STEP: [margin_lo + A, margin_hi - A]) with numpy's clip
+ * order min(max(x, a), b); every value is clipped to the margin.  Nothing is tabulated: each (column, env) keeps the parameters of its
+ * sub-episode in device memory and evaluates the waveform in closed form, in double, rounded to R on store.  reset() sets the carried
+ * value of every kind but WIENER to 0 (a Laplace walk restarts from 0).  Every call that takes a gemx_refgen takes these handles, with
+ * the same invariants (step x K == rollout(K), chunked == one-shot, shards by env_base, graph capture).  A handle whose columns are
+ * all WIENER with one common sub-episode length range runs the kernels of a gemx_refgen_create handle. */
+enum { GEMX_REF_WIENER = 0, GEMX_REF_LAPLACE = 1, GEMX_REF_SINUS = 2, GEMX_REF_STEP = 3, GEMX_REF_TRIANGULAR = 4, GEMX_REF_SAWTOOTH = 5, GEMX_REF_CONST = 6 };
+typedef struct gemx_refgen_kinds_config {
+    int32_t struct_size; /* = sizeof(gemx_refgen_kinds_config) */
+    int32_t n_ref;       /* 1..GEMX_MAX_REF columns */
+    uint64_t seed;
+    int64_t env_base;
+    double tau;          /* control period of the physical system: the waveforms are functions of k * tau */
+    int32_t kind[GEMX_MAX_REF]; /* GEMX_REF_* */
+    int32_t episode_len_lo[GEMX_MAX_REF], episode_len_hi[GEMX_MAX_REF]; /* episode_lengths, per column */
+    double margin_lo[GEMX_MAX_REF], margin_hi[GEMX_MAX_REF];       /* limit_margin in normalised units */
+    double sigma_lo[GEMX_MAX_REF], sigma_hi[GEMX_MAX_REF];         /* WIENER, LAPLACE: sigma_range */
+    double initial_lo[GEMX_MAX_REF], initial_hi[GEMX_MAX_REF];     /* WIENER: initial_range */
+    double amplitude_lo[GEMX_MAX_REF], amplitude_hi[GEMX_MAX_REF]; /* waveform kinds: amplitude_range; clipped to [0, (margin_hi - margin_lo) / 2] */
+    double frequency_lo[GEMX_MAX_REF], frequency_hi[GEMX_MAX_REF]; /* waveform kinds: frequency_range, Hz (STEP: > 0) */
+    double offset_lo[GEMX_MAX_REF], offset_hi[GEMX_MAX_REF];       /* waveform kinds: offset_range; clipped to the margin */
+    double reference_value[GEMX_MAX_REF];                          /* CONST */
+} gemx_refgen_kinds_config;
+int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out);
+/* debug / test access, per (column, env) arrays [n_ref][N] (any pointer may be NULL): kind_index_len int32 [3][n_ref][N] = the kind, the
+ * step index inside the sub-episode and its length; params double [6][n_ref][N] = amplitude, frequency, offset, phase, width (STEP: the
+ * high/low ratio r), roll.  A handle that runs the all-Wiener kernels does not track index and length: both read -1. */
+int gemx_refgen_get_params(gemx_refgen *r, int32_t *kind_index_len_out_dev, double *params_out_dev, void *stream);
 
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
