@@ -34,9 +34,13 @@ def main():
     ap.add_argument("--graph", type=int, default=0, metavar="S", help="--complete: S control steps per HIP graph")
     ap.add_argument("--reference", default="wiener", metavar="KIND", choices=sorted(REFERENCES),
                     help="--complete: the kind of the i_sd / i_sq reference generators: " + ", ".join(sorted(REFERENCES)))
+    ap.add_argument("--flat", action="store_true", help="--complete: the device-side observation stage hands the policy ONE flat tensor "
+                                                        "(i_sd, i_sq, cos(epsilon), sin(epsilon), reference i_sd, reference i_sq)")
     args = ap.parse_args()
     if args.reference != "wiener" and not args.complete:
         ap.error("--reference needs --complete")
+    if args.flat and not args.complete:
+        ap.error("--flat needs --complete")
     if args.complete:
         return complete(args)
     import torch
@@ -85,9 +89,14 @@ def complete(args):
         holder = getattr(ga, REFERENCES[args.reference])
         kw = dict() if args.reference in ("laplace", "constant") else dict(frequency_range=(5, 50), amplitude_range=(0.1, 0.4))
         generator = [holder(reference_state=s, **kw) for s in ("i_sd", "i_sq")]
-    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),),
-                  reference_generator=generator, seed=1)
+    wrappers, obs_kw = (ga.DqToAbcActionProcessor.make("PMSM"),), dict()
+    if args.flat:  # cos / sin instead of the angle, the four columns the policy reads, state and references in one tensor
+        wrappers += (ga.CosSinProcessor(remove_angle=True),)
+        obs_kw = dict(observed_states=["i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"], flatten_observation=True)
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw)
     ps = env.physical_system
+    if args.flat:
+        return flat_loop(args, env)
     cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
     gain = torch.tensor(8.0, device="cuda")
     ret = torch.zeros(n, device="cuda")
@@ -136,6 +145,52 @@ def complete(args):
     steps = reps * (args.graph or 1)
     print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
           f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
+    assert torch.isfinite(ret).all()
+    env.close()
+
+
+def flat_loop(args, env):
+    """The same closed loop on the flat observation [N, 4 + 2]: the policy reads its input as it is, nothing is selected or concatenated."""
+    import torch
+
+    n = args.envs
+    gain = torch.tensor(8.0, device="cuda")
+    ret = torch.zeros(n, device="cuda")
+    action = torch.zeros((n, 2), device="cuda")
+    stream = torch.cuda.Stream() if args.graph else None
+    step, obs, reward, done = env.bind_step(action, stream=stream)
+    assert obs.shape == (n, 6)
+
+    def control_step():
+        torch.clamp(gain * (obs[:, 4:6] - obs[:, 0:2]), -1, 1, out=action)
+        step()
+        ret.add_(reward)
+
+    env.reset()
+    mode, reps, run_one = "bind_step, flat observation", args.steps, control_step
+    if args.graph:
+        mode = f"HIP graph of {args.graph} steps, flat observation"
+        stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(stream):
+            for _ in range(3):
+                control_step()
+            env.reset()
+            ret.zero_()
+        torch.cuda.current_stream().wait_stream(stream)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            for _ in range(args.graph):
+                control_step()
+        reps, run_one = args.steps // args.graph, graph.replay
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        run_one()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = reps * (args.graph or 1)
+    print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
+          f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}")
     assert torch.isfinite(ret).all()
     env.close()
 

@@ -29,13 +29,14 @@ from .components import (  # noqa: F401
     SquirrelCageInductionMotor,
     SynchronousReluctanceMotor,
 )
-from .envs import BatchedElectricMotorEnv, CompleteBatchedElectricMotorEnv, default_components, default_env_modules, default_ode_solver, make  # noqa: F401
+from .envs import BatchedElectricMotorEnv, CompleteBatchedElectricMotorEnv, default_components, default_env_modules, default_ode_solver, default_physical_system_wrappers, make  # noqa: F401
 from .reference_generators import BatchedWienerProcessReferenceGenerator, ReplayReferenceGenerator  # noqa: F401
 from .reference_generators import (  # noqa: F401
     BatchedMultipleReferenceGenerator, ConstReferenceGenerator, LaplaceProcessReferenceGenerator, SawtoothReferenceGenerator,
     SinusoidalReferenceGenerator, StepReferenceGenerator, TriangularReferenceGenerator, WienerProcessReferenceGenerator,
 )
-from .physical_system_wrappers import DeadTimeProcessor, DqToAbcActionProcessor  # noqa: F401
+from .physical_system_wrappers import CosSinProcessor, CurrentSumProcessor, DeadTimeProcessor, DqToAbcActionProcessor  # noqa: F401
+from .observation import ObservationStage  # noqa: F401
 from .physical_systems import (  # noqa: F401
     BatchedDcMotorSystem,
     BatchedDoublyFedInductionMotorSystem,

@@ -98,12 +98,32 @@ class GemxRefgenKindsConfig(C.Structure):
     ]
 
 
+OBS_MAX_POST = 32
+OBS_COPY, OBS_SUM, OBS_COSPI, OBS_SINPI = range(4)  # GEMX_OBS_*
+
+
+class GemxObsprocEntry(C.Structure):
+    """Mirror of `gemx_obsproc_entry` (include/gemx.h)."""
+
+    _fields_ = [("op", C.c_int32), ("src", C.c_int32), ("mask", C.c_uint32)]
+
+
+class GemxObsprocConfig(C.Structure):
+    """Mirror of `gemx_obsproc_config` (include/gemx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_in", C.c_int32), ("n_post", C.c_int32), ("n_ref", C.c_int32), ("flat", C.c_int32),
+        ("entries", GemxObsprocEntry * OBS_MAX_POST),
+    ]
+
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
     "gemx_refgen_rollout", "gemx_refgen_get_state", "gemx_refgen_step", "gemx_refgen_create_kinds", "gemx_refgen_get_params",
     "gemx_reset", "gemx_step", "gemx_rollout", "gemx_rollout_half", "gemx_get_state", "gemx_set_state", "gemx_get_switch_state",
     "gemx_set_switch_state", "gemx_aux_state_bytes", "gemx_get_aux_state", "gemx_set_aux_state", "gemx_reset_again", "gemx_rollout_synthetic", "gemx_synthetic_actions", "gemx_set_rate_limiter", "gemx_set_steps_per_block", "gemx_last_launch", "gemx_error_flags", "gemx_debug_read",
+    "gemx_obsproc_create", "gemx_obsproc_apply", "gemx_obsproc_destroy",
 )
 
 
@@ -157,6 +177,9 @@ def load():
     L.gemx_refgen_rollout.argtypes = [vp, vp, i32, vp, vp]
     L.gemx_refgen_get_state.argtypes = [vp, vp, vp, vp, vp]
     L.gemx_refgen_step.argtypes = [vp, vp, vp, vp]
+    L.gemx_obsproc_create.argtypes = [C.POINTER(GemxObsprocConfig), C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_obsproc_apply.argtypes = [vp, vp, vp, i64, vp, vp]
+    L.gemx_obsproc_destroy.argtypes = [vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

@@ -27,11 +27,24 @@ WeightedSumOfErrors reward, and the reference's shell semantics (core.py:300-371
 Two kernel launches per step, no host round trip; `bind_step` resolves everything once and can be captured in a HIP graph.
 The reference's other generator kinds (sinusoidal, step, triangular, sawtooth, Laplace process, constant) run on the same path: pass a
 holder named after the reference's class, a list of them or a `BatchedMultipleReferenceGenerator` as `reference_generator=`.
-`state_filter`, visualisation and `SwitchedReferenceGenerator` are outside the accelerated path.  For a full single-env GEM
-environment pass a `BatchedSCMLSystem(n_envs=1)` as `physical_system=` to the reference's own `ElectricMotorEnvironment`
-(INTEGRATION.md).
+
+The observation side runs on the device too (observation.py, csrc/gemx_obsproc.hip): `physical_system_wrappers=` may hold
+`CurrentSumProcessor` / `CosSinProcessor` holders (`"default"`: what the reference's env class wraps its system in -- the `i_sum` column
+of the six shunt envs), `observed_states=[names]` is the reference's `state_filter`, `flatten_observation=True` hands out ONE
+`[N, n_post + n_ref]` tensor, the processed state followed by the references.  One more launch per step, after the generators:
+
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator="default", flatten_observation=True,
+                  physical_system_wrappers=(ga.CosSinProcessor(remove_angle=True),), observed_states=["omega", "i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"])
+    obs, _ = env.reset()                                # [N, 5 + 2], ready for the policy
+
+Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the noisy state, which
+the fused kernels cannot reproduce in a post-pass), `FluxObserver`, reward weights or constraints on appended columns (`i_sum`,
+`cos(...)`), visualisation and `SwitchedReferenceGenerator`.  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
+`physical_system=` to the reference's own `ElectricMotorEnvironment`.
 """
 import re
+
+import numpy as np
 
 from .spaces import Box
 from . import components as comp
@@ -108,8 +121,7 @@ def default_components(env_id):
         d = dict(system=bps.BatchedDcMotorSystem, supply=dict(u_nominal=60.0), motor=motor_cls,
                  converter=comp.FiniteFourQuadrantConverter if finite else comp.ContFourQuadrantConverter,
                  constraints=("i_a", "i_e") if motor == "ShuntDc" else ("i",))
-        # NOTE: the reference's shunt envs additionally wrap the system in a CurrentSumProcessor ('i_sum' observation):
-        # observation post-processing, outside the accelerated path
+        # (the reference's shunt envs additionally wrap the system in a CurrentSumProcessor: default_physical_system_wrappers)
     else:
         motor_cls = {"PMSM": comp.PermanentMagnetSynchronousMotor, "SynRM": comp.SynchronousReluctanceMotor,
                      "SCIM": comp.SquirrelCageInductionMotor}[motor]
@@ -174,6 +186,17 @@ def default_env_modules(env_id):
     return dict(reference_states=states, generator=gen, reward=reward)
 
 
+def default_physical_system_wrappers(env_id):
+    """The physical-system wrappers the reference's env class puts around its system when the caller names none: the six shunt envs'
+    `CurrentSumProcessor(("i_a", "i_e"))` (envs/gym_dcm/shunt_dc_motor_env/*.py, e.g. cont_cc_shunt_dc_env.py:187), nothing elsewhere."""
+    from .physical_system_wrappers import CurrentSumProcessor
+
+    m = _ID.match(env_id)
+    if not m:
+        default_components(env_id)  # (raises the KeyError that names the supported ids)
+    return (CurrentSumProcessor(("i_a", "i_e")),) if m.group(3) == "ShuntDc" else ()
+
+
 def default_ode_solver(env_id, tau=None, load=None):
     """The solver `make(env_id)` uses when the caller names none.  The reference's default is scipy's ADAPTIVE dopri5 (rtol 1e-6,
     solvers.py:139-184); the device integrates with fixed steps, so the default is chosen per env such that the fp32 trajectories stay
@@ -199,18 +222,49 @@ def default_ode_solver(env_id, tau=None, load=None):
 class BatchedElectricMotorEnv:
     """Vector-env style shell around a batched physical system (physics + done mask only)."""
 
-    def __init__(self, physical_system):
+    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False):
+        """observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
+        `step()` and `rollout()` then return the PROCESSED state, `state_space` / `state_names` describe it; `physical_system` stays raw."""
         self.physical_system = physical_system
         self.action_space = physical_system.action_space
         self.state_space = physical_system.state_space
+        self.state_names = list(physical_system.state_names)
         self.n_envs = physical_system.n_envs
+        self.observation_stage = None
+        self._raw_scratch = None
+        if observation is not None:
+            from .observation import ObservationStage
+
+            if getattr(physical_system, "_obs_layout", "aos") != "aos":
+                raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
+            stage = ObservationStage(physical_system, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
+                                     n_ref=_n_ref)
+            self.observation_stage = stage
+            self.state_space = stage.observation_space
+            self.state_names = list(stage.observation_names)
+            if not _defer_create:
+                ps = physical_system
+                stage.create(ps._device, ps._dtype_name)
+                self._pstate = bps._torch().empty((ps.n_envs, stage.n_post), dtype=ps._tdtype, device=ps._tdev)
 
     @property
     def unwrapped(self):
         return self
 
+    def _processed(self, raw):
+        """The stage on the system's internal state buffer (n_envs == 1 with numpy in / out keeps numpy)."""
+        self.observation_stage.apply(self.physical_system._obs, out=self._pstate)
+        if isinstance(raw, np.ndarray):
+            return self._pstate.reshape(-1).double().cpu().numpy()
+        return self._pstate
+
+    def _processed_trajectory(self, raw, obs_out=None):
+        return self.observation_stage.apply(raw, out=obs_out)
+
     def reset(self, seed=None, options=None):
         """All envs to the initial state; returns (observations, {})."""
+        if self.observation_stage is not None:
+            return self._processed(self.physical_system.reset()), {}
         return self.physical_system.reset(), {}
 
     def step(self, actions, references=None):
@@ -220,22 +274,58 @@ class BatchedElectricMotorEnv:
         right after that restart is `physical_system.reset_observation`."""
         if references is not None:
             obs = self.physical_system.simulate(actions, references=references)
+            if self.observation_stage is not None:
+                obs = self._processed(obs)
             return obs, self.physical_system.reward, self.physical_system.done, False, {}
         obs = self.physical_system.simulate(actions)
+        if self.observation_stage is not None:
+            obs = self._processed(obs)
         return obs, None, self.physical_system.done, False, {}
 
-    def rollout(self, actions, **kw):
-        return self.physical_system.rollout(actions, **kw)
+    def rollout(self, actions, obs_out=None, **kw):
+        """PhysicalSystem.rollout; with an observation stage the raw trajectory goes into a scratch tensor and ONE `apply` writes the
+        processed `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
+        if self.observation_stage is None:
+            return self.physical_system.rollout(actions, obs_out=obs_out, **kw)
+        res = self.physical_system.rollout(actions, obs_out=self._scratch(int(actions.shape[0]), kw.get("last_only", False)), **kw)
+        return (self._processed_trajectory(res[0], obs_out),) + tuple(res[1:])
 
-    def rollout_synthetic(self, K, **kw):
+    def _scratch(self, K, last_only=False):
+        ps = self.physical_system
+        shape = tuple(ps._obs.shape) if last_only else (K,) + tuple(ps._obs.shape)
+        if self._raw_scratch is None or tuple(self._raw_scratch.shape) != shape:
+            self._raw_scratch = bps._torch().empty(shape, dtype=ps._tdtype, device=ps._tdev)
+        return self._raw_scratch
+
+    def rollout_synthetic(self, K, obs_out=None, **kw):
         """K fused steps on random actions generated on the device (PhysicalSystem.rollout_synthetic)."""
-        return self.physical_system.rollout_synthetic(K, **kw)
+        if self.observation_stage is None:
+            return self.physical_system.rollout_synthetic(K, obs_out=obs_out, **kw)
+        res = self.physical_system.rollout_synthetic(K, obs_out=self._scratch(K), **kw)
+        return (self._processed_trajectory(res[0], obs_out),) + tuple(res[1:])
 
     def bind_rollout(self, actions, obs_out, done_out, stream=None):
-        """-> zero-argument launch(): the pre-bound `gemx_rollout` call for fixed tensors (PhysicalSystem.bind_rollout)."""
-        return self.physical_system.bind_rollout(actions, obs_out, done_out, stream=stream)
+        """-> zero-argument launch(): the pre-bound `gemx_rollout` call for fixed tensors (PhysicalSystem.bind_rollout); with an
+        observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus one `apply`."""
+        if self.observation_stage is None:
+            return self.physical_system.bind_rollout(actions, obs_out, done_out, stream=stream)
+        ps = self.physical_system
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        raw = self._scratch(int(actions.shape[0]))
+        physics = ps.bind_rollout(actions, raw, done_out, stream=stream)
+        post = self.observation_stage.bind_apply(raw, None, obs_out, stream)
+        out = (obs_out, done_out)
+
+        def launch():
+            physics()
+            post()
+            return out
+
+        return launch
 
     def close(self):
+        if self.observation_stage is not None:
+            self.observation_stage.close()
         self.physical_system.close()
 
 
@@ -250,9 +340,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     _REWARD_KEYS = ("reward_weights", "gamma", "reward_power", "bias", "violation_reward", "normed_reward_weights")
 
-    def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False):
+    def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None):
         super().__init__(physical_system)
         ps = physical_system
+        if observation is not None and getattr(ps, "_obs_layout", "aos") != "aos":
+            raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
         d = default_modules or dict(reference_states=(), reward=dict())
         if getattr(ps, "_obs_layout", "aos") != "aos":
             raise ValueError("the complete env needs obs_layout='aos' (states [N, S_out])")
@@ -277,7 +369,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         self.reward_range = ps.reward_range
         lo, hi = gen.reference_space
         self.reference_space = Box(lo, hi, dtype=float)
+        stage = None
+        if observation is not None:  # (after the generator: a flat observation carries its n_ref columns)
+            from .observation import ObservationStage
+
+            stage = ObservationStage(ps, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
+                                     n_ref=len(self.reference_names))
+            self.state_space = stage.observation_space
+            self.state_names = list(stage.observation_names)
+        self.observation_stage = stage
         self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
+        if stage is not None and stage.flatten:  # FlattenObservation of that Tuple: one box, state then reference
+            self.observation_space = Box(np.concatenate((self.state_space.low, self.reference_space.low)),
+                                         np.concatenate((self.state_space.high, self.reference_space.high)), dtype=float)
         self._bound = None
         if _defer_create:
             return
@@ -286,6 +390,14 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps._reward_buf = self._reward  # (`physical_system.reward` shows the same buffer)
         self._refs = gen.references
         self._obs = (ps._obs, self._refs)
+        if stage is not None:
+            stage.create(ps._device, ps._dtype_name)
+            self._pstate = torch.empty((ps.n_envs, stage.n_out), dtype=ps._tdtype, device=ps._tdev)
+            self._obs = self._pstate if stage.flatten else (self._pstate, self._refs)
+
+    def _stage_launcher(self, stream):
+        """The third launch of a step: the observation stage on the fresh state rows and the references the generators just wrote."""
+        return self.observation_stage.bind_apply(self.physical_system._obs, self._refs, self._pstate, stream)
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state, all generators restarted and advanced once (core.py:312-313, 485-505).
@@ -294,6 +406,8 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps.reset()
         gen.reset()
         gen.step(None)
+        if self.observation_stage is not None:
+            self.observation_stage.apply(ps._obs, self._refs, out=self._pstate)
         return self._obs, {}
 
     def _launchers(self, action_ptr, stream):
@@ -307,6 +421,13 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         args = (C.c_void_p(action_ptr), 1, C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr),
                 C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
         gen_step = gen.bind_step(ps._done, stream=stream)
+        if self.observation_stage is not None:  # generators, then the stage: it reads the references the observation must carry
+            gen_only, post = gen_step, self._stage_launcher(stream)
+
+            def gen_step():
+                gen_only()
+                post()
+
         call = L.gemx_rollout_reward
 
         def physics(_args=args, _call=call):
@@ -318,7 +439,8 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         return physics, gen_step
 
     def step(self, actions, references=None):
-        """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches."""
+        """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches; three with
+        an observation stage, whose processed state (or flat `[N, n_post + n_ref]` observation) replaces the raw one."""
         if references is not None:
             raise TypeError("the complete env generates its references: step(actions)")
         ps = self.physical_system
@@ -335,7 +457,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     def bind_step(self, action_buffer, stream=None):
         """A zero-argument `step()` for a closed loop that reuses ONE action tensor: -> `(step, (state, ref), reward, done)`; `step()`
-        enqueues the two launches and returns `(state, ref)`.  Nothing is looked up, allocated or synchronised per call, and no step
+        enqueues the two launches (three with an observation stage) and returns the observation.  Nothing is looked up, allocated or synchronised per call, and no step
         index lives on the host, so `step` can be captured with `torch.cuda.graph` (a linear graph) and replayed -- with the Wiener
         and the other device generators; a ReplayReferenceGenerator keeps its row index on the host and refuses to step while a stream is capturing."""
         ps = self.physical_system
@@ -356,15 +478,18 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     def close(self):
         self.reference_generator.close()
-        super().close()
+        super().close()  # (closes the observation stage too)
 
 
 def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, load=None, ode_solver=None, tau=None,
          constraints=None, dtype="float32", auto_reset=None, obs_layout="aos", physical_system_wrappers=(), reference_generator=None,
-         reward_function=None, state_filter=None, **kwargs):
+         reward_function=None, state_filter=None, observed_states=None, flatten_observation=False, **kwargs):
     """Build a batched env.  Component arguments follow the reference's env-arg convention (instance | dict | None).
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
-    (or the reference's own instances); they are folded into the kernel's action stage.
+    (or the reference's own instances), which are folded into the kernel's action stage, and of CurrentSumProcessor / CosSinProcessor
+    holders, which become the device-side observation stage; 'default': `default_physical_system_wrappers(env_id)`.
+    observed_states: None | list of state names of the wrapped system -- the reference's `state_filter`, applied last.
+    flatten_observation: the complete env hands out ONE tensor [N, n_post + n_ref], the processed state followed by the references.
     reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
     StepReferenceGenerator(...) or a list of holders (one per referenced state; the reference's own generator instances are read the
     same way) | ReplayReferenceGenerator;
@@ -374,10 +499,21 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     from .physical_system_wrappers import fold_wrappers
 
     if state_filter is not None:
-        raise NotImplementedError("state_filter is outside the accelerated path: select the columns of the returned state tensor "
-                                  "(`physical_system.state_positions`) instead")
+        raise NotImplementedError("state_filter is spelled observed_states=[names] on the accelerated path (a device-side column selection, "
+                                  "applied after the physical-system wrappers)")
+    if isinstance(physical_system_wrappers, str):
+        if physical_system_wrappers != "default":
+            raise ValueError("physical_system_wrappers: a tuple of wrapper holders or 'default'")
+        physical_system_wrappers = default_physical_system_wrappers(env_id)
+    chain = []
     if physical_system_wrappers:
-        kwargs = dict(kwargs, **fold_wrappers(physical_system_wrappers))
+        kwargs = dict(kwargs, **fold_wrappers(physical_system_wrappers, observation_chain=chain))
+    observation = None
+    if chain or observed_states is not None or flatten_observation:
+        if obs_layout != "aos":
+            raise ValueError("the observation stage (observation-side wrappers, observed_states, flatten_observation) reads state rows: "
+                             "it needs obs_layout='aos', not 'soa'")
+        observation = dict(chain=tuple(chain), observed_states=observed_states, flatten=bool(flatten_observation))
     d = default_components(env_id)
     tau = d["tau"] if tau is None else tau
     conv_cls = d["converter"]
@@ -400,7 +536,7 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         **kwargs,
     )
     if reference_generator is None and reward_function is None:
-        return BatchedElectricMotorEnv(system)
+        return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)))
     from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators
 
     modules = default_env_modules(env_id)
@@ -418,4 +554,4 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     if not (reward_function is None or isinstance(reward_function, dict) or (isinstance(reward_function, str) and reward_function == "default")):
         raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
     return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,
-                                           _defer_create=bool(kwargs.get("_defer_create", False)))
+                                           _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation)

@@ -1,0 +1,228 @@
+"""Device-side observation stage: what the reference's observation-side physical-system wrappers, the env shell's `state_filter`
+and gymnasium's FlattenObservation do to a state, as ONE kernel launch over the state rows the stepping kernels wrote
+(csrc/gemx_obsproc.hip, include/gemx.h: gemx_obsproc_*).
+
+`ObservationStage(physical_system, chain, observed_states=None, flatten=False, n_ref=0)` resolves the chain the way the reference's
+`set_physical_system` calls do -- innermost first, every processor seeing the state names of what is beneath it -- into
+
+* the metadata the WRAPPED system shows: `state_names`, `state_positions`, `limits`, `nominal_state`, `state_space`
+  (current_sum_processor.py:24-44, cos_sin_processor.py:33-50), plus `state_filter` (core.py:273-277: indices into those names) and
+  `observation_names` / `observation_space` (the filtered state the observation carries);
+* a flat COLUMN PROGRAM over the base system's columns, one entry `(op, src, mask)` per observed column: COPY a column, SUM the columns
+  of a bit mask, cos / sin of pi times a column.  The program is one level deep: a processor whose source is itself a derived column
+  (`CosSinProcessor(angle='i_sum')`, a current sum over another `i_sum`) is refused by name.
+
+`remove_angle=True`: the reference's CosSinProcessor deletes the angle in `simulate()` but forgets to in `reset()`
+(cos_sin_processor.py:52-55 against 57-62), so its reset state is one column longer than its step state and than its own state space.
+A batched tensor has one shape: the stage uses `simulate()`'s -- the shape the wrapper's `state_space`, `state_names` and `limits`
+describe -- everywhere, reset included.
+
+`apply(state [..., n_in], refs=None, out=None)` runs the program on any contiguous trajectory; `evaluate(state)` is the same program on
+the host in numpy (float64 unless told otherwise), for tests and for data that never was on a device.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .spaces import Box
+
+_OPS = {"copy": _lib.OBS_COPY, "sum": _lib.OBS_SUM, "cospi": _lib.OBS_COSPI, "sinpi": _lib.OBS_SINPI}
+
+
+class _Column:
+    __slots__ = ("name", "op", "src", "mask", "limit", "nominal", "low", "high")
+
+    def __init__(self, name, op, src, mask, limit, nominal, low, high):
+        self.name, self.op, self.src, self.mask = name, op, src, mask
+        self.limit, self.nominal, self.low, self.high = float(limit), float(nominal), float(low), float(high)
+
+
+def _source(col, what):
+    if col.op != "copy":
+        raise ValueError(f"{what}: its source {col.name!r} is itself a derived column; the device-side column program is one level deep "
+                         "(sources must be states of the base physical system)")
+    return col.src
+
+
+class ObservationStage:
+    """The resolved observation stage of one physical system (see the module docstring)."""
+
+    def __init__(self, physical_system, chain=(), observed_states=None, flatten=False, n_ref=0):
+        ps = physical_system
+        names = [str(n) for n in ps.state_names]
+        self.n_in = len(names)
+        self.n_ref = int(n_ref)
+        self.flatten = bool(flatten)
+        if not 0 <= self.n_ref <= _lib.MAX_REF:
+            raise ValueError(f"n_ref must be in [0, {_lib.MAX_REF}]")
+        low, high = np.asarray(ps.state_space.low, dtype=float), np.asarray(ps.state_space.high, dtype=float)
+        cols = [_Column(n, "copy", j, 0, ps.limits[j], ps.nominal_state[j], low[j], high[j]) for j, n in enumerate(names)]
+        positions = {n: j for j, n in enumerate(names)}
+        self.chain = tuple(chain)
+        for spec in self.chain:
+            if spec[0] == "sum":
+                _, currents, limit = spec
+                idx = [positions[c] for c in currents]  # (KeyError for an unknown name, as current_sum_processor.py:27)
+                if len(set(idx)) != len(idx) or not idx:
+                    raise ValueError(f"CurrentSumProcessor({list(currents)}): the currents must be distinct and at least one")
+                mask = 0
+                for i in idx:
+                    mask |= 1 << _source(cols[i], f"CurrentSumProcessor({list(currents)})")
+                f = max if limit == "max" else np.sum
+                cols.append(_Column("i_sum", "sum", 0, mask, f(np.array([cols[i].limit for i in idx])), f(np.array([cols[i].nominal for i in idx])), -1.0, 1.0))
+                positions = dict(positions)
+                positions["i_sum"] = [c.name for c in cols].index("i_sum")
+            elif spec[0] == "cossin":
+                _, angle, remove = spec
+                i = positions[angle]  # (KeyError for an unknown name, as cos_sin_processor.py:36)
+                src = _source(cols[i], f"CosSinProcessor({angle!r})")
+                if remove:
+                    del cols[i]
+                cols.append(_Column(f"cos({angle})", "cospi", src, 0, 1.0, 1.0, -1.0, 1.0))
+                cols.append(_Column(f"sin({angle})", "sinpi", src, 0, 1.0, 1.0, -1.0, 1.0))
+                positions = {c.name: j for j, c in enumerate(cols)}
+            else:
+                raise ValueError(f"unknown observation-stage spec {spec!r}")
+        # the wrapped system's metadata
+        self.state_names = [c.name for c in cols]
+        self.state_positions = positions
+        self.limits = np.array([c.limit for c in cols])
+        self.nominal_state = np.array([c.nominal for c in cols])
+        self.state_space = Box(np.array([c.low for c in cols]), np.array([c.high for c in cols]), dtype=np.float64)
+        # the env shell's state_filter, applied last (core.py:273-277)
+        observed = list(observed_states) if observed_states is not None else list(self.state_names)
+        self.state_filter = [self.state_names.index(s) for s in observed]
+        if not self.state_filter:
+            raise ValueError("observed_states selects no state")
+        self._cols = [cols[i] for i in self.state_filter]
+        self.observation_names = [c.name for c in self._cols]
+        self.observation_space = Box(self.state_space.low[self.state_filter], self.state_space.high[self.state_filter], dtype=np.float64)
+        self.n_post = len(self._cols)
+        if self.n_post > _lib.OBS_MAX_POST:
+            raise ValueError(f"the observation has {self.n_post} columns, the device-side stage at most {_lib.OBS_MAX_POST}")
+        if self.n_in > _lib.MAX_OUT:
+            raise ValueError(f"the physical system has {self.n_in} states, the device-side stage reads at most {_lib.MAX_OUT}")
+        self.n_out = self.n_post + (self.n_ref if self.flatten else 0)
+        self.program = [(c.op, c.src, c.mask) for c in self._cols]
+        self._cfg = self._build_config()
+        self._handle = None
+
+    @property
+    def is_identity(self):
+        return not self.flatten and self.n_post == self.n_in and all(op == "copy" and src == j for j, (op, src, _) in enumerate(self.program))
+
+    def _build_config(self):
+        cfg = _lib.GemxObsprocConfig()
+        cfg.struct_size = C.sizeof(_lib.GemxObsprocConfig)
+        cfg.n_in, cfg.n_post, cfg.n_ref, cfg.flat = self.n_in, self.n_post, self.n_ref, int(self.flatten)
+        for c, (op, src, mask) in enumerate(self.program):
+            cfg.entries[c].op, cfg.entries[c].src, cfg.entries[c].mask = _OPS[op], src, mask
+        return cfg
+
+    # ------------------------------------------------------------------ host-side evaluator
+    def evaluate(self, state, refs=None, dtype=np.float64):
+        """The program in numpy on `state [..., n_in]` (computed in `dtype`; sums sequentially in ascending column order, as the kernel
+        adds them) -> [..., n_post], or with `flatten` [..., n_post + n_ref]."""
+        s = np.asarray(state, dtype=dtype)
+        if s.shape[-1] != self.n_in:
+            raise ValueError(f"state has {s.shape[-1]} columns, the stage reads {self.n_in}")
+        out = np.empty(s.shape[:-1] + (self.n_out,), dtype=dtype)
+        for c, (op, src, mask) in enumerate(self.program):
+            if op == "copy":
+                out[..., c] = s[..., src]
+            elif op == "sum":
+                js = [j for j in range(self.n_in) if mask >> j & 1]
+                acc = s[..., js[0]].copy()
+                for j in js[1:]:
+                    acc = acc + s[..., j]
+                out[..., c] = acc
+            else:
+                x = s[..., src].astype(np.float64) * np.pi
+                out[..., c] = (np.cos(x) if op == "cospi" else np.sin(x)).astype(dtype)
+        if self.flatten and self.n_ref:
+            out[..., self.n_post:] = np.asarray(refs, dtype=dtype).reshape(s.shape[:-1] + (self.n_ref,))
+        return out
+
+    # ------------------------------------------------------------------ device side
+    def create(self, device, dtype_name="float32"):
+        """Create the device handle (no CPU fallback: without a HIP device this raises)."""
+        import torch
+
+        L = _lib.load()
+        h = C.c_void_p()
+        _lib.check(L.gemx_obsproc_create(C.byref(self._cfg), _lib.F64 if dtype_name == "float64" else _lib.F32, int(device), C.byref(h)))
+        self._handle, self._L = h, L
+        self._tdev = torch.device("cuda", int(device))
+        self._tdtype = torch.float64 if dtype_name == "float64" else torch.float32
+        return self
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None:
+            self._L.gemx_obsproc_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, t, cols, what):
+        import torch
+
+        if not (torch.is_tensor(t) and t.device == self._tdev and t.dtype == self._tdtype and t.is_contiguous() and t.dim() >= 1 and t.shape[-1] == cols):
+            raise ValueError(f"{what} must be a contiguous {self._tdtype} tensor [..., {cols}] on {self._tdev}")
+
+    def apply(self, state, refs=None, out=None, stream=None):
+        """state [..., n_in] (contiguous device tensor) -> out [..., n_post] (or [..., n_post + n_ref] with `flatten`, reading refs
+        [..., n_ref]).  One kernel launch on `stream` (default: the current one); `out` is allocated unless given and must not alias
+        the inputs."""
+        import torch
+
+        if self._handle is None:
+            raise _lib.GemxError("the observation stage has no device handle (built with _defer_create, or closed)")
+        self._check(state, self.n_in, "state")
+        lead = tuple(state.shape[:-1])
+        need_refs = self.flatten and self.n_ref > 0
+        if need_refs:
+            if refs is None:
+                raise ValueError(f"a flat observation needs refs [..., {self.n_ref}]")
+            self._check(refs, self.n_ref, "refs")
+            if tuple(refs.shape[:-1]) != lead:
+                raise ValueError(f"refs {tuple(refs.shape)} do not match state {tuple(state.shape)}")
+        if out is None:
+            out = torch.empty(lead + (self.n_out,), dtype=self._tdtype, device=self._tdev)
+        else:
+            self._check(out, self.n_out, "out")
+            if tuple(out.shape[:-1]) != lead:
+                raise ValueError(f"out {tuple(out.shape)} does not match state {tuple(state.shape)}")
+        rows = state.numel() // self.n_in
+        st = (stream if stream is not None else torch.cuda.current_stream(self._tdev)).cuda_stream
+        _lib.check(self._L.gemx_obsproc_apply(self._handle, C.c_void_p(state.data_ptr()), C.c_void_p(refs.data_ptr()) if need_refs else None, rows,
+                                              C.c_void_p(out.data_ptr()), C.c_void_p(st)))
+        return out
+
+    def bind_apply(self, state, refs, out, stream):
+        """-> zero-argument launch() of `apply` on fixed tensors: everything is checked and resolved here, once."""
+        if self._handle is None:
+            raise _lib.GemxError("the observation stage has no device handle (built with _defer_create, or closed)")
+        self._check(state, self.n_in, "state")
+        self._check(out, self.n_out, "out")
+        if self.flatten and self.n_ref > 0:
+            self._check(refs, self.n_ref, "refs")
+            if tuple(refs.shape[:-1]) != tuple(state.shape[:-1]):
+                raise ValueError(f"refs {tuple(refs.shape)} do not match state {tuple(state.shape)}")
+        if tuple(out.shape[:-1]) != tuple(state.shape[:-1]):
+            raise ValueError(f"out {tuple(out.shape)} does not match state {tuple(state.shape)}")
+        need_refs = self.flatten and self.n_ref > 0
+        args = (C.c_void_p(state.data_ptr()), C.c_void_p(refs.data_ptr()) if need_refs else None, state.numel() // self.n_in, C.c_void_p(out.data_ptr()),
+                C.c_void_p(stream.cuda_stream))
+        call, check = self._L.gemx_obsproc_apply, _lib.check
+
+        def launch(_args=args, _call=call, _keep=(state, refs, out, stream)):
+            rc = _call(self._handle, *_args)
+            if rc:
+                check(rc)
+
+        return launch

@@ -1,14 +1,23 @@
-"""Parameter-holder mirrors of the two ACTION-side physical-system wrappers that sit directly in front of `simulate()`
-(SURVEY.md section 8f rank 2).  They contain no logic: `make(..., physical_system_wrappers=(...))` (or the
-`action_delay=` / `action_frame=` arguments of `BatchedSCMLSystem`) folds them into the kernel's action stage, so the
-fused rollout stays on the device.
+"""Parameter-holder mirrors of the reference's physical-system wrappers that run on the device.  They contain no logic:
+`make(..., physical_system_wrappers=(...))` splits the tuple with `fold_wrappers`.
+
+ACTION side, in front of `simulate()`: folded into the kernel's action stage (or passed as the
+`action_delay=` / `action_frame=` arguments of `BatchedSCMLSystem`), so the fused rollout stays on the device.
 
     DeadTimeProcessor(steps[, reset_action]) physical_system_wrappers/dead_time_processor.py:8-85
     DqToAbcActionProcessor.make(motor_type)  physical_system_wrappers/dq_to_abc_action_processor.py:9-175
 
+OBSERVATION side, behind `simulate()`: resolved by `observation.ObservationStage` into the column program of ONE post-processing
+kernel (csrc/gemx_obsproc.hip) that reads the state rows the stepping kernels wrote.
+
+    CurrentSumProcessor(currents[, limit])          physical_system_wrappers/current_sum_processor.py:7-65
+    CosSinProcessor([angle][, remove_angle])        physical_system_wrappers/cos_sin_processor.py:7-89
+
 As in the reference, wrappers are applied innermost first: `(DeadTimeProcessor(2), DqToAbcActionProcessor.make("PMSM"))`
-delays the abc action by two steps and lets the dq processor advance its angle by 0.5 + 2 steps (lines 83-86).
-Observation-side wrappers (flux observer, cos/sin, current sum, noise) are post-processing and stay on the host.
+delays the abc action by two steps and lets the dq processor advance its angle by 0.5 + 2 steps (lines 83-86); an observation-side
+processor sees the state names of everything listed before it.  The two sides do not interact, so they may be listed in any order.
+Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the NOISY state,
+core.py:344-350, and those are fused into the stepping kernels) and `FluxObserver`.
 """
 
 
@@ -67,13 +76,61 @@ class DqToAbcActionProcessor:
         return cls(motor_type)
 
 
-def fold_wrappers(wrappers):
+class CurrentSumProcessor:
+    """Appends `i_sum`, the sum of the named currents, to the state vector (current_sum_processor.py:10-22); its limit and nominal
+    value are the maximum (`limit='max'`) or the sum (`'sum'`) of the source currents'."""
+
+    def __init__(self, currents, limit="max", physical_system=None):
+        self._currents = currents
+        assert limit in ["max", "sum"]
+        self._limit_name = limit
+
+
+class CosSinProcessor:
+    """Appends `cos(angle)` and `sin(angle)` of one state (an angle normalised to pi) to the state vector, optionally removing the
+    angle itself (cos_sin_processor.py:19-31)."""
+
+    def __init__(self, angle="epsilon", physical_system=None, remove_angle=False):
+        self._angle = angle
+        self._remove_angle = remove_angle
+
+    @property
+    def angle(self):
+        return self._angle
+
+
+STATE_NOISE_REFUSAL = ("StateNoiseProcessor is not on the accelerated path: the reference checks the constraints and computes the reward on the NOISY "
+                       "state (core.py:344-350), and the done mask, the auto-reset and the reward are fused into the stepping kernels, which a pass "
+                       "over their output cannot reproduce")
+
+
+def _observation_spec(w, names):
+    """('sum', currents, 'max' | 'sum') | ('cossin', angle, remove_angle) | None for an observation-side wrapper (holder or the reference's instance)."""
+    if "CurrentSumProcessor" in names:
+        limit = getattr(w, "_limit_name", None)
+        if limit is None:  # the reference's instance keeps the function: `max` or `np.sum`
+            limit = "max" if getattr(w, "_limit", max) is max else "sum"
+        return ("sum", tuple(w._currents), limit)
+    if "CosSinProcessor" in names:
+        return ("cossin", w._angle, bool(w._remove_angle))
+    return None
+
+
+def fold_wrappers(wrappers, observation_chain=None):
     """-> dict(action_delay=..., action_frame=...[, action_delay_reset=...]) for BatchedSCMLSystem from a reference-style wrapper tuple (innermost first).
-    Accepts this module's holders and the reference's own instances (by class name)."""
+    Accepts this module's holders and the reference's own instances (by class name).  The observation-side processors
+    (CurrentSumProcessor, CosSinProcessor), in any position, are appended to the list `observation_chain` as specs for
+    `observation.ObservationStage`, innermost first; without such a list they are refused like any other wrapper the kernels' action stage
+    cannot hold."""
     delay, frame, seen_dq, reset_row = 0, None, False, None  # frame None: leave it to the system's control_space
     for w in wrappers:
         names = {c.__name__ for c in type(w).__mro__}
-        if "DeadTimeProcessor" in names:
+        spec = _observation_spec(w, names)
+        if spec is not None and observation_chain is not None:
+            observation_chain.append(spec)
+        elif "StateNoiseProcessor" in names:
+            raise NotImplementedError(STATE_NOISE_REFUSAL)
+        elif "DeadTimeProcessor" in names:
             if seen_dq:
                 raise ValueError("DeadTimeProcessor must be wrapped INSIDE the DqToAbcActionProcessor (listed before it), as the "
                                  "reference's processor expects (dq_to_abc_action_processor.py:83-86)")

@@ -376,6 +376,43 @@ int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs
  * high/low ratio r), roll.  A handle that runs the all-Wiener kernels does not track index and length: both read -1. */
 int gemx_refgen_get_params(gemx_refgen *r, int32_t *kind_index_len_out_dev, double *params_out_dev, void *stream);
 
+/* Device-side OBSERVATION STAGE: the observation-side physical-system wrappers of the reference (CurrentSumProcessor,
+ * physical_system_wrappers/current_sum_processor.py:40-57; CosSinProcessor, cos_sin_processor.py:52-66), the env shell's state_filter
+ * (core.py:273-276, 317, 366) and the flat (state || reference) vector FlattenObservation makes of the shell's Tuple, in ONE pass over the
+ * state rows the stepping kernels wrote.  A handle holds a COLUMN PROGRAM: output column c of a row is
+ *   GEMX_OBS_COPY   in[src]                                                          (the same bits)
+ *   GEMX_OBS_SUM    the sum of in[j] over the set bits j of mask, added in ascending j with plain adds: no fused multiply-add, no
+ *                   reassociation -- numpy's sequential float32 / float64 sum, bit for bit
+ *   GEMX_OBS_COSPI  cos(pi * in[src]) }  evaluated in half-turns: the state's epsilon IS an angle in units of pi (limit pi), and it is
+ *   GEMX_OBS_SINPI  sin(pi * in[src]) }  never multiplied by a rounded pi first: +-1 and +-0.5 give 0 / +-1 exactly
+ * The program is one level deep (every source is an input column).  It is uniform over the rows and travels as a kernel argument.
+ *   gemx_obsproc_apply: state_dev [rows][n_in] R (a trajectory [K][N][n_in] is rows = K * N contiguous rows) -> out_dev
+ *   [rows][n_post] R, or with flat = 1 [rows][n_post + n_ref] R: the processed state followed by that row's n_ref references from
+ *   refs_dev [rows][n_ref] R (flat = 0: refs_dev is not read and may be NULL; so it may with n_ref = 0).  The tensors need the alignment
+ *   of R only (a 4-byte aligned fp32 base is legal); in and out must not overlap.  One kernel launch, nothing else: no per-call host
+ *   state, no device counters, no allocation, no synchronisation -- a captured call replays.  rows = 0 is a no-op.
+ * GEMX_ERR_ARG at create: a null pointer, struct_size, n_in outside [1, GEMX_MAX_OUT], n_post outside [1, GEMX_OBS_MAX_POST], n_ref
+ * outside [0, GEMX_MAX_REF], flat not 0 | 1, an unknown op, a src or a mask bit >= n_in, a SUM with an empty mask. */
+#define GEMX_OBS_MAX_POST 32
+enum { GEMX_OBS_COPY = 0, GEMX_OBS_SUM = 1, GEMX_OBS_COSPI = 2, GEMX_OBS_SINPI = 3 };
+typedef struct gemx_obsproc_entry {
+    int32_t op;    /* GEMX_OBS_* */
+    int32_t src;   /* input column (COPY, COSPI, SINPI); ignored by SUM */
+    uint32_t mask; /* SUM: bit j set = input column j is a summand; ignored by the others */
+} gemx_obsproc_entry;
+typedef struct gemx_obsproc_config {
+    int32_t struct_size; /* = sizeof(gemx_obsproc_config) */
+    int32_t n_in;        /* columns of a state row: 1..GEMX_MAX_OUT */
+    int32_t n_post;      /* processed-state columns: 1..GEMX_OBS_MAX_POST */
+    int32_t n_ref;       /* reference columns appended when flat = 1: 0..GEMX_MAX_REF */
+    int32_t flat;        /* 1: out rows are (processed state || references) */
+    gemx_obsproc_entry entries[GEMX_OBS_MAX_POST];
+} gemx_obsproc_config;
+typedef struct gemx_obsproc gemx_obsproc;
+int gemx_obsproc_create(const gemx_obsproc_config *cfg, int dtype, int device, gemx_obsproc **out);
+int gemx_obsproc_apply(gemx_obsproc *p, const void *state_dev, const void *refs_dev, int64_t rows, void *out_dev, void *stream);
+int gemx_obsproc_destroy(gemx_obsproc *p);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
