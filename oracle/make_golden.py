@@ -53,7 +53,8 @@ def make_solver(name):
 
 
 def gen_actions(space_kind, K, seed, mode):
-    """uniform: iid every step.  held: piecewise-constant for random dwell times."""
+    """uniform: iid every step.  held: piecewise-constant for random dwell times.  held_pos: the same with every continuous value in
+    [0.75, 1] (a series machine's current only reaches its limit under a voltage that stays high for hundreds of steps)."""
     rng = np.random.default_rng(seed)
     if space_kind == "box1":
         shape, disc = (K, 1), False
@@ -84,7 +85,7 @@ def gen_actions(space_kind, K, seed, mode):
         if disc:
             v = rng.integers(0, nact)  # array-valued `nact` -> one draw per sub-converter
         else:
-            v = rng.uniform(-1, 1, shape[1:]) * rng.uniform(0.0, 1.0)
+            v = rng.uniform(0.75, 1, shape[1:]) if mode == "held_pos" else rng.uniform(-1, 1, shape[1:]) * rng.uniform(0.0, 1.0)
         out[k : k + dwell] = v
         k += dwell
     return out
@@ -252,10 +253,14 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
     extra = {}
     if record_reward:
         rf = env._reward_function  # WeightedSumOfErrors (reward_functions/weighted_sum_of_errors.py:88-129)
-        meta["reward"] = dict(weights=[float(x) for x in rf._reward_weights], powers=[float(x) for x in np.asarray(rf._n, dtype=float)],
-                              state_length=[float(x) for x in rf._state_length], bias=float(rf._bias),
+        # columns a wrapper appended behind the physical system's own (the shunt envs' 'i_sum') are dropped as they are from the states:
+        # they carry no weight and no reference, so nothing of the reward goes with them
+        assert not np.any(np.asarray(rf._reward_weights)[n_keep:]) and not np.any(env.reference_generator.referenced_states[n_keep:])
+        meta["reward"] = dict(weights=[float(x) for x in rf._reward_weights[:n_keep]],
+                              powers=[float(x) for x in np.asarray(rf._n, dtype=float)[:n_keep]],
+                              state_length=[float(x) for x in rf._state_length[:n_keep]], bias=float(rf._bias),
                               violation_reward=float(rf._violation_reward),
-                              referenced_states=[bool(x) for x in env.reference_generator.referenced_states])
+                              referenced_states=[bool(x) for x in env.reference_generator.referenced_states[:n_keep]])
         extra = dict(references=np.asarray(recorder.references)[:, :n_keep], rewards=np.asarray(recorder.rewards))
         assert len(recorder.rewards) == K
     np.savez_compressed(
@@ -416,6 +421,8 @@ def main(only=None):
         main_wrappers()
     if not only or "reward" in only:
         main_reward()
+    if only and "reward_new" in only:
+        main_reward_lengths_and_terms()
     if not only or "supply" in only:
         main_supply()
     if not only or "init" in only:
@@ -638,6 +645,25 @@ def main_reward():
     run_case("rw_eesm_cont_cc_pow_mixed_epi_held_euler", "Cont-CC-EESM-v0", "euler", K, 1406, "held", True, "box4", record_reward=True,
              reward_function=WeightedSumOfErrors(reward_weights=dict(i_sd=0.4, i_sq=0.4, i_e=0.2), reward_power=dict(i_sd=1, i_sq=2, i_e=0.5),
                                                  gamma=0.95))
+    main_reward_lengths_and_terms()
+
+
+def main_reward_lengths_and_terms():
+    """States of length 1 (the series and shunt machines' speed, the series machine's torque: their state space starts at 0, so the error
+    is divided by 1, not 2) and more weighted states than the device keeps in registers (four), with and without general powers."""
+    from gym_electric_motor.reward_functions import WeightedSumOfErrors
+    K = 2000
+    run_case("rw_series_cont_sc_epi_heldpos_euler", "Cont-SC-SeriesDc-v0", "euler", K, 1410, "held_pos", True, "box1", record_reward=True,
+             load=dict(load_parameter=dict(j_load=0.05)))  # (a heavy load: the speed, and with it the back-EMF, stays behind the current)
+    run_case("rw_shunt_fin_cc_omega_epi_held_euler", "Finite-CC-ShuntDc-v0", "euler", K, 1411, "held", True, "disc4", record_reward=True,
+             reward_function=WeightedSumOfErrors(reward_weights=dict(i_a=0.6, omega=0.4)))
+    run_case("rw_series_cont_tc_epi_heldpos_euler", "Cont-TC-SeriesDc-v0", "euler", K, 1412, "held_pos", True, "box1", record_reward=True)
+    run_case("rw_pmsm_cont_cc_six_terms_epi_held_euler", "Cont-CC-PMSM-v0", "euler", K, 1413, "held", True, "box3", record_reward=True,
+             reward_function=WeightedSumOfErrors(reward_weights=dict(omega=0.1, torque=0.15, i_sd=0.25, i_sq=0.25, u_sq=0.1, u_sup=0.15),
+                                                 reward_power=dict(omega=1, torque=2, i_sd=1, i_sq=2, u_sq=1, u_sup=2), bias="positive"))
+    run_case("rw_extex_cont_cc_seven_terms_pow_epi_held_euler", "Cont-CC-ExtExDc-v0", "euler", K, 1414, "held", True, "box2", record_reward=True,
+             reward_function=WeightedSumOfErrors(reward_weights=dict(omega=0.1, torque=0.1, i_a=0.25, i_e=0.2, u_a=0.15, u_e=0.1, u_sup=0.1),
+                                                 reward_power=dict(omega=2, torque=0.5, i_a=1, i_e=3, u_a=2, u_e=0.5, u_sup=3), gamma=0.8))
 
 
 INIT_CASES = {

@@ -66,6 +66,11 @@ def test_default_modules_match_the_reference_env_class(env_id):
         k = want["state_names"].index(name)
         assert _close(rc.weight[i], rw["_reward_weights"][k]), name
         assert rc.power[i] == rw["_n"][k], name
+        # what each error is divided by, and the bounds it is the difference of: exact (the ids differ in which states reach below 0)
+        assert rc.state_length[i] == rw["_state_length"][k], (name, rc.state_length[i], rw["_state_length"][k])
+        assert float(ps.state_space.low[i]) == want["state_space"]["low"][k], name
+        assert float(ps.state_space.high[i]) == want["state_space"]["high"][k], name
+    assert len(ps.state_space.low) == len(ps.state_space.high) == len(ref_names)
     if "i_sum" in want["state_names"]:
         assert rw["_reward_weights"][want["state_names"].index("i_sum")] == 0.0  # (nothing of the reward is lost with that column)
     assert rc.bias == rw["_bias"]

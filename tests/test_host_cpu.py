@@ -389,6 +389,14 @@ def test_action_stage_config():
                                                 violation_reward=-7.5, normed_reward_weights=True)),
     ("rw_eesm_cont_cc_pow_mixed_epi_held_euler", dict(reward_weights=dict(i_sd=0.4, i_sq=0.4, i_e=0.2),
                                                      reward_power=dict(i_sd=1, i_sq=2, i_e=0.5), gamma=0.95)),
+    # states of length 1 (a state space that starts at 0), alone and beside states of length 2; more than four weighted states
+    ("rw_series_cont_sc_epi_heldpos_euler", dict(reward_weights=dict(omega=1.0))),
+    ("rw_series_cont_tc_epi_heldpos_euler", dict(reward_weights=dict(torque=1.0))),
+    ("rw_shunt_fin_cc_omega_epi_held_euler", dict(reward_weights=dict(i_a=0.6, omega=0.4))),
+    ("rw_pmsm_cont_cc_six_terms_epi_held_euler", dict(reward_weights=dict(omega=0.1, torque=0.15, i_sd=0.25, i_sq=0.25, u_sq=0.1, u_sup=0.15),
+                                                     reward_power=dict(omega=1, torque=2, i_sd=1, i_sq=2, u_sq=1, u_sup=2), bias="positive")),
+    ("rw_extex_cont_cc_seven_terms_pow_epi_held_euler", dict(reward_weights=dict(omega=0.1, torque=0.1, i_a=0.25, i_e=0.2, u_a=0.15, u_e=0.1, u_sup=0.1),
+                                                            reward_power=dict(omega=2, torque=0.5, i_a=1, i_e=3, u_a=2, u_e=0.5, u_sup=3), gamma=0.8)),
 ])
 def test_reward_config_derivation_matches_reference(name, kwargs):
     """set_reward() with WeightedSumOfErrors' own arguments derives the arrays the live reference's reward function held

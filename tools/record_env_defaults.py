@@ -3,7 +3,8 @@
 
 TEST INFRASTRUCTURE ONLY -- never imported by the product package.  Imports the unmodified reference the way oracle/make_golden.py
 does (oracle/gymnasium_standin and $GEM_REFERENCE/src on sys.path), calls `gem.make(env_id)` for every id and writes what its
-reference generator and reward function resolved to after `set_modules`: settings only, no trajectories.
+reference generator and reward function resolved to after `set_modules` (with the reward function's `_state_length` and the physical
+system's state-space bounds it is derived from): settings only, no trajectories.
 
     MPLBACKEND=Agg python tools/record_env_defaults.py [--out tests/golden/env_defaults.json]
 
@@ -47,7 +48,9 @@ def record(env_id, gem):
         referenced_states=[bool(x) for x in rg.referenced_states],
         generators=gens,
         reward=dict(_reward_weights=[float(x) for x in rf._reward_weights], _n=[float(x) for x in rf._n], _bias=float(rf._bias),
-                    _violation_reward=float(rf._violation_reward), _gamma=float(rf._gamma), reward_range=_pair(rf.reward_range)),
+                    _violation_reward=float(rf._violation_reward), _gamma=float(rf._gamma), reward_range=_pair(rf.reward_range),
+                    _state_length=[float(x) for x in rf._state_length]),
+        state_space=dict(low=[float(x) for x in ps.state_space.low], high=[float(x) for x in ps.state_space.high]),
         reference_space=dict(low=[float(x) for x in rg.reference_space.low], high=[float(x) for x in rg.reference_space.high]),
     )
 
