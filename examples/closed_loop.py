@@ -5,10 +5,14 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
     python examples/closed_loop.py [--envs 16384] [--steps 2000]                        # generator and reward wired by hand
     python examples/closed_loop.py --complete [--bind | --graph 64]                     # the same loop through the complete env
     python examples/closed_loop.py --complete --graph 64 --reference step               # ... on step (sinusoidal, ...) profiles
+    python examples/closed_loop.py --complete --rollout 500                             # open loop: (state, reference, reward, done) datasets
 
 Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
 step per control step.  `--complete`: `ga.make(..., reference_generator="default")` does the wiring -- two launches per control step (physics +
 reward, then the fused generator step), `--bind` with everything resolved once (`env.bind_step`), `--graph S` with S control steps per HIP graph.
+`--complete --rollout K`: no policy in the loop -- random actions generated on the device, K control steps per `rollout_complete_synthetic`
+call (physics rollout, generator rollout in the shell's order, reward pass: three launches per K steps), i.e. the dataset a closed loop
+of K `step()`s on the same actions would have produced, bit for bit.
 
 The same loop with the reference package is `env.step(policy(obs))` on ONE env per Python call (reference: core.py:329-372).
 """
@@ -36,7 +40,10 @@ def main():
                     help="--complete: the kind of the i_sd / i_sq reference generators: " + ", ".join(sorted(REFERENCES)))
     ap.add_argument("--flat", action="store_true", help="--complete: the device-side observation stage hands the policy ONE flat tensor "
                                                         "(i_sd, i_sq, cos(epsilon), sin(epsilon), reference i_sd, reference i_sq)")
+    ap.add_argument("--rollout", type=int, default=0, metavar="K", help="--complete: open-loop datasets, K control steps per rollout_complete_synthetic call")
     args = ap.parse_args()
+    if args.rollout and (not args.complete or args.bind or args.graph):
+        ap.error("--rollout needs --complete (and neither --bind nor --graph)")
     if args.reference != "wiener" and not args.complete:
         ap.error("--reference needs --complete")
     if args.flat and not args.complete:
@@ -95,6 +102,8 @@ def complete(args):
         obs_kw = dict(observed_states=["i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"], flatten_observation=True)
     env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw)
     ps = env.physical_system
+    if args.rollout:
+        return rollout_loop(args, env)
     if args.flat:
         return flat_loop(args, env)
     cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
@@ -145,6 +154,34 @@ def complete(args):
     steps = reps * (args.graph or 1)
     print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
           f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
+    assert torch.isfinite(ret).all()
+    env.close()
+
+
+def rollout_loop(args, env):
+    """Open loop: K control steps per call on the device's synthetic action stream, into fixed output tensors."""
+    import torch
+
+    n, K = args.envs, args.rollout
+    ps = env.physical_system
+    shapes = env._complete_shapes(K)
+    state, refs, reward = (torch.empty(s, device="cuda") for s in shapes[:3])
+    done = torch.empty(shapes[3], dtype=torch.uint8, device="cuda")
+    ret = torch.zeros(n, device="cuda")
+    env.reset()
+    env.rollout_complete_synthetic(K, seed=1, state_out=state, refs_out=refs, reward_out=reward, done_out=done)  # (untimed: first launches)
+    reps = max(1, args.steps // K)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        env.rollout_complete_synthetic(K, seed=1, state_out=state, refs_out=refs, reward_out=reward, done_out=done)
+        ret.add_(reward.sum(dim=0))
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = reps * K
+    print(f"complete env (rollout_complete_synthetic, K = {K}, {args.reference} references): {n} envs x {steps} steps in {dt:.3f} s = "
+          f"{n * steps / dt / 1e6:.1f} M env-steps/s ({dt / steps * 1e6:.2f} us/step); state {tuple(state.shape)}, refs {tuple(refs.shape)}; "
+          f"{int(done.sum())} terminations in the last chunk; mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
     assert torch.isfinite(ret).all()
     env.close()
 

@@ -124,6 +124,7 @@ EXPORTS = (
     "gemx_reset", "gemx_step", "gemx_rollout", "gemx_rollout_half", "gemx_get_state", "gemx_set_state", "gemx_get_switch_state",
     "gemx_set_switch_state", "gemx_aux_state_bytes", "gemx_get_aux_state", "gemx_set_aux_state", "gemx_reset_again", "gemx_rollout_synthetic", "gemx_synthetic_actions", "gemx_set_rate_limiter", "gemx_set_steps_per_block", "gemx_last_launch", "gemx_error_flags", "gemx_debug_read",
     "gemx_obsproc_create", "gemx_obsproc_apply", "gemx_obsproc_destroy",
+    "gemx_refgen_rollout_shell", "gemx_reward_rows",
 )
 
 
@@ -177,6 +178,8 @@ def load():
     L.gemx_refgen_rollout.argtypes = [vp, vp, i32, vp, vp]
     L.gemx_refgen_get_state.argtypes = [vp, vp, vp, vp, vp]
     L.gemx_refgen_step.argtypes = [vp, vp, vp, vp]
+    L.gemx_refgen_rollout_shell.argtypes = [vp, vp, i32, vp, vp]
+    L.gemx_reward_rows.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp]
     L.gemx_obsproc_create.argtypes = [C.POINTER(GemxObsprocConfig), C.c_int, C.c_int, C.POINTER(vp)]
     L.gemx_obsproc_apply.argtypes = [vp, vp, vp, i64, vp, vp]
     L.gemx_obsproc_destroy.argtypes = [vp]

@@ -160,6 +160,7 @@ using namespace gemx;
 
 void gemx_cov_note(const char *key);  // instantiation coverage (below): a process with GEMX_COVERAGE_FILE set lists every distinct kernel it launches
 #define GEMX_COV(name) gemx_cov_note(name)
+void gemx_rewardpass_note(const gemx_handle *h, const void *desc);  // gemx_rewardpass.hip: the host copy of a handle's reward description (nullptr: none)
 static thread_local char g_err[512] = "";
 namespace gemx {
 int fail(int code, const char *fmt, ...) {
@@ -798,6 +799,7 @@ int gemx_create(const gemx_config *cfg, int64_t n_envs, int device, gemx_handle 
 
 int gemx_destroy(gemx_handle *h) {
     if (!h) return GEMX_OK;
+    gemx_rewardpass_note(h, nullptr);
     gemx::DeviceGuard guard(h->device);
     if (h->state) (void)hipFree(h->state);
     if (h->angle) (void)hipFree(h->angle);
@@ -1026,7 +1028,7 @@ int gemx_rollout_half(gemx_handle *h, const void *actions_half_dev, int32_t K, v
 
 int gemx_set_reward(gemx_handle *h, const gemx_reward_config *rc) {
     if (!h) return fail(GEMX_ERR_ARG, "null handle");
-    if (!rc) { h->rw_n_ref = -1; return GEMX_OK; }
+    if (!rc) { h->rw_n_ref = -1; gemx_rewardpass_note(h, nullptr); return GEMX_OK; }
     if (rc->struct_size != (int32_t)sizeof(gemx_reward_config)) return fail(GEMX_ERR_ARG, "gemx_reward_config size mismatch");
     if (rc->n_ref < 0 || rc->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "n_ref must be in [0, %d]", GEMX_MAX_REF);
     for (int j = 0; j < rc->n_ref; ++j) {
@@ -1043,11 +1045,13 @@ int gemx_set_reward(gemx_handle *h, const gemx_reward_config *rc) {
         build_reward(h, rc, W);
         reward_hot_from(W, h->rh_d);
         HIP_TRY(hipMemcpy(h->rw_dev, &W, sizeof(W), hipMemcpyHostToDevice));
+        gemx_rewardpass_note(h, &W);
     } else {
         RewardDev<float> W;
         build_reward(h, rc, W);
         reward_hot_from(W, h->rh_f);
         HIP_TRY(hipMemcpy(h->rw_dev, &W, sizeof(W), hipMemcpyHostToDevice));
+        gemx_rewardpass_note(h, &W);
     }
     h->rw_n_ref = rc->n_ref;
     return GEMX_OK;

@@ -14,6 +14,7 @@
 // (env, generator) walks its K steps sequentially: scale by the sub-episode's sigma, accumulate, clip, restart on `done`.
 // One kernel per env-shell step (gemx_refgen_step): one lane per env resets its generators on `done`, draws the step's normal inline and
 // advances every generator by one step -- the same draws, the same double arithmetic, hence the same bits as a rollout.
+// K such steps in one call (gemx_refgen_rollout_shell): the two rollout kernels with the reset of done[k] BEFORE row k, the env shell's order.
 // The step index of the normal draws lives on the device, per (generator, env) like the other counters (every lane advances its own:
 // no lane reads a counter another lane writes), so a replayed HIP graph of steps advances the streams.
 //
@@ -114,8 +115,10 @@ __device__ inline double walk_step(const RefgenDev &G, int g, double value, doub
 
 // (2) out[k][env][g] holds z on entry and the reference of step k on exit.  done[k][env] != 0: the env terminated in step k, its
 // generators are reset before the reference of step k+1 is produced (env.reset() -> reference_generator.reset(), core.py:312-313).
+// done_first (gemx_refgen_rollout_shell, the env shell's order): the reset of done[k][env] comes BEFORE row k instead -- row k is then what
+// refgen_step_kernel produces with the mask done[k].
 template <class R>
-__global__ void refgen_walk_kernel(R *out, const uint8_t *done, const uint8_t *reset_mask, int reset_all, int64_t N, int K, RefgenDev G,
+__global__ void refgen_walk_kernel(R *out, const uint8_t *done, int done_first, const uint8_t *reset_mask, int reset_all, int64_t N, int K, RefgenDev G,
                                    double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset, uint64_t *t) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= N * G.n_ref) return;
@@ -130,11 +133,13 @@ __global__ void refgen_walk_kernel(R *out, const uint8_t *done, const uint8_t *r
     }
     for (int k = 0; k < K; ++k) {
         const int64_t o = ((int64_t)k * N + env) * G.n_ref + g;
+        const bool dn = done != nullptr && done[(int64_t)k * N + env];
+        if (dn && done_first) reset_generator(G, env, g, nr, ns, lf, sg, v);
         if (lf <= 0) new_subepisode(G, env, g, ns, lf, sg);
         v = walk_step(G, g, v, sg, (double)out[o]);
         --lf;
         out[o] = (R)v;
-        if (done != nullptr && done[(int64_t)k * N + env]) reset_generator(G, env, g, nr, ns, lf, sg, v);
+        if (dn && !done_first) reset_generator(G, env, g, nr, ns, lf, sg, v);
     }
     value[si] = v; sigma[si] = sg; left[si] = lf; n_sub[si] = ns; n_reset[si] = nr;
     if (K > 0) t[si] += (uint64_t)K;
@@ -188,10 +193,10 @@ RefgenDev make_dev(const gemx_refgen_config &c) {
     return G;
 }
 
-template <class R> int walk(gemx_refgen *r, void *out, const uint8_t *done, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+template <class R> int walk(gemx_refgen *r, void *out, const uint8_t *done, int done_first, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
     const int64_t lanes = r->n * r->cfg.n_ref;
     gemx_cov_note(sizeof(R) == 4 ? "refgen_walk_kernel<float>" : "refgen_walk_kernel<double>");
-    hipLaunchKernelGGL(refgen_walk_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done, mask, reset_all, r->n, K, make_dev(r->cfg),
+    hipLaunchKernelGGL(refgen_walk_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done, done_first, mask, reset_all, r->n, K, make_dev(r->cfg),
                        r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t);
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
@@ -328,8 +333,9 @@ template <class R> __device__ inline double kinds_advance(const RefgenKindsDev &
     return v;
 }
 
-// reset (K = 0: the envs of reset_mask, or all), rollout (K steps, reset AFTER step k where done_post[k][env]) and step (K = 1, reset
-// BEFORE the step where done_pre[env]): out[k][env][g], adjacent lanes write adjacent columns.
+// reset (K = 0: the envs of reset_mask, or all), rollout (K steps, reset AFTER step k where done_post[k][env]), step (K = 1, reset
+// BEFORE the step where done_pre[env]) and shell-order rollout (K steps, reset BEFORE step k where done_pre[k][env]): out[k][env][g],
+// adjacent lanes write adjacent columns.
 template <class R>
 __global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
                                     int K, RefgenKindsDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
@@ -357,10 +363,9 @@ __global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8
     const uint32_t ns0 = s.ns, nr0 = s.nr;
     if (K == 0) {
         if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, s);
-    } else if (done_pre != nullptr && done_pre[env]) {
-        kinds_reset(G, env, g, s);
     }
     for (int k = 0; k < K; ++k) {
+        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) kinds_reset(G, env, g, s);
         out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, s);
         if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, s);
     }
@@ -531,15 +536,11 @@ int gemx_refgen_reset(gemx_refgen *r, const uint8_t *mask_dev, void *stream) {
     hipStream_t st = (hipStream_t)stream;
     const int all = mask_dev == nullptr;
     if (r->mixed) return kinds(r, nullptr, nullptr, nullptr, mask_dev, all, 0, st);
-    return r->f64 ? walk<double>(r, nullptr, nullptr, mask_dev, all, 0, st) : walk<float>(r, nullptr, nullptr, mask_dev, all, 0, st);
+    return r->f64 ? walk<double>(r, nullptr, nullptr, 0, mask_dev, all, 0, st) : walk<float>(r, nullptr, nullptr, 0, mask_dev, all, 0, st);
 }
 
-int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream) {
-    if (!r || !refs_out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
-    if (K < 1) return gemx::fail(GEMX_ERR_ARG, "K must be >= 1");
-    gemx::DeviceGuard guard(r->device);
-    hipStream_t st = (hipStream_t)stream;
-    if (r->mixed) return kinds(r, refs_out_dev, nullptr, done_dev, nullptr, 0, K, st);
+// the all-Wiener pair: K * N * n_ref normals into the output tensor, then the sequential walk over them (which advances the step counters by K)
+static int refgen_wiener_rollout(gemx_refgen *r, const uint8_t *done_dev, int done_first, int32_t K, void *refs_out_dev, hipStream_t st) {
     const int64_t total = (int64_t)K * r->n * r->cfg.n_ref;
     gemx_cov_note(r->f64 ? "refgen_normals_kernel<double>" : "refgen_normals_kernel<float>");
     if (r->f64)
@@ -549,8 +550,26 @@ int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void
         hipLaunchKernelGGL(refgen_normals_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)refs_out_dev, r->n, r->cfg.n_ref, K,
                            r->cfg.seed, r->t, r->cfg.env_base);
     GEMX_HIP_TRY(hipGetLastError());
-    // (the walk kernel advances the step counters by K)
-    return r->f64 ? walk<double>(r, refs_out_dev, done_dev, nullptr, 0, K, st) : walk<float>(r, refs_out_dev, done_dev, nullptr, 0, K, st);
+    return r->f64 ? walk<double>(r, refs_out_dev, done_dev, done_first, nullptr, 0, K, st) : walk<float>(r, refs_out_dev, done_dev, done_first, nullptr, 0, K, st);
+}
+
+int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream) {
+    if (!r || !refs_out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    if (K < 1) return gemx::fail(GEMX_ERR_ARG, "K must be >= 1");
+    gemx::DeviceGuard guard(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (r->mixed) return kinds(r, refs_out_dev, nullptr, done_dev, nullptr, 0, K, st);
+    return refgen_wiener_rollout(r, done_dev, 0, K, refs_out_dev, st);
+}
+
+// K env-shell steps in the SHELL's order: row k = gemx_refgen_step(done[k]) -- restart where done[k][env], then advance (include/gemx.h)
+int gemx_refgen_rollout_shell(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream) {
+    if (!r || !refs_out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    if (K < 1) return gemx::fail(GEMX_ERR_ARG, "K must be >= 1");
+    gemx::DeviceGuard guard(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    if (r->mixed) return kinds(r, refs_out_dev, done_dev, nullptr, nullptr, 0, K, st);
+    return refgen_wiener_rollout(r, done_dev, 1, K, refs_out_dev, st);
 }
 
 // One env-shell step in ONE launch: the generators of envs with done_dev[env] != 0 (NULL: none) are reset, then every generator advances

@@ -25,6 +25,9 @@ WeightedSumOfErrors reward, and the reference's shell semantics (core.py:300-371
              launch 2  generators of terminated envs restart, every generator advances, `ref` rewritten  (core.py:351)
 
 Two kernel launches per step, no host round trip; `bind_step` resolves everything once and can be captured in a HIP graph.
+K steps in one call: `state, refs, reward, done = env.rollout_complete(actions [K, N, A])` -- what K calls of `step` return, stacked, bit for
+bit, in three launches (physics rollout; generators in the shell's order on its done mask; reward pass over the stored rows); also
+`rollout_complete_synthetic(K)` and the pre-bound, graph-capturable `bind_rollout_complete(...)`.
 The reference's other generator kinds (sinusoidal, step, triangular, sawtooth, Laplace process, constant) run on the same path: pass a
 holder named after the reference's class, a list of them or a `BatchedMultipleReferenceGenerator` as `reference_generator=`.
 
@@ -475,6 +478,144 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             return obs
 
         return step, obs, self._reward[0], ps._done
+
+    # ------------------------------------------------------------------ complete K-step rollouts: physics -> references -> reward
+    def _complete_shapes(self, K):
+        """(state, refs, reward, done) shapes of a complete K-step rollout."""
+        ps = self.physical_system
+        stage = self.observation_stage
+        n_state = len(ps.state_names) if stage is None else stage.n_out
+        return (K, ps.n_envs, n_state), (K, ps.n_envs, len(self.reference_names)), (K, ps.n_envs), (K, ps.n_envs)
+
+    def _check_complete(self, what, K, actions=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
+        """bind_rollout-style validation (K, then per tensor: dtype, shape, contiguity, device) -> K.  Needs no device: it runs
+        before anything is launched, and on an env whose handles were never created."""
+        torch = bps._torch()
+        ps = self.physical_system
+        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
+        tdev = getattr(ps, "_tdev", None) or torch.device("cuda", ps._device)
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"{what}: K must be >= 1, not {K}")
+
+        def check(t, name, dtype, shape=None, numel=None):
+            if not torch.is_tensor(t):
+                raise ValueError(f"{what}: {name} must be a tensor")
+            if t.dtype != dtype:
+                raise ValueError(f"{what}: {name} must have dtype {dtype}, not {t.dtype}")
+            if (shape is not None and tuple(t.shape) != shape) or (numel is not None and t.numel() != numel):
+                raise ValueError(f"{what}: {name} must have shape {shape if shape is not None else f'of {numel} elements'}, not {tuple(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{what}: {name} must be contiguous")
+            if t.device != tdev:
+                raise ValueError(f"{what}: {name} must be on device {tdev}, not {t.device}")
+
+        if actions is not None:
+            space = ps.action_space
+            discrete = hasattr(space, "n") or hasattr(space, "nvec")
+            check(actions, "actions", torch.uint8 if discrete else tdtype, numel=K * ps.n_envs * (1 if discrete else int(space.shape[0])))
+        shapes = self._complete_shapes(K)
+        for t, name, dtype, shape in ((state_out, "state_out", tdtype, shapes[0]), (refs_out, "refs_out", tdtype, shapes[1]),
+                                      (reward_out, "reward_out", tdtype, shapes[2]), (done_out, "done_out", torch.uint8, shapes[3])):
+            if t is not None:
+                check(t, name, dtype, shape)
+        return K
+
+    def _reward_rows_args(self, raw, refs, done, reward, K, stream):
+        import ctypes as C
+
+        n_ref = int(self.reward_config.n_ref)
+        return (C.c_void_p(raw.data_ptr()), C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(refs.data_ptr()) if n_ref else None,
+                C.c_void_p(done.data_ptr()), K, C.c_void_p(reward.data_ptr()), C.c_void_p(stream.cuda_stream))
+
+    def _rollout_complete(self, what, K, physics, state_out, refs_out, reward_out, done_out):
+        torch = bps._torch()
+        ps, gen, stage = self.physical_system, self.reference_generator, self.observation_stage
+        s_shape, r_shape, w_shape, d_shape = self._complete_shapes(K)
+        if state_out is None:
+            state_out = torch.empty(s_shape, dtype=ps._tdtype, device=ps._tdev)
+        if reward_out is None:
+            reward_out = torch.empty(w_shape, dtype=ps._tdtype, device=ps._tdev)
+        if done_out is None:
+            done_out = torch.empty(d_shape, dtype=torch.uint8, device=ps._tdev)
+        raw = state_out if stage is None else self._scratch(K)
+        physics(raw, done_out)                                   # 1. physics: state rows and done bytes
+        refs = gen.rollout_shell(K, done_out, out=refs_out)      # 2. generators in the shell's order: restart on done[k], advance
+        stream = torch.cuda.current_stream(ps._tdev)             # 3. reward of row k against the references shown before step k
+        bps._lib.check(ps._L.gemx_reward_rows(ps._handle, *self._reward_rows_args(raw, refs, done_out, reward_out, K, stream)))
+        if stage is not None:
+            stage.apply(raw, refs, out=state_out)
+        self._refs.copy_(refs[K - 1])  # (after the reward pass has read the old ones: step() and further rollouts continue from row K-1)
+        return state_out, refs, reward_out, done_out
+
+    def rollout_complete(self, actions, state_out=None, refs_out=None, reward_out=None, done_out=None):
+        """K complete control steps in THREE launches (four with an observation stage) instead of K x (two or three):
+        -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], done [K, N]) -- exactly what K calls of `step(actions[k])` return,
+        stacked, bit for bit.  The physics rollout writes the states and the done mask; the generators replay the shell's order on that
+        mask (`rollout_shell`); the reward pass (`gemx_reward_rows`) rewards row k against the references shown before step k.  With an
+        observation stage `state` is the processed trajectory; with `flatten_observation=True` it is the flat `[K, N, n_post + n_ref]`
+        tensor, and `refs` is still returned.  Afterwards `reference_generator.references` holds row K-1: `step()` and further rollouts
+        continue the same sequence.  (`physical_system.done` / `.reward` and the internal state buffer keep what the last `step()` wrote,
+        as after `rollout()`.)  actions: [K, N, A] / [K, N], as `rollout` takes them."""
+        if not hasattr(actions, "shape") or len(actions.shape) < 1:
+            raise ValueError("rollout_complete needs actions [K, N, A] / [K, N]")
+        K = self._check_complete("rollout_complete", actions.shape[0], None, state_out, refs_out, reward_out, done_out)
+        ps = self.physical_system
+        a = ps._actions_to_device(actions, (K, ps._n_envs))
+        return self._rollout_complete("rollout_complete", K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), state_out, refs_out, reward_out, done_out)
+
+    def rollout_complete_synthetic(self, K, seed=0, step0=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
+        """`rollout_complete` on the device-side action source (`physical_system.rollout_synthetic(K, seed, step0)`): no action tensor is
+        read.  Equal, bit for bit, to `rollout_complete(physical_system.synthetic_actions(K, seed, step0))`."""
+        K = self._check_complete("rollout_complete_synthetic", K, None, state_out, refs_out, reward_out, done_out)
+        ps = self.physical_system
+        return self._rollout_complete("rollout_complete_synthetic", K, lambda raw, done: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done),
+                                      state_out, refs_out, reward_out, done_out)
+
+    def bind_rollout_complete(self, actions, state_out, refs_out, reward_out, done_out, stream=None):
+        """-> zero-argument launch() of `rollout_complete` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
+        done_out)`.  Everything -- handles, pointers, the stream -- is resolved here, once: a call allocates nothing and never
+        synchronises, and every launch goes to ONE stream, so it can be captured with `torch.cuda.graph` (a linear graph) and replayed;
+        replays advance the physics and the generators.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
+        if not hasattr(actions, "shape") or len(actions.shape) < 1:
+            raise ValueError("bind_rollout_complete needs a device tensor of actions [K, N, A] / [K, N]")
+        for t, name in ((state_out, "state_out"), (refs_out, "refs_out"), (reward_out, "reward_out"), (done_out, "done_out")):
+            if t is None:
+                raise ValueError(f"bind_rollout_complete: {name} must be given (a bound launch allocates nothing)")
+        K = self._check_complete("bind_rollout_complete", actions.shape[0], actions, state_out, refs_out, reward_out, done_out)
+        if isinstance(self.reference_generator, ReplayReferenceGenerator):
+            self.reference_generator.bind_rollout_shell(done_out, refs_out)  # (raises: cannot be captured)
+        torch = bps._torch()
+        ps, gen, stage = self.physical_system, self.reference_generator, self.observation_stage
+        L, check = ps._L, bps._lib.check
+        stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
+        raw = state_out if stage is None else self._scratch(K)
+        physics = ps.bind_rollout(actions, raw, done_out, stream=stream)
+        generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
+        args = self._reward_rows_args(raw, refs_out, done_out, reward_out, K, stream)
+        call = L.gemx_reward_rows
+        post = stage.bind_apply(raw, refs_out, state_out, stream) if stage is not None else None
+        shown, last = self._refs, refs_out[K - 1]
+        current, on = torch.cuda.current_stream, torch.cuda.stream
+        out = (state_out, refs_out, reward_out, done_out)
+        keep = (actions, raw, stream)
+
+        def launch(_args=args, _call=call, _keep=keep):
+            physics()
+            generators()
+            rc = _call(ps._handle, *_args)
+            if rc:
+                check(rc)
+            if post is not None:
+                post()
+            if current(ps._tdev) == stream:  # the references shown last: one device-to-device copy on the launch stream
+                shown.copy_(last)
+            else:
+                with on(stream):
+                    shown.copy_(last)
+            return out
+
+        return launch
 
     def close(self):
         self.reference_generator.close()

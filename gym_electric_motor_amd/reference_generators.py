@@ -14,6 +14,8 @@ derives the margins the way the reference's `set_modules` does and owns the tens
 Closed loop, one launch per control step (what `ga.make(env_id, reference_generator="default")` drives): `gen.reset(); ref = gen.step()`,
 then per control step `ref = gen.step(done)` -- terminated envs restart their generators, every generator advances, `ref [N, n_ref]` is
 rewritten in place.  K x `step(done[k-1])` equals `rollout(K, done)` bit for bit, and the two can be mixed.
+`rollout_shell(K, done)` is K such steps in one call -- row k is `step(done[k])`: restart first, then advance (what the complete env's
+`rollout_complete` runs on the physics rollout's done mask); `rollout` resets AFTER row k.
 
 The reference's other generator kinds -- sinusoidal, step, triangular, sawtooth, Laplace process, constant -- are parameter holders named
 after the reference's classes, mixed per state by `BatchedMultipleReferenceGenerator` (MultipleReferenceGenerator's counterpart), on the
@@ -95,6 +97,56 @@ class _DeviceGenerators:
         _lib.check(self._L.gemx_refgen_rollout(self._handle, C.c_void_p(d.data_ptr()) if d is not None else None, int(K),
                                                C.c_void_p(out.data_ptr()), self._stream()))
         return out
+
+    def _check_shell(self, K, done, out, what):
+        """Validation of rollout_shell / bind_rollout_shell, without a device: K >= 1, done [K, N] uint8, out [K, N, n_ref]."""
+        import torch
+
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"{what}: K must be >= 1, not {K}")
+        if done is not None and not (torch.is_tensor(done) and done.dtype == torch.uint8 and tuple(done.shape) == (K, self._n_envs) and done.is_contiguous()
+                                     and done.device == getattr(self, "_tdev", done.device)):
+            raise ValueError(f"{what}: done must be a contiguous uint8 tensor of shape {(K, self._n_envs)} on the generator's device")
+        oshape = (K, self._n_envs, int(self._cfg.n_ref))
+        if out is not None and not (torch.is_tensor(out) and tuple(out.shape) == oshape and out.is_contiguous() and out.dtype == getattr(self, "_tdtype", out.dtype)
+                                    and out.device == getattr(self, "_tdev", out.device)):
+            raise ValueError(f"{what}: out must be a contiguous tensor of shape {oshape} of the generator's dtype on its device")
+        return K
+
+    def rollout_shell(self, K, done=None, out=None):
+        """K env-shell steps in the SHELL's order (gemx_refgen_rollout_shell): row k of the returned [K, N, n_ref] tensor is what
+        `step(done[k])` returns -- the generators of the envs with done[k, env] != 0 restart first, then every generator advances.  (`rollout`
+        resets AFTER row k.)  done: [K, N] uint8 device tensor, e.g. a physics rollout's done mask, or None.  `references` is not
+        touched; may be mixed freely with `step` and `rollout`."""
+        import torch
+
+        K = self._check_shell(K, done, out, "rollout_shell")
+        if out is None:
+            out = torch.empty((K, self._n_envs, int(self._cfg.n_ref)), dtype=self._tdtype, device=self._tdev)
+        _lib.check(self._L.gemx_refgen_rollout_shell(self._handle, C.c_void_p(done.data_ptr()) if done is not None else None, K,
+                                                     C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def bind_rollout_shell(self, done, out, stream=None):
+        """-> zero-argument launch(): `gemx_refgen_rollout_shell(done) -> out` with the handle, both pointers and the stream resolved once."""
+        import torch
+
+        if done is None or out is None:
+            raise ValueError("bind_rollout_shell needs the done [K, N] and out [K, N, n_ref] tensors")
+        K = self._check_shell(done.shape[0] if torch.is_tensor(done) and done.dim() == 2 else 0, done, out, "bind_rollout_shell")
+        stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
+        call, check = self._L.gemx_refgen_rollout_shell, _lib.check
+        args = (C.c_void_p(done.data_ptr()), K, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        keep = (done, out, stream)
+
+        def launch(_args=args, _call=call, _keep=keep):
+            rc = _call(self._handle, *_args)
+            if rc:
+                check(rc)
+            return out
+
+        return launch
 
     def step(self, done=None, out=None):
         """One env-shell step in ONE launch (gemx_refgen_step): the generators of the envs with done[env] != 0 restart, then every
@@ -511,6 +563,33 @@ class ReplayReferenceGenerator:
 
     def bind_step(self, done, stream=None):
         return self._show
+
+    def rollout_shell(self, K, done=None, out=None):
+        """The next K rows of the profile, [K, N, n_ref] (`done` is ignored); the host row index advances by K.  Eager only."""
+        import torch
+
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"rollout_shell: K must be >= 1, not {K}")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a ReplayReferenceGenerator cannot be captured in a graph: its row index lives on the host")
+        if self._k + K > self._rows.shape[0]:
+            raise IndexError(f"the replayed profile has {self._rows.shape[0]} rows")
+        rows = self._rows[self._k:self._k + K]
+        if rows.dim() == 2:  # ([K, n_ref] profiles: every env sees the same row)
+            rows = rows[:, None, :].expand(K, self._n_envs, rows.shape[-1])
+        if out is None:
+            out = rows.contiguous()
+        else:
+            if tuple(out.shape) != (K, self._n_envs, int(self._rows.shape[-1])):
+                raise ValueError(f"rollout_shell: out must have shape {(K, self._n_envs, int(self._rows.shape[-1]))}")
+            out.copy_(rows)
+        self._k += K
+        return out
+
+    def bind_rollout_shell(self, done, out, stream=None):
+        raise RuntimeError("a ReplayReferenceGenerator cannot be captured in a graph: its row index lives on the host, so a bound rollout "
+                           "would replay the rows of its first launch")
 
     def close(self):
         pass

@@ -334,6 +334,27 @@ int gemx_refgen_reset(gemx_refgen *r, const uint8_t *mask_dev, void *stream);
 int gemx_refgen_rollout(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
 int gemx_refgen_step(gemx_refgen *r, const uint8_t *done_dev, void *refs_dev, void *stream);
 int gemx_refgen_get_state(gemx_refgen *r, double *value_out_dev, double *sigma_out_dev, int32_t *left_out_dev, void *stream);
+/* K env-shell steps of the generators in the SHELL's order (new entry point, ABI number unchanged): row k of refs_out_dev [K, N, n_ref] (R)
+ * comes out as gemx_refgen_step(done[k]) would produce it -- the generators of envs with done_dev[k][env] != 0 restart FIRST, then every
+ * generator advances once.  One call == K x gemx_refgen_step(done[k]), row for row and bit for bit.  (gemx_refgen_rollout resets AFTER
+ * row k: its row k is what the reward of step k is computed against; here row k is what the env shell shows after step k.)  done_dev
+ * [K, N] uint8 may be NULL (no restarts).  Serves both kernel families, may be mixed freely with step / rollout / reset on one handle,
+ * keeps nothing on the host, allocates nothing and can be captured in a HIP graph. */
+int gemx_refgen_rollout_shell(gemx_refgen *r, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
+
+/* REWARD PASS over a stored trajectory (new entry point, ABI number unchanged): the reward installed with gemx_set_reward, evaluated for
+ * the K * N rows of obs_dev [K, N, S_out] (R, AoS: what gemx_rollout wrote) with the arithmetic of the fused reward of
+ * gemx_rollout_reward -- same term order, same select for powers 1 and 2, pow() for every other power, bias - sum, violation_reward where
+ * done_dev[k][env] != 0 -- so reward_out_dev [K, N] (R) holds, bit for bit, what gemx_rollout_reward writes for the same rows and
+ * references.  Row k is rewarded against the reference the agent saw BEFORE step k: refs_first_dev [N, n_ref] for k = 0,
+ * refs_rows_dev[k - 1] after that (refs_rows_dev [K, N, n_ref] is the output of gemx_refgen_rollout_shell: its last row is not read).
+ * Both may be NULL when the reward has n_ref = 0; refs_rows_dev may be NULL when K = 1.  The tensors need the alignment of R only.  One
+ * kernel launch: no host state, no allocation, no synchronisation, capturable.  GEMX_ERR_ARG without an installed reward, for an SoA
+ * handle, K < 1 or a null / misaligned tensor.
+ * With gemx_rollout (physics -> obs, done) and gemx_refgen_rollout_shell (done -> references) this makes a complete K-step rollout of
+ * three launches on one stream: the physics never reads the references, so nothing has to run twice. */
+int gemx_reward_rows(gemx_handle *h, const void *obs_dev, const void *refs_first_dev, const void *refs_rows_dev, const uint8_t *done_dev,
+                     int32_t K, void *reward_out_dev, void *stream);
 
 /* The reference's other generator kinds behind the same handle (ABI 9): every column of a gemx_refgen_create_kinds handle has a kind of
  * its own, freely mixed as MultipleReferenceGenerator mixes its sub-generators (files under reference_generators/):

@@ -1,0 +1,113 @@
+#!/usr/bin/env python3
+"""Timing of the complete env's fused K-step rollout on one GPU -> the table of profiles/complete_rollout.md.
+
+Cont-CC-PMSM-v0 complete env (default Wiener generators, default reward) at --envs envs, K = --steps control steps per launch:
+
+  1. `bind_rollout_complete`: physics rollout + generator rollout in the shell's order + reward pass, three launches per K steps;
+  2. the physics-only `bind_rollout` of the same env: what the references and the reward cost on top;
+  3. K bound `step()`s (two launches each), 64 steps per HIP graph, replayed: the closed-loop path the rollout replaces;
+  4. the reward pass (gemx_reward_rows) alone over the stored trajectory, in algorithmic bytes per row
+     4 (S_out + n_ref + 1) + 1, beside the chip's measured float4-copy rate.
+
+Device time between two events on the launching stream, median over --windows windows (an untimed window first).
+
+    python tools/time_complete_rollout.py [--envs 16384] [--steps 1000] [--windows 9]
+"""
+import argparse
+import ctypes as C
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+COPY_TBPS = 6.29  # the chip's measured float4-copy rate (profiles/obs_stage.md quotes the same figure)
+
+
+def timed(fn, windows, stream=None):
+    import torch
+
+    ms = []
+    for w in range(windows + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        fn()
+        b.record(stream)
+        b.synchronize()
+        if w:
+            ms.append(a.elapsed_time(b))
+    return statistics.median(ms)
+
+
+def main():
+    import torch
+
+    import gym_electric_motor_amd as ga
+    from gym_electric_motor_amd import _lib
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--steps", type=int, default=1000)
+    ap.add_argument("--windows", type=int, default=9)
+    args = ap.parse_args()
+    n, K = args.envs, args.steps
+
+    def make():
+        env = ga.make("Cont-CC-PMSM-v0", n_envs=n, reference_generator="default", seed=1)
+        env.reset()
+        return env
+
+    acts = torch.rand((K, n, 3), device="cuda") * 0.02 - 0.01
+    # 1. the complete rollout
+    env = make()
+    ps = env.physical_system
+    shapes = env._complete_shapes(K)
+    state, refs, reward = (torch.empty(s, device="cuda") for s in shapes[:3])
+    done = torch.empty(shapes[3], dtype=torch.uint8, device="cuda")
+    launch = env.bind_rollout_complete(acts, state, refs, reward, done)
+    us_complete = timed(launch, args.windows) * 1e3 / K
+    # 4. the reward pass alone, on the trajectory just stored
+    n_ref, s_out = shapes[1][2], shapes[0][2]
+    first = env.reference_generator.references.clone()
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    call = lambda: _lib.check(ps._L.gemx_reward_rows(ps._handle, C.c_void_p(state.data_ptr()), C.c_void_p(first.data_ptr()), C.c_void_p(refs.data_ptr()),  # noqa: E731
+                                                        C.c_void_p(done.data_ptr()), K, C.c_void_p(reward.data_ptr()), st))
+    ms_pass = timed(call, args.windows)
+    gb = (4 * (s_out + n_ref + 1) + 1) * K * n / 1e9
+    env.close()
+    # 2. physics only
+    env = make()
+    launch = env.physical_system.bind_rollout(acts, state, done)
+    us_physics = timed(launch, args.windows) * 1e3 / K
+    env.close()
+    # 3. bound steps from a HIP graph
+    env = make()
+    action = torch.full((n, 3), 0.01, device="cuda")
+    stream = torch.cuda.Stream()
+    step = env.bind_step(action, stream=stream)[0]
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):
+        for _ in range(3):
+            step()
+    torch.cuda.current_stream().wait_stream(stream)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        for _ in range(64):
+            step()
+    reps = max(1, K // 64)
+    with torch.cuda.stream(stream):
+        us_steps = timed(lambda: [graph.replay() for _ in range(reps)], args.windows, stream) * 1e3 / (reps * 64)
+    env.close()
+    print(f"Cont-CC-PMSM-v0, {n} envs, K = {K}, median of {args.windows} windows")
+    print("| path | us per control step |")
+    print("|---|---|")
+    print(f"| (1) bind_rollout_complete: physics + generators + reward pass | {us_complete:.3f} |")
+    print(f"| (2) bind_rollout: physics only | {us_physics:.3f} |")
+    print(f"| (3) bound step() x K, 64 steps per HIP graph | {us_steps:.3f} |")
+    print(f"(1) against (3): {us_steps / us_complete:.2f} x faster; (1) against (2): {us_complete / us_physics:.2f} x the physics alone")
+    rate = gb / (ms_pass * 1e-3)
+    print(f"reward pass alone over [{K}, {n}, {s_out}]: {ms_pass:.3f} ms, {rate:.0f} GB/s algorithmic = {rate / (COPY_TBPS * 1e3):.2f} of the {COPY_TBPS} TB/s copy rate")
+
+
+if __name__ == "__main__":
+    main()
