@@ -241,6 +241,11 @@ template <class R> static void fill_params(const gemx_handle &h, const double *m
     for (int i = 0; i < GEMX_MAX_OUT; ++i) {
         P.inv_lim[i] = (R)(i < h.nout ? 1.0 / c.limits[i] : 0.0);
     }
+    // The u_sup column (the last one) of an ideal supply is u_sup * inv_lim, the constant 1 of the reference (limit == u_nominal).  The
+    // rounded reciprocal can put the product one ulp ABOVE 1 ((R)u_nominal may lie above u_nominal): an env that observes the column --
+    // "all_states" -- would then terminate at once.  Step the reciprocal down until it does not (no integer voltage needs it).
+    if (h.nout > 0 && c.limits[h.nout - 1] == c.u_nominal)
+        while (P.u_sup * P.inv_lim[h.nout - 1] > R(1)) P.inv_lim[h.nout - 1] = std::nextafter(P.inv_lim[h.nout - 1], R(0));
     P.cw = (const R *)h.cw_dev;
     for (int i = 0; i < h.nd; ++i) P.init[i] = (R)c.init_state[i];
     P.init_angle_rep = Angle<R>::to_bits(Angle<R>::from_rad(h.has_angle ? c.init_state[h.nd] : 0.0));

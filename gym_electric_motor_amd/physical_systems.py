@@ -229,11 +229,17 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         """Map the env's `constraints` argument (core.py:256-262) onto bit masks over the system state."""
         pos = {n: i for i, n in enumerate(self._build_state_names())}
         limit_mask = squared_mask = 0
+
+        def bit(n):
+            if n not in pos:  # (also the columns a wrapper appends behind the system's own, 'i_sum', 'cos(epsilon)': not evaluated in-kernel)
+                raise ValueError(f"constraint on {n!r}: not a state of this system {tuple(pos)}")
+            return 1 << pos[n]
+
         for c in constraints:
             if isinstance(c, str):
                 names = list(pos) if c == "all_states" else [c]
                 for n in names:
-                    limit_mask |= 1 << pos[n]
+                    limit_mask |= bit(n)
             elif _is_a(c, "LimitConstraint"):
                 names = getattr(c, "observed_state_names", None)
                 if names is None:
@@ -243,13 +249,13 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
                 if "all_states" in names:
                     names = list(pos)
                 for n in names:
-                    limit_mask |= 1 << pos[n]
+                    limit_mask |= bit(n)
             elif _is_a(c, "SquaredConstraint"):
                 if squared_mask:
                     raise ValueError("only one SquaredConstraint is supported in-kernel")
                 names = getattr(c, "states", None) or getattr(c, "_states", ())
                 for n in names:
-                    squared_mask |= 1 << pos[n]
+                    squared_mask |= bit(n)
             else:
                 raise ValueError(f"constraint {c!r} cannot be evaluated in-kernel (supported: state names, "
                                  "LimitConstraint, SquaredConstraint)")

@@ -187,11 +187,15 @@ def torque_kat(env, n=8, seed=0):
 
 
 def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1, action_frame="abc", dead_time_steps=0,
-             record_reward=False, dead_time_reset_action=None, record_overrides=False, **make_kwargs):
+             record_reward=False, dead_time_reset_action=None, record_overrides=False, constraints_spec=None, out_dir=None,
+             **make_kwargs):
     """action_frame: 'abc' | 'dq' (system.control_space = 'dq') | 'dq_processor' (DqToAbcActionProcessor wrapper);
     dead_time_steps > 0: DeadTimeProcessor(steps) wrapped INSIDE the dq processor, as the reference's processors expect.
     record_overrides: store the make-kwargs `motor`, `supply`, `load` (dicts) and `tau` exactly as passed in meta["overrides"], and the
-    motor's torque known-answer table in meta["torque_kat"] (the `params` group)."""
+    motor's torque known-answer table in meta["torque_kat"] (the `params` group).
+    constraints_spec: a custom constraint set as data, [{"kind": "limit" | "squared" | "name", "states": [...]}, ...] -- built here from the
+    reference's own LimitConstraint / SquaredConstraint classes ("name": bare state names, or "all_states", handed to make() as strings) and
+    stored as it stands in meta["constraints"] (the `constraints` group).  out_dir: where the fixture goes (default tests/golden)."""
     from gym_electric_motor.physical_system_wrappers import DeadTimeProcessor, DqToAbcActionProcessor
 
     kw = dict(make_kwargs)
@@ -210,6 +214,9 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
     kw["ode_solver"] = make_solver(solver)
     if not episodic:
         kw["constraints"] = ()
+    if constraints_spec is not None:
+        assert episodic
+        kw["constraints"] = reference_constraints(constraints_spec)
     recorder = _StepRecorder()
     if record_reward:
         kw["callbacks"] = (recorder,)
@@ -239,7 +246,8 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
             env.reset()
     meta = describe(env)
     meta.update(name=name, env_id=env_id, solver=solver, K=K, seed=seed, mode=mode, episodic=bool(episodic),
-                every=every, constraints=("default" if episodic else "none"), action_frame=action_frame,
+                every=every, constraints=(constraints_spec if constraints_spec is not None else "default" if episodic else "none"),
+                action_frame=action_frame,
                 dead_time_steps=int(dead_time_steps))
     if dead_time_reset_action is not None:
         meta["dead_time_reset_action"] = [float(x) for x in dead_time_reset_action]
@@ -264,7 +272,7 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
         extra = dict(references=np.asarray(recorder.references)[:, :n_keep], rewards=np.asarray(recorder.rewards))
         assert len(recorder.rewards) == K
     np.savez_compressed(
-        os.path.join(OUT, name + ".npz"),
+        os.path.join(out_dir or OUT, name + ".npz"),
         **extra,
         actions=actions.astype(np.uint8) if "disc" in space_kind else actions,
         states=states[keep],
@@ -274,6 +282,23 @@ def run_case(name, env_id, solver, K, seed, mode, episodic, space_kind, every=1,
         meta=np.array(json.dumps(meta)),
     )
     print(f"{name:48s} K={K} terminated={int(term.sum()):5d} max|x|={np.abs(states).max():.3f}")
+    return states, term
+
+
+def reference_constraints(spec):
+    """A constraint set stored as data -> what make(constraints=...) takes: the reference's own constraint objects and bare names."""
+    from gym_electric_motor.constraints import LimitConstraint, SquaredConstraint
+
+    return _constraint_cases().build_constraints(spec, LimitConstraint, SquaredConstraint)
+
+
+def _constraint_cases():
+    """tests/constraint_cases.py: the one place where a stored set is spelled (L / S / NAMES) and turned into constraint objects."""
+    if os.path.join(REPO, "tests") not in sys.path:
+        sys.path.insert(0, os.path.join(REPO, "tests"))
+    import constraint_cases
+
+    return constraint_cases
 
 
 def replay_ref_data():
@@ -439,6 +464,8 @@ def main(only=None):
         main_defaults()
     if not only or "params" in only:
         main_params()
+    if not only or "constraints" in only:
+        main_constraints()
 
 
 ALL_ENV_IDS = [f"{a}-{c}-{m}-v0" for m in ("PermExDc", "SeriesDc", "ShuntDc", "ExtExDc", "PMSM", "SynRM", "SCIM", "EESM", "DFIM")
@@ -870,6 +897,35 @@ def main_params():
         "scim_cc_negspeed_uniform": ("Cont-CC-SCIM-v0", uni, None, dict(omega_fixed=-100.0), dict(motor_parameter=dict(S["scim"]))),
         "dfim_cc_negspeed_uniform": ("Cont-CC-DFIM-v0", uni, None, dict(omega_fixed=-60.0), dict(motor_parameter=dict(S["dfim"]))),
     }, fname="init_samples_params.npz", n_obs=32)
+
+
+# Custom constraint sets (the `constraints` group): (name, env id, seed, action space, set, make-kwargs).  Short episodic Euler runs,
+# every step recorded, reset on termination; the seeds were picked so that each run terminates at least three times and holds at
+# least one episode of more than 50 steps (asserted when recording).
+_L, _S, _N = _constraint_cases().L, _constraint_cases().S, _constraint_cases().NAMES
+CONSTRAINT_CASES = [
+    ("cs_permexdc_cont_sc_sq_i_omega_euler", "Cont-SC-PermExDc-v0", 1800, "box1", [_S("i", "omega")], {}),
+    ("cs_permexdc_cont_cc_all_states_euler", "Cont-CC-PermExDc-v0", 1901, "box1", [_N("all_states")], {}),
+    ("cs_extex_cont_cc_lim_ia_torque_name_ie_euler", "Cont-CC-ExtExDc-v0", 1702, "box2", [_L("i_a", "torque"), _N("i_e")], {}),
+    ("cs_pmsm_cont_sc_sq_idq_lim_omega_euler", "Cont-SC-PMSM-v0", 1703, "box3", [_S("i_sd", "i_sq"), _L("omega")], {}),
+    ("cs_pmsm_fin_cc_lim_ia_ib_torque_tau1e-4_euler", "Finite-CC-PMSM-v0", 1704, "disc8", [_L("i_a", "i_b", "torque")], dict(tau=1e-4)),
+    ("cs_eesm_cont_cc_sq_idq_ie_euler", "Cont-CC-EESM-v0", 1705, "box4", [_S("i_sd", "i_sq", "i_e")], {}),
+    ("cs_scim_cont_sc_sq_iabc_lim_torque_euler", "Cont-SC-SCIM-v0", 1706, "box3", [_S("i_sa", "i_sb", "i_sc"), _L("torque")], {}),
+    ("cs_dfim_cont_sc_sq_idq_lim_ira_omega_euler", "Cont-SC-DFIM-v0", 1807, "box6", [_S("i_sd", "i_sq"), _L("i_ra", "omega")], {}),
+]
+
+
+def main_constraints(out_dir=None, cases=None, K=400):
+    """Custom constraint sets through the reference's ConstraintMonitor: squared sets that are not the default pair, mixed limit + squared
+    sets, limits on derived columns (torque, phase currents), bare names beside objects, "all_states".  Written to tests/golden/constraints/
+    (a directory of its own: the tests that enrol every tests/golden/*.npz apply the env's DEFAULT masks)."""
+    out_dir = out_dir or os.path.join(OUT, "constraints")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, env_id, seed, space_kind, spec, kw in (CONSTRAINT_CASES if cases is None else cases):
+        _, term = run_case(name, env_id, "euler", K, seed, "held", True, space_kind, constraints_spec=spec, out_dir=out_dir, **kw)
+        ends = np.nonzero(term)[0]
+        lengths = np.diff(np.concatenate([[-1], ends, [K - 1]]))
+        assert len(ends) >= 3 and lengths.max() > 50, (name, len(ends), lengths.tolist())
 
 
 def main_dfim():

@@ -107,8 +107,29 @@ def default_masks(meta):
     return lim, (1 << names.index("i_sd")) | (1 << names.index("i_sq"))
 
 
-def params_from_meta(meta, solver=None, episodic=None):
-    """Build OrcParams from a golden fixture's meta blob (see oracle/make_golden.py:describe)."""
+def masks_from_spec(meta, spec):
+    """(limit mask, squared mask) of a constraint set stored as data (oracle/make_golden.py:run_case, meta["constraints"]):
+    [{"kind": "limit" | "squared" | "name", "states": [...]}, ...]; "all_states" among a limit's or the bare names: every state
+    (constraints.py:60-68); one squared set at the most."""
+    names = meta["state_names"]
+    lim = sq = 0
+    for c in spec:
+        states = list(names) if "all_states" in c["states"] and c["kind"] in ("limit", "name") else c["states"]
+        bits = 0
+        for n in states:
+            bits |= 1 << names.index(n)
+        if c["kind"] == "squared":
+            assert sq == 0, "one squared set"
+            sq = bits
+        else:
+            assert c["kind"] in ("limit", "name"), c
+            lim |= bits
+    return lim, sq
+
+
+def params_from_meta(meta, solver=None, episodic=None, masks=None):
+    """Build OrcParams from a golden fixture's meta blob (see oracle/make_golden.py:describe).
+    masks: (limit mask, squared mask) of a custom constraint set in place of the env's default pair (episodic runs only)."""
     if isinstance(meta, (str, bytes, np.ndarray)):
         meta = json.loads(str(meta))
     p = OrcParams()
@@ -121,7 +142,7 @@ def params_from_meta(meta, solver=None, episodic=None):
     p.rtol, p.atol = _IVP_TOL.get(solver or meta["solver"], (0.0, 0.0))
     epi = meta.get("episodic", False) if episodic is None else episodic
     if epi:
-        p.limit_mask, p.squared_mask = default_masks(meta)
+        p.limit_mask, p.squared_mask = default_masks(meta) if masks is None else masks
     p.tau, p.t_il, p.u_sup = meta["tau"], meta["interlocking_time"], meta["u_nominal"]
     for i, k in enumerate(_MP_KEYS[p.system]):
         p.mp[i] = meta["motor_parameter"].get(k, 0.0)  # SynchronousReluctanceMotor has no psi_p (-> 0)
