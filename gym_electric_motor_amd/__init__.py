@@ -33,7 +33,7 @@ from .envs import BatchedElectricMotorEnv, CompleteBatchedElectricMotorEnv, defa
 from .reference_generators import BatchedWienerProcessReferenceGenerator, ReplayReferenceGenerator  # noqa: F401
 from .reference_generators import (  # noqa: F401
     BatchedMultipleReferenceGenerator, ConstReferenceGenerator, LaplaceProcessReferenceGenerator, SawtoothReferenceGenerator,
-    SinusoidalReferenceGenerator, StepReferenceGenerator, TriangularReferenceGenerator, WienerProcessReferenceGenerator,
+    SinusoidalReferenceGenerator, StepReferenceGenerator, SwitchedReferenceGenerator, TriangularReferenceGenerator, WienerProcessReferenceGenerator,
 )
 from .physical_system_wrappers import CosSinProcessor, CurrentSumProcessor, DeadTimeProcessor, DqToAbcActionProcessor  # noqa: F401
 from .observation import ObservationStage  # noqa: F401

@@ -98,6 +98,28 @@ class GemxRefgenKindsConfig(C.Structure):
     ]
 
 
+MAX_ALT = 5  # GEMX_MAX_ALT
+_ALT = MAX_REF * MAX_ALT
+
+
+class GemxRefgenSwitchedConfig(C.Structure):
+    """Mirror of `gemx_refgen_switched_config` (include/gemx.h): alternative a of column g at index g * MAX_ALT + a."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_ref", C.c_int32), ("seed", C.c_uint64), ("env_base", C.c_int64), ("tau", C.c_double),
+        ("n_alt", C.c_int32 * MAX_REF), ("super_len_lo", C.c_int32 * MAX_REF), ("super_len_hi", C.c_int32 * MAX_REF),
+        ("p", C.c_double * _ALT),
+        ("kind", C.c_int32 * _ALT), ("episode_len_lo", C.c_int32 * _ALT), ("episode_len_hi", C.c_int32 * _ALT),
+        ("margin_lo", C.c_double * _ALT), ("margin_hi", C.c_double * _ALT),
+        ("sigma_lo", C.c_double * _ALT), ("sigma_hi", C.c_double * _ALT),
+        ("initial_lo", C.c_double * _ALT), ("initial_hi", C.c_double * _ALT),
+        ("amplitude_lo", C.c_double * _ALT), ("amplitude_hi", C.c_double * _ALT),
+        ("frequency_lo", C.c_double * _ALT), ("frequency_hi", C.c_double * _ALT),
+        ("offset_lo", C.c_double * _ALT), ("offset_hi", C.c_double * _ALT),
+        ("reference_value", C.c_double * _ALT),
+    ]
+
+
 OBS_MAX_POST = 32
 OBS_COPY, OBS_SUM, OBS_COSPI, OBS_SINPI = range(4)  # GEMX_OBS_*
 
@@ -125,6 +147,7 @@ EXPORTS = (
     "gemx_set_switch_state", "gemx_aux_state_bytes", "gemx_get_aux_state", "gemx_set_aux_state", "gemx_reset_again", "gemx_rollout_synthetic", "gemx_synthetic_actions", "gemx_set_rate_limiter", "gemx_set_steps_per_block", "gemx_last_launch", "gemx_error_flags", "gemx_debug_read",
     "gemx_obsproc_create", "gemx_obsproc_apply", "gemx_obsproc_destroy",
     "gemx_refgen_rollout_shell", "gemx_reward_rows",
+    "gemx_refgen_create_switched", "gemx_refgen_get_switch_state",
 )
 
 
@@ -173,6 +196,8 @@ def load():
     L.gemx_refgen_create.argtypes = [C.POINTER(GemxRefgenConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
     L.gemx_refgen_create_kinds.argtypes = [C.POINTER(GemxRefgenKindsConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
     L.gemx_refgen_get_params.argtypes = [vp, vp, vp, vp]
+    L.gemx_refgen_create_switched.argtypes = [C.POINTER(GemxRefgenSwitchedConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_refgen_get_switch_state.argtypes = [vp, vp, vp]
     L.gemx_refgen_destroy.argtypes = [vp]
     L.gemx_refgen_reset.argtypes = [vp, vp, vp]
     L.gemx_refgen_rollout.argtypes = [vp, vp, i32, vp, vp]

@@ -22,6 +22,10 @@
 // and constant columns, freely mixed with Wiener columns.  ONE kernel (refgen_kinds_kernel) serves reset, rollout and step: one lane per
 // (env, column) keeps the sub-episode's drawn parameters in SoA arrays and evaluates its waveform in closed form at its step index --
 // nothing is tabulated.  A Wiener column there makes the draws and the arithmetic of the kernels above: the same bits.
+//
+// SwitchedReferenceGenerator (gemx_refgen_create_switched; last part of the kernels): a column that runs one of several alternatives per
+// super-episode.  A kernel of its own (refgen_switched_kernel) beside the kinds kernel, on the same helpers; handles without such a column
+// launch what they launched before.
 #include "gemx_common.hpp"
 
 void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
@@ -42,6 +46,13 @@ struct gemx_refgen {
     int has_kinds = 0, mixed = 0;
     int32_t *len = nullptr;
     double *par = nullptr;
+    // handles of gemx_refgen_create_switched with a switched column (`switched`: the handle runs refgen_switched_kernel; `kcfg` then holds
+    // alternative 0 of every column): per (column, env) the current alternative, the super-episode's step counter and length, the
+    // super-episodes drawn so far; `sdev`: the kernel's description (RefgenSwitchedDev), derived once
+    int switched = 0;
+    int32_t *alt = nullptr, *sk = nullptr, *slen = nullptr;
+    uint32_t *n_super = nullptr;
+    void *sdev = nullptr;
 };
 
 namespace {
@@ -257,21 +268,21 @@ __device__ inline double sawtooth(double x, double w) {
 
 // get_reference_observation, subepisoded_reference_generator.py:93-99, and the kinds' _reset_reference: length, then the parameters in the
 // reference's order (amplitude, frequency, offset, extras)
-__device__ inline void kinds_new_subepisode(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
+template <class Dev> __device__ inline void kinds_new_subepisode(const Dev &G, int64_t env, int g, int c, KindLane &s) {
     uint32_t r[4], q[4];
-    const int kind = G.kind[g];
+    const int kind = G.kind[c];
     refgen_block(G.seed, G.env_base + env, g, DRAW_SUB, s.ns, r);
-    s.len = (int32_t)((double)(G.len_hi[g] - G.len_lo[g]) * gemx::Philox::u01(r[0]) + (double)G.len_lo[g]);
+    s.len = (int32_t)((double)(G.len_hi[c] - G.len_lo[c]) * gemx::Philox::u01(r[0]) + (double)G.len_lo[c]);
     s.lf = s.len;
     if (kind == GEMX_REF_WIENER || kind == GEMX_REF_LAPLACE) {  // wiener ... :31, laplace ... :27
-        s.sg = pow(10.0, (G.log_sig_hi[g] - G.log_sig_lo[g]) * gemx::Philox::u01(r[1]) + G.log_sig_lo[g]);
+        s.sg = pow(10.0, (G.log_sig_hi[c] - G.log_sig_lo[c]) * gemx::Philox::u01(r[1]) + G.log_sig_lo[c]);
     } else {
         refgen_block(G.seed, G.env_base + env, g, DRAW_SUB2, s.ns, q);
-        s.amp = uniform(G.a_lo[g], G.a_hi[g], r[1]);
-        s.freq = uniform(G.f_lo[g], G.f_hi[g], r[2]);
+        s.amp = uniform(G.a_lo[c], G.a_hi[c], r[1]);
+        s.freq = uniform(G.f_lo[c], G.f_hi[c], r[2]);
         // sinusoidal ... :53-57 (triangle, sawtooth alike): [-m_hi + A, m_hi - A]; step_reference_generator.py:41-45: [m_lo + A, m_hi - A]
-        const double lo = (kind == GEMX_REF_STEP ? G.m_lo[g] : -G.m_hi[g]) + s.amp, hi = G.m_hi[g] - s.amp;
-        s.off = uniform(clip(G.o_lo[g], lo, hi), clip(G.o_hi[g], lo, hi), r[3]);
+        const double lo = (kind == GEMX_REF_STEP ? G.m_lo[c] : -G.m_hi[c]) + s.amp, hi = G.m_hi[c] - s.amp;
+        s.off = uniform(clip(G.o_lo[c], lo, hi), clip(G.o_hi[c], lo, hi), r[3]);
         const double u0 = gemx::Philox::u01(q[0]), u1 = gemx::Philox::u01(q[1]);
         s.phase = 0.0; s.width = 1.0; s.roll = 0.0;
         if (kind == GEMX_REF_STEP) {
@@ -287,23 +298,23 @@ __device__ inline void kinds_new_subepisode(const RefgenKindsDev &G, int64_t env
 
 // reset(): Wiener draws its initial value (wiener ... :43-49), every other sub-episoded kind restarts from 0 (subepisoded ... :80-86);
 // a new sub-episode starts with the next step.  (Constant columns never get here: refgen_kinds_kernel writes their value and returns.)
-__device__ inline void kinds_reset(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
-    const int kind = G.kind[g];
+template <class Dev> __device__ inline void kinds_reset(const Dev &G, int64_t env, int g, int c, KindLane &s) {
+    const int kind = G.kind[c];
     if (kind == GEMX_REF_WIENER) {
         uint32_t r[4];
         refgen_block(G.seed, G.env_base + env, g, DRAW_RESET, s.nr++, r);
-        s.v = (G.i_hi[g] - G.i_lo[g]) * gemx::Philox::u01(r[0]) + G.i_lo[g];
+        s.v = (G.i_hi[c] - G.i_lo[c]) * gemx::Philox::u01(r[0]) + G.i_lo[c];
     } else {
         s.v = 0.0;
     }
     s.lf = 0;
 }
 
-template <class R> __device__ inline double kinds_advance(const RefgenKindsDev &G, int64_t env, int g, KindLane &s) {
-    const int kind = G.kind[g];
-    if (s.lf <= 0) kinds_new_subepisode(G, env, g, s);
+template <class R, class Dev> __device__ inline double kinds_advance(const Dev &G, int64_t env, int g, int c, KindLane &s) {
+    const int kind = G.kind[c];
+    if (s.lf <= 0) kinds_new_subepisode(G, env, g, c, s);
     const int32_t k = s.len - s.lf;  // index inside the sub-episode
-    const double m_lo = G.m_lo[g], m_hi = G.m_hi[g];
+    const double m_lo = G.m_lo[c], m_hi = G.m_hi[c];
     double v;
     if (kind == GEMX_REF_WIENER) {  // (walk_step's arithmetic on step_normal's draw: the bits of the all-Wiener kernels)
         v = s.v + s.sg * (double)step_normal<R>(G.seed, G.env_base + env, g, s.t);
@@ -362,12 +373,12 @@ __global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8
     }
     const uint32_t ns0 = s.ns, nr0 = s.nr;
     if (K == 0) {
-        if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, s);
+        if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, g, s);
     }
     for (int k = 0; k < K; ++k) {
-        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) kinds_reset(G, env, g, s);
-        out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, s);
-        if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, s);
+        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
+        out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, g, s);
+        if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
     }
     value[si] = s.v; left[si] = s.lf; t[si] = s.t;
     if (s.nr != nr0) n_reset[si] = s.nr;
@@ -380,23 +391,26 @@ __global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8
     }
 }
 
+// description slot `s` of G from column / alternative `j` of a config (gemx_refgen_kinds_config, gemx_refgen_switched_config: the same fields)
+template <class Dev, class Cfg> void set_description(Dev &G, int s, const Cfg &c, int j) {
+    G.kind[s] = c.kind[j]; G.len_lo[s] = c.episode_len_lo[j]; G.len_hi[s] = c.episode_len_hi[j];
+    G.m_lo[s] = c.margin_lo[j]; G.m_hi[s] = c.margin_hi[j]; G.c[s] = c.reference_value[j];
+    if (c.kind[j] == GEMX_REF_WIENER || c.kind[j] == GEMX_REF_LAPLACE) {
+        G.log_sig_lo[s] = log10(c.sigma_lo[j]); G.log_sig_hi[s] = log10(c.sigma_hi[j]);
+        G.i_lo[s] = c.initial_lo[j]; G.i_hi[s] = c.initial_hi[j];
+    } else {  // the reference's set_modules (e.g. sinusoidal ... :42-48): amplitudes within half the margin's width, offsets within the margin
+        const double half = (c.margin_hi[j] - c.margin_lo[j]) / 2;
+        G.a_lo[s] = fmin(fmax(c.amplitude_lo[j], 0.0), half); G.a_hi[s] = fmin(fmax(c.amplitude_hi[j], 0.0), half);
+        G.o_lo[s] = fmin(fmax(c.offset_lo[j], c.margin_lo[j]), c.margin_hi[j]); G.o_hi[s] = fmin(fmax(c.offset_hi[j], c.margin_lo[j]), c.margin_hi[j]);
+        G.f_lo[s] = c.frequency_lo[j]; G.f_hi[s] = c.frequency_hi[j];
+    }
+}
+
 RefgenKindsDev make_kinds_dev(const gemx_refgen_kinds_config &c) {
     RefgenKindsDev G;
     memset(&G, 0, sizeof(G));
     G.n_ref = c.n_ref; G.seed = c.seed; G.env_base = c.env_base; G.tau = c.tau;
-    for (int g = 0; g < c.n_ref; ++g) {
-        G.kind[g] = c.kind[g]; G.len_lo[g] = c.episode_len_lo[g]; G.len_hi[g] = c.episode_len_hi[g];
-        G.m_lo[g] = c.margin_lo[g]; G.m_hi[g] = c.margin_hi[g]; G.c[g] = c.reference_value[g];
-        if (c.kind[g] == GEMX_REF_WIENER || c.kind[g] == GEMX_REF_LAPLACE) {
-            G.log_sig_lo[g] = log10(c.sigma_lo[g]); G.log_sig_hi[g] = log10(c.sigma_hi[g]);
-            G.i_lo[g] = c.initial_lo[g]; G.i_hi[g] = c.initial_hi[g];
-        } else {  // the reference's set_modules (e.g. sinusoidal ... :42-48): amplitudes within half the margin's width, offsets within the margin
-            const double half = (c.margin_hi[g] - c.margin_lo[g]) / 2;
-            G.a_lo[g] = fmin(fmax(c.amplitude_lo[g], 0.0), half); G.a_hi[g] = fmin(fmax(c.amplitude_hi[g], 0.0), half);
-            G.o_lo[g] = fmin(fmax(c.offset_lo[g], c.margin_lo[g]), c.margin_hi[g]); G.o_hi[g] = fmin(fmax(c.offset_hi[g], c.margin_lo[g]), c.margin_hi[g]);
-            G.f_lo[g] = c.frequency_lo[g]; G.f_hi[g] = c.frequency_hi[g];
-        }
-    }
+    for (int g = 0; g < c.n_ref; ++g) set_description(G, g, c, g);
     return G;
 }
 
@@ -409,10 +423,6 @@ int kinds_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
 }
-int kinds(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
-    return r->f64 ? kinds_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
-                  : kinds_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
-}
 
 // small kernel of gemx_refgen_get_params: kind / step index / length per (column, env)
 __global__ void refgen_kinds_index_kernel(int32_t *out, int64_t N, int n_ref, int mixed, RefgenKindsDev G, const int32_t *left, const int32_t *len) {
@@ -422,6 +432,177 @@ __global__ void refgen_kinds_index_kernel(int32_t *out, int64_t N, int n_ref, in
     out[si] = G.kind[si / N];
     out[m + si] = mixed ? len[si] - left[si] : -1;
     out[2 * m + si] = mixed ? len[si] : -1;
+}
+
+// ---- SwitchedReferenceGenerator (switched_reference_generator.py:8-95; include/gemx.h) ---------------------------------------------------
+// A switched column runs ONE of its alternatives per super-episode; which one is per-lane state, so the kernel reads the alternative's
+// description at slot column * GEMX_MAX_ALT + alternative and hands it to the helpers of the kinds kernel above.  A plain column is
+// slot column * GEMX_MAX_ALT with no super-episodes: the kinds kernel's draws and arithmetic.
+//   DRAW_SUPER index n_super  word 0: super-episode length, integers(lo, hi); word 1: the alternative, inverse distribution function of p
+enum { DRAW_SUPER = 4 };
+constexpr int ALT_SLOTS = GEMX_MAX_REF * GEMX_MAX_ALT;
+
+struct RefgenSwitchedDev {  // 2560 B, a kernel argument
+    int32_t n_ref;
+    uint64_t seed;
+    int64_t env_base;
+    double tau;
+    int32_t n_alt[GEMX_MAX_REF], sup_lo[GEMX_MAX_REF], sup_hi[GEMX_MAX_REF];  // n_alt = 0: a plain column
+    double cdf[ALT_SLOTS];                                                    // running sums of p
+    int32_t kind[ALT_SLOTS], len_lo[ALT_SLOTS], len_hi[ALT_SLOTS];
+    double log_sig_lo[ALT_SLOTS], log_sig_hi[ALT_SLOTS], m_lo[ALT_SLOTS], m_hi[ALT_SLOTS], i_lo[ALT_SLOTS], i_hi[ALT_SLOTS];
+    double a_lo[ALT_SLOTS], a_hi[ALT_SLOTS], f_lo[ALT_SLOTS], f_hi[ALT_SLOTS], o_lo[ALT_SLOTS], o_hi[ALT_SLOTS], c[ALT_SLOTS];
+};
+
+__device__ inline bool is_wave(int kind) { return kind >= GEMX_REF_SINUS && kind <= GEMX_REF_SAWTOOTH; }
+
+struct SuperLane {  // the super-episode state of one (column, env), in registers
+    int32_t alt, sk, slen;
+    uint32_t nsup;
+};
+
+// _reset_reference, switched ... :83-88: the length, then the alternative
+__device__ inline void switched_new_superepisode(const RefgenSwitchedDev &G, int64_t env, int g, SuperLane &u) {
+    uint32_t r[4];
+    refgen_block(G.seed, G.env_base + env, g, DRAW_SUPER, u.nsup++, r);
+    u.slen = (int32_t)((double)(G.sup_hi[g] - G.sup_lo[g]) * gemx::Philox::u01(r[0]) + (double)G.sup_lo[g]);
+    const double x = gemx::Philox::u01(r[1]);
+    int a = 0;
+#pragma unroll
+    for (int i = 0; i < GEMX_MAX_ALT - 1; ++i) a += (i + 1 < G.n_alt[g] && x >= G.cdf[g * GEMX_MAX_ALT + i]) ? 1 : 0;
+    u.alt = a;
+}
+// reset(), :65-68: a new super-episode; the chosen alternative is reset without an initial reference.  Its own first value comes with the
+// next step and is not counted: sk = -1 until then
+__device__ inline void switched_reset(const RefgenSwitchedDev &G, int64_t env, int g, SuperLane &u, KindLane &s) {
+    switched_new_superepisode(G, env, g, u);
+    u.sk = -1;
+    kinds_reset(G, env, g, g * GEMX_MAX_ALT + u.alt, s);
+}
+// get_reference_observation, :74-81: at the super-episode's end the newly chosen alternative restarts from the value shown last (kept in
+// s.v) with a sub-episode of its own; a CONST alternative shows its value
+template <class R> __device__ inline double switched_advance(const RefgenSwitchedDev &G, int64_t env, int g, SuperLane &u, KindLane &s) {
+    if (u.sk >= u.slen) {
+        switched_new_superepisode(G, env, g, u);
+        u.sk = 0;
+        s.lf = 0;
+    }
+    const int c = g * GEMX_MAX_ALT + u.alt;
+    ++u.sk;
+    if (G.kind[c] == GEMX_REF_CONST) return s.v = G.c[c];
+    return kinds_advance<R>(G, env, g, c, s);
+}
+
+// the four uses of refgen_kinds_kernel (reset, rollout, step, shell-order rollout), same lane mapping: out[k][env][g].  Launched with
+// 256 threads, and told so: without the bound the compiler keeps to 128 VGPRs and spills
+template <class R>
+__global__ void __launch_bounds__(256) refgen_switched_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
+                                       int K, RefgenSwitchedDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
+                                       uint64_t *t, int32_t *len, double *par, int32_t *alt, int32_t *sk, int32_t *slen, uint32_t *n_super) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= N * G.n_ref) return;
+    const int g = (int)(idx % G.n_ref);
+    const int64_t env = idx / G.n_ref;
+    const int64_t si = (int64_t)g * N + env, stride = (int64_t)G.n_ref * N;
+    const bool switched = G.n_alt[g] > 0;
+    const int c0 = g * GEMX_MAX_ALT;
+    if (!switched && G.kind[c0] == GEMX_REF_CONST) {  // a plain constant column: no state at all
+        for (int k = 0; k < K; ++k) out[((int64_t)k * N + env) * G.n_ref + g] = (R)G.c[c0];
+        return;
+    }
+    SuperLane u = {0, 0, 0, 0u};
+    if (switched) { u.alt = alt[si]; u.sk = sk[si]; u.slen = slen[si]; u.nsup = n_super[si]; }
+    const SuperLane u0 = u;
+    // the waveform's parameters: read where the lane's current kind is a waveform (a newly chosen alternative draws all of them before it
+    // reads any); written back -- like sigma and the length -- only by a lane that started a sub-episode in this launch: the parameters of
+    // its last one, zeros where that was a walk's, so that the stored state does not depend on how the steps were cut into launches
+    const int kind0 = G.kind[c0 + u.alt];
+    KindLane s;
+    s.v = value[si]; s.sg = sigma[si]; s.lf = left[si]; s.ns = n_sub[si]; s.nr = n_reset[si]; s.t = t[si]; s.len = len[si];
+    s.amp = s.freq = s.off = s.phase = s.roll = 0.0; s.width = 1.0;
+    bool wave = is_wave(kind0);  // (from here on: the kind of the last sub-episode started in this launch)
+    if (wave) {
+        s.amp = par[PAR_AMP * stride + si]; s.freq = par[PAR_FREQ * stride + si]; s.off = par[PAR_OFF * stride + si];
+        s.phase = par[PAR_PHASE * stride + si]; s.width = par[PAR_WIDTH * stride + si]; s.roll = par[PAR_ROLL * stride + si];
+    }
+    const uint32_t ns0 = s.ns, nr0 = s.nr;
+    if (K == 0 && (reset_all || (reset_mask != nullptr && reset_mask[env]))) {
+        if (switched) switched_reset(G, env, g, u, s);
+        else kinds_reset(G, env, g, c0, s);
+    }
+    for (int k = 0; k < K; ++k) {
+        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) {
+            if (switched) switched_reset(G, env, g, u, s);
+            else kinds_reset(G, env, g, c0, s);
+        }
+        const uint32_t ns1 = s.ns;
+        out[((int64_t)k * N + env) * G.n_ref + g] = (R)(switched ? switched_advance<R>(G, env, g, u, s) : kinds_advance<R>(G, env, g, c0, s));
+        if (s.ns != ns1) wave = is_wave(G.kind[c0 + u.alt]);
+        if (done_post != nullptr && done_post[(int64_t)k * N + env]) {
+            if (switched) switched_reset(G, env, g, u, s);
+            else kinds_reset(G, env, g, c0, s);
+        }
+    }
+    value[si] = s.v; left[si] = s.lf; t[si] = s.t;
+    if (s.nr != nr0) n_reset[si] = s.nr;
+    if (s.ns != ns0) {
+        n_sub[si] = s.ns; sigma[si] = s.sg; len[si] = s.len;
+        if (wave || switched) {
+            par[PAR_AMP * stride + si] = wave ? s.amp : 0.0; par[PAR_FREQ * stride + si] = wave ? s.freq : 0.0; par[PAR_OFF * stride + si] = wave ? s.off : 0.0;
+            par[PAR_PHASE * stride + si] = wave ? s.phase : 0.0; par[PAR_WIDTH * stride + si] = wave ? s.width : 0.0; par[PAR_ROLL * stride + si] = wave ? s.roll : 0.0;
+        }
+    }
+    if (u.sk != u0.sk) sk[si] = u.sk;
+    if (u.nsup != u0.nsup) { alt[si] = u.alt; slen[si] = u.slen; n_super[si] = u.nsup; }
+}
+
+RefgenSwitchedDev make_switched_dev(const gemx_refgen_switched_config &c) {
+    RefgenSwitchedDev G;
+    memset(&G, 0, sizeof(G));
+    G.n_ref = c.n_ref; G.seed = c.seed; G.env_base = c.env_base; G.tau = c.tau;
+    for (int g = 0; g < c.n_ref; ++g) {
+        G.n_alt[g] = c.n_alt[g]; G.sup_lo[g] = c.super_len_lo[g]; G.sup_hi[g] = c.super_len_hi[g];
+        double sum = 0.0;
+        for (int a = 0; a < (c.n_alt[g] > 0 ? c.n_alt[g] : 1); ++a) {
+            const int s = g * GEMX_MAX_ALT + a;
+            set_description(G, s, c, s);
+            G.cdf[s] = (sum += c.p[s]);
+        }
+    }
+    return G;
+}
+
+template <class R>
+int switched_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+    const int64_t lanes = r->n * r->cfg.n_ref;
+    gemx_cov_note(sizeof(R) == 4 ? "refgen_switched_kernel<float>" : "refgen_switched_kernel<double>");
+    hipLaunchKernelGGL(refgen_switched_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
+                       *(const RefgenSwitchedDev *)r->sdev, r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par, r->alt, r->sk, r->slen,
+                       r->n_super);
+    GEMX_HIP_TRY(hipGetLastError());
+    return GEMX_OK;
+}
+// every entry point's dispatch for the handles that run one kernel for all four uses: the switched kernel, else the kinds kernel
+int kinds(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+    if (r->switched)
+        return r->f64 ? switched_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
+                      : switched_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
+    return r->f64 ? kinds_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
+                  : kinds_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
+}
+
+// gemx_refgen_get_params on a switched handle: the kind of the lane's current alternative
+__global__ void refgen_switched_index_kernel(int32_t *out, int64_t N, int n_ref, RefgenSwitchedDev G, const int32_t *left, const int32_t *len, const int32_t *alt) {
+    const int64_t si = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t m = N * n_ref;
+    if (si >= m) return;
+    const int g = (int)(si / N);
+    const bool switched = G.n_alt[g] > 0;
+    const int kind = G.kind[g * GEMX_MAX_ALT + (switched ? alt[si] : 0)];
+    const bool none = switched && kind == GEMX_REF_CONST;  // (a constant alternative has no sub-episodes)
+    out[si] = kind;
+    out[m + si] = none ? -1 : len[si] - left[si];
+    out[2 * m + si] = none ? -1 : len[si];
 }
 
 }  // namespace
@@ -446,6 +627,44 @@ static int gemx_refgen_alloc(const gemx_refgen_config &cfg, const gemx_refgen_ki
     (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4); (void)hipMemset(r->t, 0, m * 8);
     if (kcfg) { (void)hipMemset(r->len, 0, m * 4); (void)hipMemset(r->par, 0, m * 8 * N_PAR); }
     *out = r;
+    return GEMX_OK;
+}
+
+// the columns of a kinds config, checked; `w`: their Wiener view (what gemx_refgen_create would be given for these columns)
+static int refgen_check_columns(const gemx_refgen_kinds_config &c, gemx_refgen_config &w, int &all_wiener) {
+    const gemx_refgen_kinds_config *cfg = &c;
+    memset(&w, 0, sizeof(w));
+    w.struct_size = (int32_t)sizeof(w); w.n_ref = cfg->n_ref; w.seed = cfg->seed; w.env_base = cfg->env_base;
+    w.episode_len_lo = cfg->episode_len_lo[0]; w.episode_len_hi = cfg->episode_len_hi[0];
+    all_wiener = 1;
+    for (int g = 0; g < cfg->n_ref; ++g) {
+        const int kind = cfg->kind[g];
+        if (kind < GEMX_REF_WIENER || kind > GEMX_REF_CONST) return gemx::fail(GEMX_ERR_ARG, "column %d: unknown generator kind %d", g, kind);
+        w.margin_lo[g] = cfg->margin_lo[g]; w.margin_hi[g] = cfg->margin_hi[g]; w.sigma_lo[g] = cfg->sigma_lo[g]; w.sigma_hi[g] = cfg->sigma_hi[g];
+        w.initial_lo[g] = cfg->initial_lo[g]; w.initial_hi[g] = cfg->initial_hi[g];
+        if (kind != GEMX_REF_WIENER || cfg->episode_len_lo[g] != w.episode_len_lo || cfg->episode_len_hi[g] != w.episode_len_hi) all_wiener = 0;
+        if (kind == GEMX_REF_CONST) continue;
+        if (cfg->episode_len_lo[g] < 1 || cfg->episode_len_hi[g] < cfg->episode_len_lo[g]) return gemx::fail(GEMX_ERR_ARG, "episode lengths %d must satisfy 1 <= lo <= hi", g);
+        if (cfg->margin_hi[g] < cfg->margin_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty margin %d", g);
+        if (kind == GEMX_REF_WIENER || kind == GEMX_REF_LAPLACE) {
+            if (!(cfg->sigma_lo[g] > 0) || cfg->sigma_hi[g] < cfg->sigma_lo[g]) return gemx::fail(GEMX_ERR_ARG, "sigma range %d must satisfy 0 < lo <= hi", g);
+            if (kind == GEMX_REF_WIENER && cfg->initial_hi[g] < cfg->initial_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty initial range %d", g);
+        } else {
+            if (!(cfg->frequency_lo[g] >= 0) || cfg->frequency_hi[g] < cfg->frequency_lo[g] || !(cfg->frequency_hi[g] < HUGE_VAL))
+                return gemx::fail(GEMX_ERR_ARG, "frequency range %d must satisfy 0 <= lo <= hi < inf", g);
+            if (kind == GEMX_REF_STEP && !(cfg->frequency_lo[g] > 0)) return gemx::fail(GEMX_ERR_ARG, "frequency range %d of a step generator must be positive", g);
+            if (cfg->amplitude_lo[g] != cfg->amplitude_lo[g] || cfg->amplitude_hi[g] != cfg->amplitude_hi[g] || cfg->offset_lo[g] != cfg->offset_lo[g] ||
+                cfg->offset_hi[g] != cfg->offset_hi[g])
+                return gemx::fail(GEMX_ERR_ARG, "amplitude / offset range %d is not a number", g);
+        }
+    }
+    return GEMX_OK;
+}
+static int refgen_check_device(int device, int dtype) {
+    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
+    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
     return GEMX_OK;
 }
 
@@ -478,39 +697,83 @@ int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs
     if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
     if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
     if (!(cfg->tau > 0)) return gemx::fail(GEMX_ERR_ARG, "tau must be positive");
-    gemx_refgen_config w;  // the Wiener view: what gemx_refgen_create would be given for these columns
-    memset(&w, 0, sizeof(w));
-    w.struct_size = (int32_t)sizeof(w); w.n_ref = cfg->n_ref; w.seed = cfg->seed; w.env_base = cfg->env_base;
-    w.episode_len_lo = cfg->episode_len_lo[0]; w.episode_len_hi = cfg->episode_len_hi[0];
+    gemx_refgen_config w;
     int all_wiener = 1;
-    for (int g = 0; g < cfg->n_ref; ++g) {
-        const int kind = cfg->kind[g];
-        if (kind < GEMX_REF_WIENER || kind > GEMX_REF_CONST) return gemx::fail(GEMX_ERR_ARG, "column %d: unknown generator kind %d", g, kind);
-        w.margin_lo[g] = cfg->margin_lo[g]; w.margin_hi[g] = cfg->margin_hi[g]; w.sigma_lo[g] = cfg->sigma_lo[g]; w.sigma_hi[g] = cfg->sigma_hi[g];
-        w.initial_lo[g] = cfg->initial_lo[g]; w.initial_hi[g] = cfg->initial_hi[g];
-        if (kind != GEMX_REF_WIENER || cfg->episode_len_lo[g] != w.episode_len_lo || cfg->episode_len_hi[g] != w.episode_len_hi) all_wiener = 0;
-        if (kind == GEMX_REF_CONST) continue;
-        if (cfg->episode_len_lo[g] < 1 || cfg->episode_len_hi[g] < cfg->episode_len_lo[g]) return gemx::fail(GEMX_ERR_ARG, "episode lengths %d must satisfy 1 <= lo <= hi", g);
-        if (cfg->margin_hi[g] < cfg->margin_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty margin %d", g);
-        if (kind == GEMX_REF_WIENER || kind == GEMX_REF_LAPLACE) {
-            if (!(cfg->sigma_lo[g] > 0) || cfg->sigma_hi[g] < cfg->sigma_lo[g]) return gemx::fail(GEMX_ERR_ARG, "sigma range %d must satisfy 0 < lo <= hi", g);
-            if (kind == GEMX_REF_WIENER && cfg->initial_hi[g] < cfg->initial_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty initial range %d", g);
-        } else {
-            if (!(cfg->frequency_lo[g] >= 0) || cfg->frequency_hi[g] < cfg->frequency_lo[g] || !(cfg->frequency_hi[g] < HUGE_VAL))
-                return gemx::fail(GEMX_ERR_ARG, "frequency range %d must satisfy 0 <= lo <= hi < inf", g);
-            if (kind == GEMX_REF_STEP && !(cfg->frequency_lo[g] > 0)) return gemx::fail(GEMX_ERR_ARG, "frequency range %d of a step generator must be positive", g);
-            if (cfg->amplitude_lo[g] != cfg->amplitude_lo[g] || cfg->amplitude_hi[g] != cfg->amplitude_hi[g] || cfg->offset_lo[g] != cfg->offset_lo[g] ||
-                cfg->offset_hi[g] != cfg->offset_hi[g])
-                return gemx::fail(GEMX_ERR_ARG, "amplitude / offset range %d is not a number", g);
-        }
-    }
-    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
-    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
+    if (int rc = refgen_check_columns(*cfg, w, all_wiener)) return rc;
+    if (int rc = refgen_check_device(device, dtype)) return rc;
     const int rc = gemx_refgen_alloc(w, cfg, n_envs, device, dtype, out);
     if (rc == GEMX_OK) (*out)->mixed = !all_wiener;  // all Wiener, one length range: the kernels (and bits) of a gemx_refgen_create handle
     return rc;
+}
+
+// column g of a kinds config := alternative a of column g of a switched config
+static void refgen_alternative(const gemx_refgen_switched_config &c, int g, int a, gemx_refgen_kinds_config &k) {
+    const int s = g * GEMX_MAX_ALT + a;
+    k.kind[g] = c.kind[s]; k.episode_len_lo[g] = c.episode_len_lo[s]; k.episode_len_hi[g] = c.episode_len_hi[s];
+    k.margin_lo[g] = c.margin_lo[s]; k.margin_hi[g] = c.margin_hi[s]; k.sigma_lo[g] = c.sigma_lo[s]; k.sigma_hi[g] = c.sigma_hi[s];
+    k.initial_lo[g] = c.initial_lo[s]; k.initial_hi[g] = c.initial_hi[s]; k.amplitude_lo[g] = c.amplitude_lo[s]; k.amplitude_hi[g] = c.amplitude_hi[s];
+    k.frequency_lo[g] = c.frequency_lo[s]; k.frequency_hi[g] = c.frequency_hi[s]; k.offset_lo[g] = c.offset_lo[s]; k.offset_hi[g] = c.offset_hi[s];
+    k.reference_value[g] = c.reference_value[s];
+}
+
+int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
+    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(gemx_refgen_switched_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_switched_config size mismatch");
+    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
+    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
+    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
+    if (!(cfg->tau > 0)) return gemx::fail(GEMX_ERR_ARG, "tau must be positive");
+    int any = 0, most = 1;
+    for (int g = 0; g < cfg->n_ref; ++g) {
+        const int n = cfg->n_alt[g];
+        if (n < 0 || n > GEMX_MAX_ALT) return gemx::fail(GEMX_ERR_ARG, "column %d: n_alt must be in [0, %d] (0: a plain column), not %d", g, GEMX_MAX_ALT, n);
+        if (n == 0) continue;
+        any = 1;
+        if (n > most) most = n;
+        double sum = 0.0;
+        for (int a = 0; a < n; ++a) {
+            const double p = cfg->p[g * GEMX_MAX_ALT + a];
+            if (!(p >= 0.0)) return gemx::fail(GEMX_ERR_ARG, "column %d: probability %d must be >= 0", g, a);
+            sum += p;
+        }
+        if (!(fabs(sum - 1.0) <= 1e-9)) return gemx::fail(GEMX_ERR_ARG, "column %d: the probabilities must sum to 1", g);
+        if (cfg->super_len_lo[g] < 1 || cfg->super_len_hi[g] <= cfg->super_len_lo[g])
+            return gemx::fail(GEMX_ERR_ARG, "column %d: super-episode lengths must satisfy 1 <= lo < hi", g);
+    }
+    // the alternatives, one kinds config per alternative index (a column with fewer alternatives repeats its last): checked as
+    // gemx_refgen_create_kinds checks its columns
+    gemx_refgen_kinds_config k0;
+    gemx_refgen_config w0;
+    for (int a = 0; a < most; ++a) {
+        gemx_refgen_kinds_config k;
+        memset(&k, 0, sizeof(k));
+        k.struct_size = (int32_t)sizeof(k); k.n_ref = cfg->n_ref; k.seed = cfg->seed; k.env_base = cfg->env_base; k.tau = cfg->tau;
+        for (int g = 0; g < cfg->n_ref; ++g) refgen_alternative(*cfg, g, a < cfg->n_alt[g] ? a : (cfg->n_alt[g] > 0 ? cfg->n_alt[g] - 1 : 0), k);
+        gemx_refgen_config w;
+        int all_wiener = 1;
+        if (int rc = refgen_check_columns(k, w, all_wiener)) return rc;
+        if (a == 0) { k0 = k; w0 = w; }
+    }
+    if (!any) return gemx_refgen_create_kinds(&k0, n_envs, device, dtype, out);  // no switched column: that handle, and its kernels
+    if (int rc = refgen_check_device(device, dtype)) return rc;
+    const int rc = gemx_refgen_alloc(w0, &k0, n_envs, device, dtype, out);
+    if (rc != GEMX_OK) return rc;
+    gemx_refgen *r = *out;
+    gemx::DeviceGuard guard(device);
+    const size_t m = (size_t)n_envs * cfg->n_ref;
+    RefgenSwitchedDev *G = new (std::nothrow) RefgenSwitchedDev(make_switched_dev(*cfg));
+    r->sdev = G;
+    if (!G || hipMalloc((void **)&r->alt, m * 4) != hipSuccess || hipMalloc((void **)&r->sk, m * 4) != hipSuccess ||
+        hipMalloc((void **)&r->slen, m * 4) != hipSuccess || hipMalloc((void **)&r->n_super, m * 4) != hipSuccess) {
+        gemx_refgen_destroy(r);
+        *out = nullptr;
+        return gemx::fail(GEMX_ERR_ALLOC, "allocation (switched refgen) failed");
+    }
+    (void)hipMemset(r->alt, 0, m * 4); (void)hipMemset(r->sk, 0, m * 4); (void)hipMemset(r->slen, 0, m * 4); (void)hipMemset(r->n_super, 0, m * 4);
+    r->mixed = 1;
+    r->switched = 1;
+    return GEMX_OK;
 }
 
 int gemx_refgen_destroy(gemx_refgen *r) {
@@ -524,6 +787,11 @@ int gemx_refgen_destroy(gemx_refgen *r) {
     if (r->t) (void)hipFree(r->t);
     if (r->len) (void)hipFree(r->len);
     if (r->par) (void)hipFree(r->par);
+    if (r->alt) (void)hipFree(r->alt);
+    if (r->sk) (void)hipFree(r->sk);
+    if (r->slen) (void)hipFree(r->slen);
+    if (r->n_super) (void)hipFree(r->n_super);
+    delete (RefgenSwitchedDev *)r->sdev;
     delete r;
     return GEMX_OK;
 }
@@ -601,12 +869,27 @@ int gemx_refgen_get_params(gemx_refgen *r, int32_t *kind_index_len_out_dev, doub
     gemx::DeviceGuard guard(r->device);
     const int64_t m = r->n * r->kcfg.n_ref;
     hipStream_t st = (hipStream_t)stream;
-    if (kind_index_len_out_dev) {
+    if (kind_index_len_out_dev && r->switched) {
+        hipLaunchKernelGGL(refgen_switched_index_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, kind_index_len_out_dev, r->n, r->kcfg.n_ref,
+                           *(const RefgenSwitchedDev *)r->sdev, r->left, r->len, r->alt);
+        GEMX_HIP_TRY(hipGetLastError());
+    } else if (kind_index_len_out_dev) {
         hipLaunchKernelGGL(refgen_kinds_index_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, kind_index_len_out_dev, r->n, r->kcfg.n_ref, r->mixed,
                            make_kinds_dev(r->kcfg), r->left, r->len);
         GEMX_HIP_TRY(hipGetLastError());
     }
     if (params_out_dev) GEMX_HIP_TRY(hipMemcpyAsync(params_out_dev, r->par, (size_t)m * 8 * N_PAR, hipMemcpyDeviceToDevice, st));
+    return GEMX_OK;
+}
+
+int gemx_refgen_get_switch_state(gemx_refgen *r, int32_t *alt_sk_slen_nsuper_out_dev, void *stream) {
+    if (!r || !alt_sk_slen_nsuper_out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    if (!r->switched) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_get_switch_state needs a gemx_refgen_create_switched handle with a switched column");
+    gemx::DeviceGuard guard(r->device);
+    const size_t m = (size_t)r->n * r->cfg.n_ref;
+    hipStream_t st = (hipStream_t)stream;
+    const void *src[4] = {r->alt, r->sk, r->slen, r->n_super};
+    for (int i = 0; i < 4; ++i) GEMX_HIP_TRY(hipMemcpyAsync(alt_sk_slen_nsuper_out_dev + i * m, src[i], m * 4, hipMemcpyDeviceToDevice, st));
     return GEMX_OK;
 }
 

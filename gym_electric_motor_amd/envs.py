@@ -29,7 +29,8 @@ K steps in one call: `state, refs, reward, done = env.rollout_complete(actions [
 bit, in three launches (physics rollout; generators in the shell's order on its done mask; reward pass over the stored rows); also
 `rollout_complete_synthetic(K)` and the pre-bound, graph-capturable `bind_rollout_complete(...)`.
 The reference's other generator kinds (sinusoidal, step, triangular, sawtooth, Laplace process, constant) run on the same path: pass a
-holder named after the reference's class, a list of them or a `BatchedMultipleReferenceGenerator` as `reference_generator=`.
+holder named after the reference's class, a list of them or a `BatchedMultipleReferenceGenerator` as `reference_generator=`;
+`ga.SwitchedReferenceGenerator(holders, p=..., super_episode_length=...)` is such a holder: a waveform kind per super-episode and env.
 
 The observation side runs on the device too (observation.py, csrc/gemx_obsproc.hip): `physical_system_wrappers=` may hold
 `CurrentSumProcessor` / `CosSinProcessor` holders (`"default"`: what the reference's env class wraps its system in -- the `i_sum` column
@@ -42,7 +43,8 @@ of the six shunt envs), `observed_states=[names]` is the reference's `state_filt
 
 Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the noisy state, which
 the fused kernels cannot reproduce in a post-pass), `FluxObserver`, reward weights or constraints on appended columns (`i_sum`,
-`cos(...)`), visualisation and `SwitchedReferenceGenerator`.  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
+`cos(...)`) and visualisation; an instance of the reference's own `SwitchedReferenceGenerator` is refused (pass the holder of that
+name).  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
 `physical_system=` to the reference's own `ElectricMotorEnvironment`.
 """
 import re
@@ -632,8 +634,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     observed_states: None | list of state names of the wrapped system -- the reference's `state_filter`, applied last.
     flatten_observation: the complete env hands out ONE tensor [N, n_post + n_ref], the processed state followed by the references.
     reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
-    StepReferenceGenerator(...) or a list of holders (one per referenced state; the reference's own generator instances are read the
-    same way) | ReplayReferenceGenerator;
+    StepReferenceGenerator(...) or SwitchedReferenceGenerator([...]), or a list of holders (one per referenced state; the reference's own
+    generator instances are read the same way, its SwitchedReferenceGenerator excepted) | ReplayReferenceGenerator;
     reward_function: None | 'default' | dict of `set_reward` keywords.  Naming either one selects the complete env
     (CompleteBatchedElectricMotorEnv), the other then takes the env id's default (`default_env_modules`); `seed` keys the default
     generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env."""
@@ -678,7 +680,7 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     )
     if reference_generator is None and reward_function is None:
         return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)))
-    from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators
+    from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator
 
     modules = default_env_modules(env_id)
     if reference_generator is None or (isinstance(reference_generator, str) and reference_generator == "default"):
@@ -687,8 +689,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     elif isinstance(reference_generator, (str, type)):
         raise ValueError("reference_generator: 'default', a BatchedWienerProcessReferenceGenerator, a BatchedMultipleReferenceGenerator, generator "
                          "holders (e.g. StepReferenceGenerator(...), or a list of them) or a ReplayReferenceGenerator instance")
-    elif type(reference_generator).__name__ == "SwitchedReferenceGenerator":
-        raise NotImplementedError(SWITCHED_REFUSAL)
+    elif type(reference_generator).__name__ == "SwitchedReferenceGenerator" and not isinstance(reference_generator, _SubGenerator):
+        raise NotImplementedError(SWITCHED_REFUSAL)  # (the reference's own instance; the holder of the same name goes on below)
     elif not isinstance(reference_generator, (_DeviceGenerators, ReplayReferenceGenerator)):
         # holders, a list of them, or the reference's own instances: one handle, columns in state order
         reference_generator = BatchedMultipleReferenceGenerator(reference_generator, seed=kwargs.get("seed", 0))

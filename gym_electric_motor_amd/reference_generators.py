@@ -19,7 +19,8 @@ rewritten in place.  K x `step(done[k-1])` equals `rollout(K, done)` bit for bit
 
 The reference's other generator kinds -- sinusoidal, step, triangular, sawtooth, Laplace process, constant -- are parameter holders named
 after the reference's classes, mixed per state by `BatchedMultipleReferenceGenerator` (MultipleReferenceGenerator's counterpart), on the
-same kernels' handle and with the same surface and invariants:
+same kernels' handle and with the same surface and invariants; `SwitchedReferenceGenerator(holders, p=..., super_episode_length=...)`
+is a holder too: its column runs one of its alternatives per super-episode, the choice being per-env device state:
 
     gen = ga.BatchedMultipleReferenceGenerator([ga.SinusoidalReferenceGenerator(reference_state="i_sd", frequency_range=(5, 50)),
                                                 ga.StepReferenceGenerator(reference_state="i_sq", amplitude_range=(0.1, 0.4))], seed=3)
@@ -376,13 +377,47 @@ class ConstReferenceGenerator(_SubGenerator):
         self.reference_value = float(reference_value)
 
 
+class SwitchedReferenceGenerator(_SubGenerator):
+    """switched_reference_generator.py:11-37: per super-episode of `super_episode_length` steps (a number n: (n, n + 1)) ONE of the
+    alternatives, drawn by `p` (default: uniform), generates the references of its state; the next super-episode's alternative restarts
+    from the value shown last.  sub_generators: holders of the kinds above or the reference's own sub-generator instances as constructed
+    (read as `as_sub_generators` reads them), all for the same state, at most `_lib.MAX_ALT` of them."""
+
+    keywords = ("sub_generators", "p", "super_episode_length")
+
+    def __init__(self, sub_generators, p=None, super_episode_length=(100, 10000)):
+        subs = as_sub_generators(list(sub_generators) if isinstance(sub_generators, (list, tuple)) else [sub_generators])
+        if not subs:
+            raise ValueError("No sub generator was passed.")
+        if any(isinstance(h, SwitchedReferenceGenerator) for h in subs):
+            raise ValueError("the alternatives of a SwitchedReferenceGenerator are generators of the other kinds, not switched ones")
+        states = sorted({h.reference_state for h in subs})
+        if len(states) != 1:  # (the reference asserts it, switched_reference_generator.py:28-30)
+            raise ValueError(f"The passed sub generators have different referenced states: {states}")
+        if len(subs) > _lib.MAX_ALT:
+            raise ValueError(f"at most {_lib.MAX_ALT} alternatives per switched column, not {len(subs)}")
+        self.reference_state = states[0]
+        self.sub_generators = tuple(subs)
+        self.p = tuple(float(x) for x in p) if p is not None and len(p) else (1.0 / len(subs),) * len(subs)
+        if len(self.p) != len(subs):
+            raise ValueError(f"p: one probability per sub generator ({len(subs)}), not {len(self.p)}")
+        if min(self.p) < 0 or abs(sum(self.p) - 1.0) > 1e-9:
+            raise ValueError(f"p: probabilities >= 0 that sum to 1, not {self.p}")
+        if np.ndim(super_episode_length) == 0:
+            super_episode_length = (super_episode_length, super_episode_length + 1)
+        self.super_episode_length = tuple(int(x) for x in _pair(super_episode_length, "super_episode_length"))
+        if self.super_episode_length[0] < 1 or self.super_episode_length[1] <= self.super_episode_length[0]:
+            raise ValueError(f"super_episode_length: 1 <= low < high (the upper bound is excluded), not {self.super_episode_length}")
+
+
 _HOLDERS = {c.__name__: c for c in (WienerProcessReferenceGenerator, LaplaceProcessReferenceGenerator, SinusoidalReferenceGenerator,
                                     StepReferenceGenerator, TriangularReferenceGenerator, SawtoothReferenceGenerator, ConstReferenceGenerator)}
 # the private attributes the reference's instances keep their constructor arguments in -> the holders' keywords
 _REFERENCE_ATTRIBUTES = dict(_reference_state="reference_state", _episode_len_range="episode_lengths", _limit_margin="limit_margin",
                              _sigma_range="sigma_range", _initial_range="initial_range", _amplitude_range="amplitude_range",
                              _frequency_range="frequency_range", _offset_range="offset_range", _reference_value="reference_value")
-SWITCHED_REFUSAL = "SwitchedReferenceGenerator is outside the accelerated path: it switches between whole generators per super-episode, and the device handle fixes one kind per column."
+SWITCHED_REFUSAL = ("SwitchedReferenceGenerator is outside the accelerated path as an instance of the reference: pass the holder "
+                    "ga.SwitchedReferenceGenerator(sub_generators, p=..., super_episode_length=...) with the same arguments instead.")
 
 
 def as_sub_generators(generator):
@@ -416,7 +451,8 @@ def as_sub_generators(generator):
 
 class BatchedMultipleReferenceGenerator(_DeviceGenerators):
     """The batched MultipleReferenceGenerator (multiple_reference_generator.py:9-92) over the reference's sub-episoded and constant
-    generator kinds: one holder per referenced state, any mix of kinds, ONE device handle (gemx_refgen_create_kinds).  The columns follow
+    generator kinds: one holder per referenced state, any mix of kinds, ONE device handle (gemx_refgen_create_kinds; with a
+    SwitchedReferenceGenerator holder among them gemx_refgen_create_switched, whose plain columns keep their bits).  The columns follow
     the state order of the physical system.  Surface and invariants are the Wiener generator's: `reset`, `step`, `rollout`, `bind_step`
     (graph-capturable), `apply_done`; K x step == rollout(K), chunked == one-shot, shards by `env_base`.  A Wiener column draws exactly
     what the same column of a BatchedWienerProcessReferenceGenerator with the same seed draws."""
@@ -444,38 +480,55 @@ class BatchedMultipleReferenceGenerator(_DeviceGenerators):
         self._ordered = tuple(h.reference_state for h in subs)
         self._columns = tuple(subs)
         self._n_envs = ps.n_envs
-        cfg = _lib.GemxRefgenKindsConfig()
-        cfg.struct_size = C.sizeof(_lib.GemxRefgenKindsConfig)
+        switched = any(isinstance(h, SwitchedReferenceGenerator) for h in subs)
+        cfg = _lib.GemxRefgenSwitchedConfig() if switched else _lib.GemxRefgenKindsConfig()
+        cfg.struct_size = C.sizeof(cfg)
         cfg.n_ref = len(subs)
         cfg.seed = self._seed
         cfg.env_base = self._env_base if self._env_base is not None else int(getattr(ps, "env_base", 0))
         cfg.tau = float(ps.tau)
         space_lo, space_hi = [], []
         for j, h in enumerate(subs):
-            cfg.kind[j] = h.kind
-            if h.kind == _lib.REF_CONST:  # its reference space is the single point (const_reference_generator.py:20)
-                cfg.reference_value[j] = h.reference_value
-                space_lo.append(h.reference_value)
-                space_hi.append(h.reference_value)
-                continue
-            cfg.episode_len_lo[j], cfg.episode_len_hi[j] = h.episode_lengths
-            lo, hi = (float(x) for x in _limit_margins(ps, h.reference_state, h.limit_margin))
-            cfg.margin_lo[j], cfg.margin_hi[j] = lo, hi
+            if not switched:
+                lo, hi = self._describe(cfg, j, h, ps)
+            elif not isinstance(h, SwitchedReferenceGenerator):  # a plain column of a switched handle: alternative 0, n_alt = 0
+                lo, hi = self._describe(cfg, j * _lib.MAX_ALT, h, ps)
+            else:  # reference space: the alternatives' lowest low and highest high (switched_reference_generator.py:47-55)
+                cfg.n_alt[j] = len(h.sub_generators)
+                cfg.super_len_lo[j], cfg.super_len_hi[j] = h.super_episode_length
+                spaces = []
+                for a, (alt, prob) in enumerate(zip(h.sub_generators, h.p)):
+                    cfg.p[j * _lib.MAX_ALT + a] = prob
+                    spaces.append(self._describe(cfg, j * _lib.MAX_ALT + a, alt, ps))
+                lo, hi = min(x[0] for x in spaces), max(x[1] for x in spaces)
             space_lo.append(lo)
             space_hi.append(hi)
-            if h.kind in (_lib.REF_WIENER, _lib.REF_LAPLACE):
-                cfg.sigma_lo[j], cfg.sigma_hi[j] = h.sigma_range
-                ir = getattr(h, "initial_range", None)
-                cfg.initial_lo[j], cfg.initial_hi[j] = ir if ir is not None else (lo, hi)  # wiener_process_reference_generator.py:25-28
-            else:  # e.g. sinusoidal_reference_generator.py:40-48: amplitudes within half the margin's width, offsets within the margin
-                cfg.amplitude_lo[j], cfg.amplitude_hi[j] = (float(x) for x in np.clip(h.amplitude_range, 0, (hi - lo) / 2))
-                cfg.offset_lo[j], cfg.offset_hi[j] = (float(x) for x in np.clip(h.offset_range, lo, hi))
-                cfg.frequency_lo[j], cfg.frequency_hi[j] = h.frequency_range
         self._cfg = cfg
+        self._switched = switched
         self._space = (np.array(space_lo, dtype=float), np.array(space_hi, dtype=float))
         if _defer_create:
             return self
-        return self._create(ps, "gemx_refgen_create_kinds", cfg)
+        return self._create(ps, "gemx_refgen_create_switched" if switched else "gemx_refgen_create_kinds", cfg)
+
+    @staticmethod
+    def _describe(cfg, j, h, ps):
+        """Slot j of the config's per-description arrays from the holder h -> its reference space (low, high)."""
+        cfg.kind[j] = h.kind
+        if h.kind == _lib.REF_CONST:  # its reference space is the single point (const_reference_generator.py:20)
+            cfg.reference_value[j] = h.reference_value
+            return h.reference_value, h.reference_value
+        cfg.episode_len_lo[j], cfg.episode_len_hi[j] = h.episode_lengths
+        lo, hi = (float(x) for x in _limit_margins(ps, h.reference_state, h.limit_margin))
+        cfg.margin_lo[j], cfg.margin_hi[j] = lo, hi
+        if h.kind in (_lib.REF_WIENER, _lib.REF_LAPLACE):
+            cfg.sigma_lo[j], cfg.sigma_hi[j] = h.sigma_range
+            ir = getattr(h, "initial_range", None)
+            cfg.initial_lo[j], cfg.initial_hi[j] = ir if ir is not None else (lo, hi)  # wiener_process_reference_generator.py:25-28
+        else:  # e.g. sinusoidal_reference_generator.py:40-48: amplitudes within half the margin's width, offsets within the margin
+            cfg.amplitude_lo[j], cfg.amplitude_hi[j] = (float(x) for x in np.clip(h.amplitude_range, 0, (hi - lo) / 2))
+            cfg.offset_lo[j], cfg.offset_hi[j] = (float(x) for x in np.clip(h.offset_range, lo, hi))
+            cfg.frequency_lo[j], cfg.frequency_hi[j] = h.frequency_range
+        return lo, hi
 
     reference_space = property(lambda self: self._space, doc="(low, high) arrays [n_ref]: the limit margins; a constant column: its value")
 
@@ -495,6 +548,11 @@ class BatchedMultipleReferenceGenerator(_DeviceGenerators):
         torch.cuda.current_stream(self._tdev).synchronize()
         out = dict(value=v, sigma=s, left=l_, kind=kil[0], index=kil[1], length=kil[2])
         out.update(zip(("amplitude", "frequency", "offset", "phase", "width", "roll"), par))
+        if self._switched:  # alternative (its kind is `kind`), super-episode step counter and length, super-episodes drawn so far
+            sw = torch.empty((4,) + n, dtype=torch.int32, device=self._tdev)
+            _lib.check(self._L.gemx_refgen_get_switch_state(self._handle, C.c_void_p(sw.data_ptr()), self._stream()))
+            torch.cuda.current_stream(self._tdev).synchronize()
+            out.update(zip(("alternative", "super_index", "super_length", "n_super"), sw))
         return out
 
 

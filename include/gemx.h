@@ -397,6 +397,54 @@ int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs
  * high/low ratio r), roll.  A handle that runs the all-Wiener kernels does not track index and length: both read -1. */
 int gemx_refgen_get_params(gemx_refgen *r, int32_t *kind_index_len_out_dev, double *params_out_dev, void *stream);
 
+/* SwitchedReferenceGenerator behind the same handle (new struct and entry points only, ABI number unchanged;
+ * reference_generators/switched_reference_generator.py:8-95): a SWITCHED column has n_alt alternatives -- each a complete column
+ * description as in gemx_refgen_kinds_config, for the same referenced state -- and runs one of them per SUPER-EPISODE.  A super-episode
+ * draws its length, integers(super_len_lo, super_len_hi) (upper bound excluded), and its alternative by the probabilities p.  Per
+ * (column, env) the handle keeps the current alternative, the super-episode's step counter sk and length slen and the number of
+ * super-episodes drawn so far, beside the sub-episode state of a gemx_refgen_create_kinds lane.
+ *   reset (gemx_refgen_reset, a done byte): a new super-episode is drawn and the chosen alternative is reset WITHOUT an initial reference
+ *     (WIENER draws its initial value, every other kind restarts from 0).  The next generated value is the alternative's own first value:
+ *     it is not counted in sk and not tested against slen, so the super-episode after a reset shows slen + 1 values, every later one slen
+ *     (the reference's behaviour).  Between the reset and that value sk reads -1.
+ *   step: sk >= slen -> a new super-episode is drawn, sk = 0, and the chosen alternative restarts WITH the value shown last as its initial
+ *     reference (a WIENER or LAPLACE walk continues from it, WIENER draws no initial value); a new sub-episode starts at once and its first
+ *     value is this step's output.  Otherwise the current alternative advances as a plain column does.  Then sk += 1.
+ *   Alternatives that are not current keep no state.  A CONST alternative emits its value and draws nothing.
+ * Random streams: the super-episode draws are Philox blocks of a draw kind of their own, indexed by the lane's super-episode count (word 0:
+ * the length, word 1: the choice by the inverse distribution function of p); the sub-episode, step and reset draws are those of a plain column
+ * and their counters run on across the switches, so no block is used twice.  All keyed by the global env index.
+ * n_alt[g] = 0: column g is PLAIN -- alternative 0 is its description, and it makes the draws and the arithmetic, hence the bits, of
+ * column g of a gemx_refgen_create_kinds handle with the same seed.  A config without a switched column gives exactly that handle (and its
+ * kernels).  Every call that takes a gemx_refgen takes these handles with the same invariants.  Alternative a of column g sits at index
+ * g * GEMX_MAX_ALT + a of the per-alternative arrays.  GEMX_ERR_ARG: n_alt outside [0, GEMX_MAX_ALT], p negative or not summing to 1
+ * within 1e-9, super_len_lo < 1 or super_len_hi <= super_len_lo, and what gemx_refgen_create_kinds refuses, per alternative. */
+#define GEMX_MAX_ALT 5
+typedef struct gemx_refgen_switched_config {
+    int32_t struct_size; /* = sizeof(gemx_refgen_switched_config) */
+    int32_t n_ref;       /* 1..GEMX_MAX_REF columns */
+    uint64_t seed;
+    int64_t env_base;
+    double tau;
+    int32_t n_alt[GEMX_MAX_REF];                                   /* 0: plain column; 1..GEMX_MAX_ALT: switched, that many alternatives */
+    int32_t super_len_lo[GEMX_MAX_REF], super_len_hi[GEMX_MAX_REF]; /* super_episode_length, default (100, 10000) */
+    double p[GEMX_MAX_REF * GEMX_MAX_ALT];                         /* probabilities of the alternatives */
+    int32_t kind[GEMX_MAX_REF * GEMX_MAX_ALT];                     /* per alternative, as in gemx_refgen_kinds_config: */
+    int32_t episode_len_lo[GEMX_MAX_REF * GEMX_MAX_ALT], episode_len_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double margin_lo[GEMX_MAX_REF * GEMX_MAX_ALT], margin_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double sigma_lo[GEMX_MAX_REF * GEMX_MAX_ALT], sigma_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double initial_lo[GEMX_MAX_REF * GEMX_MAX_ALT], initial_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double amplitude_lo[GEMX_MAX_REF * GEMX_MAX_ALT], amplitude_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double frequency_lo[GEMX_MAX_REF * GEMX_MAX_ALT], frequency_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double offset_lo[GEMX_MAX_REF * GEMX_MAX_ALT], offset_hi[GEMX_MAX_REF * GEMX_MAX_ALT];
+    double reference_value[GEMX_MAX_REF * GEMX_MAX_ALT];
+} gemx_refgen_switched_config;
+int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out);
+/* debug / test access to the super-episode state, int32 [4][n_ref][N]: the current alternative, sk, slen, the super-episodes drawn so
+ * far.  A plain column reads 0, 0, 0, 0.  GEMX_ERR_ARG for a handle without a switched column.  On a handle with one,
+ * gemx_refgen_get_params reports the kind of the lane's CURRENT alternative (index and length of a CONST one: -1). */
+int gemx_refgen_get_switch_state(gemx_refgen *r, int32_t *alt_sk_slen_nsuper_out_dev, void *stream);
+
 /* Device-side OBSERVATION STAGE: the observation-side physical-system wrappers of the reference (CurrentSumProcessor,
  * physical_system_wrappers/current_sum_processor.py:40-57; CosSinProcessor, cos_sin_processor.py:52-66), the env shell's state_filter
  * (core.py:273-276, 317, 366) and the flat (state || reference) vector FlattenObservation makes of the shell's Tuple, in ONE pass over the
