@@ -139,6 +139,21 @@ class GemxObsprocConfig(C.Structure):
     ]
 
 
+FLUX_ACT_NONE, FLUX_ACT_SCIM, FLUX_ACT_DFIM = range(3)  # GEMX_FLUX_ACT_*
+
+
+class GemxFluxobsConfig(C.Structure):
+    """Mirror of `gemx_fluxobs_config` (include/gemx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_in", C.c_int32), ("omega_index", C.c_int32), ("current_index", C.c_int32 * 3), ("epsilon_index", C.c_int32),
+        ("action_mode", C.c_int32), ("auto_reset", C.c_int32), ("reserved", C.c_int32),
+        ("omega_limit", C.c_double), ("current_limit", C.c_double * 3), ("epsilon_limit", C.c_double), ("psi_limit", C.c_double),
+        ("p", C.c_double), ("tau", C.c_double), ("k_current", C.c_double), ("k_flux", C.c_double), ("angle_advance", C.c_double),
+        ("reset_omega", C.c_double), ("reset_epsilon", C.c_double),
+    ]
+
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
@@ -148,6 +163,8 @@ EXPORTS = (
     "gemx_obsproc_create", "gemx_obsproc_apply", "gemx_obsproc_destroy",
     "gemx_refgen_rollout_shell", "gemx_reward_rows",
     "gemx_refgen_create_switched", "gemx_refgen_get_switch_state",
+    "gemx_fluxobs_create", "gemx_fluxobs_destroy", "gemx_fluxobs_reset", "gemx_fluxobs_step", "gemx_fluxobs_rows", "gemx_fluxobs_actions",
+    "gemx_fluxobs_get_state", "gemx_fluxobs_set_state",
 )
 
 
@@ -208,6 +225,14 @@ def load():
     L.gemx_obsproc_create.argtypes = [C.POINTER(GemxObsprocConfig), C.c_int, C.c_int, C.POINTER(vp)]
     L.gemx_obsproc_apply.argtypes = [vp, vp, vp, i64, vp, vp]
     L.gemx_obsproc_destroy.argtypes = [vp]
+    L.gemx_fluxobs_create.argtypes = [C.POINTER(GemxFluxobsConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_fluxobs_destroy.argtypes = [vp]
+    L.gemx_fluxobs_reset.argtypes = [vp, vp, vp]
+    L.gemx_fluxobs_step.argtypes = [vp, vp, vp, vp, vp]
+    L.gemx_fluxobs_rows.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.gemx_fluxobs_actions.argtypes = [vp, vp, vp, vp]
+    L.gemx_fluxobs_get_state.argtypes = [vp, vp, vp]
+    L.gemx_fluxobs_set_state.argtypes = [vp, vp, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

@@ -41,9 +41,20 @@ of the six shunt envs), `observed_states=[names]` is the reference's `state_filt
                   physical_system_wrappers=(ga.CosSinProcessor(remove_angle=True),), observed_states=["omega", "i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"])
     obs, _ = env.reset()                                # [N, 5 + 2], ready for the policy
 
+Field-oriented control of the induction machines (flux_observer.py, csrc/gemx_fluxobs.hip): `ga.FluxObserver()` appends `psi_abs` and
+`psi_angle` to the state of a SCIM / DFIM system, `ga.FluxOrientedDqToAbcActionProcessor("SCIM" | "DFIM")` listed after it turns the env's
+actions into (u_d, u_q) pairs in the estimated flux frame.  A step is then four launches: dq -> abc actions, the physics, the observer,
+the observation stage (when it is not the identity).  The K-step rollouts run with a `FluxObserver` and abc actions (physics, then ONE
+pass of the observer over the stored rows, then the stage); with the flux-oriented action processor they raise: each step's angle depends
+on the previous step's observation.
+
+    env = ga.make("Cont-CC-SCIM-v0", n_envs=4096, physical_system_wrappers=(ga.FluxObserver(), ga.FluxOrientedDqToAbcActionProcessor("SCIM")))
+    state, _ = env.reset()                              # [N, 14 + 2]
+    state, _, terminated, _, _ = env.step(dq_actions)   # dq_actions [N, 2]
+
 Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the noisy state, which
-the fused kernels cannot reproduce in a post-pass), `FluxObserver`, reward weights or constraints on appended columns (`i_sum`,
-`cos(...)`) and visualisation; an instance of the reference's own `SwitchedReferenceGenerator` is refused (pass the holder of that
+the fused kernels cannot reproduce in a post-pass), reward weights or constraints on appended columns (`i_sum`,
+`cos(...)`, `psi_abs`, `psi_angle`) and visualisation; an instance of the reference's own `SwitchedReferenceGenerator` is refused (pass the holder of that
 name).  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
 `physical_system=` to the reference's own `ElectricMotorEnvironment`.
 """
@@ -227,8 +238,9 @@ def default_ode_solver(env_id, tau=None, load=None):
 class BatchedElectricMotorEnv:
     """Vector-env style shell around a batched physical system (physics + done mask only)."""
 
-    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False):
-        """observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
+    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None):
+        """flux_action: None | 'SCIM' | 'DFIM' -- the flux-oriented dq action processor (needs a FluxObserver in the observation chain).
+        observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
         `step()` and `rollout()` then return the PROCESSED state, `state_space` / `state_names` describe it; `physical_system` stays raw."""
         self.physical_system = physical_system
         self.action_space = physical_system.action_space
@@ -236,21 +248,88 @@ class BatchedElectricMotorEnv:
         self.state_names = list(physical_system.state_names)
         self.n_envs = physical_system.n_envs
         self.observation_stage = None
-        self._raw_scratch = None
+        self._raw_scratch = self._ext_scratch_buf = None
+        self.flux, self.flux_action, self._flux_only = None, None, False
+        if flux_action and observation is None:
+            raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
         if observation is not None:
             from .observation import ObservationStage
 
             if getattr(physical_system, "_obs_layout", "aos") != "aos":
                 raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
             stage = ObservationStage(physical_system, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
-                                     n_ref=_n_ref)
+                                     n_ref=_n_ref, flux_action=flux_action)
             self.observation_stage = stage
             self.state_space = stage.observation_space
             self.state_names = list(stage.observation_names)
-            if not _defer_create:
+            self._init_flux(stage, flux_action, _defer_create)
+            if not _defer_create and not self._flux_only:
                 ps = physical_system
                 stage.create(ps._device, ps._dtype_name)
                 self._pstate = bps._torch().empty((ps.n_envs, stage.n_post), dtype=ps._tdtype, device=ps._tdev)
+
+    def _init_flux(self, stage, flux_action, _defer_create):
+        """The flux-observer stage of the observation chain, if there is one: its handle, the extended row buffer `_ext [N, n_base + 2]`
+        and, with the flux-oriented action processor, the env's dq action space and the abc scratch `_abc [N, 3 | 6]`."""
+        self.flux = stage.flux
+        self.flux_action = flux_action
+        self._flux_only = self.flux is not None and stage.is_identity  # (the extended row IS the observation: no column program to run)
+        if self.flux is None:
+            return
+        ps = self.physical_system
+        if flux_action:
+            if ps._cfg.init_kind != bps._lib.INIT_CONST:
+                raise NotImplementedError("random initial states together with the flux-oriented dq action processor are not on the accelerated path: "
+                                          "the frame of the first action after a reset comes from the reset observation, which would not be a constant")
+            self.action_space = Box(-1, 1, shape=(self.flux.n_action,), dtype=np.float64)
+        if _defer_create:
+            return
+        torch = bps._torch()
+        self.flux.set_reset_observation(ps.reset_observation)
+        self.flux.create(ps.n_envs, ps._device, ps._dtype_name)
+        self._ext = torch.zeros((ps.n_envs, self.flux.n_in + 2), dtype=ps._tdtype, device=ps._tdev)
+        if flux_action:
+            self._abc = torch.zeros((ps.n_envs, self.flux.n_action * 3 // 2), dtype=ps._tdtype, device=ps._tdev)
+
+    def _flux_reset(self):
+        """The observer's reset and the extended reset rows: the system's, then [0, 0] (flux_observer.py:80-83)."""
+        self.flux.reset()
+        nb = self.flux.n_in
+        self._ext[:, :nb].copy_(self.physical_system._obs)
+        self._ext[:, nb:].zero_()
+
+    def _dq_to_device(self, actions):
+        """-> contiguous device tensor [N, 2 | 4] of the dq actions."""
+        ps, torch = self.physical_system, bps._torch()
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions, dtype=np.float64))
+        return actions.to(device=ps._tdev, dtype=ps._tdtype).reshape(ps.n_envs, self.flux.n_action).contiguous()
+
+    def _ext_scratch(self, K):
+        ps = self.physical_system
+        shape = (K, ps.n_envs, self.flux.n_in + 2)
+        if self._ext_scratch_buf is None or tuple(self._ext_scratch_buf.shape) != shape:
+            self._ext_scratch_buf = bps._torch().empty(shape, dtype=ps._tdtype, device=ps._tdev)
+        return self._ext_scratch_buf
+
+    def _refuse_flux_rollout(self):
+        if self.flux_action:
+            from .flux_observer import ROLLOUT_REFUSAL
+
+            raise NotImplementedError(ROLLOUT_REFUSAL)
+
+    def get_checkpoint(self):
+        """`physical_system.get_checkpoint()`, plus the flux observer's per-env state (`flux_observer`: float64 [4, N]) when the env has one."""
+        ck = self.physical_system.get_checkpoint()
+        if self.flux is not None:
+            ck["flux_observer"] = self.flux.get_state()
+        return ck
+
+    def set_checkpoint(self, ckpt):
+        """Restore `get_checkpoint()` of an env of the same configuration: the next `step()` continues bit for bit."""
+        self.physical_system.set_checkpoint(ckpt)
+        if self.flux is not None:
+            self.flux.set_state(ckpt["flux_observer"])
 
     @property
     def unwrapped(self):
@@ -258,18 +337,27 @@ class BatchedElectricMotorEnv:
 
     def _processed(self, raw):
         """The stage on the system's internal state buffer (n_envs == 1 with numpy in / out keeps numpy)."""
-        self.observation_stage.apply(self.physical_system._obs, out=self._pstate)
+        out = self._ext if self._flux_only else self.observation_stage.apply(self._ext if self.flux is not None else self.physical_system._obs, out=self._pstate)
         if isinstance(raw, np.ndarray):
-            return self._pstate.reshape(-1).double().cpu().numpy()
-        return self._pstate
+            return out.reshape(-1).double().cpu().numpy()
+        return out
 
-    def _processed_trajectory(self, raw, obs_out=None):
+    def _processed_trajectory(self, raw, obs_out=None, done=None):
+        if self.flux is not None:  # ONE pass of the observer over the stored rows, then the column program (unless it is the identity)
+            if raw.dim() != 3:
+                raise NotImplementedError("last_only rollouts cannot carry a FluxObserver: its recursion needs every row")
+            raw = self.flux.rows(raw, done, out=obs_out if self._flux_only else self._ext_scratch(int(raw.shape[0])))
+            if self._flux_only:
+                return raw
         return self.observation_stage.apply(raw, out=obs_out)
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state; returns (observations, {})."""
         if self.observation_stage is not None:
-            return self._processed(self.physical_system.reset()), {}
+            raw = self.physical_system.reset()
+            if self.flux is not None:
+                self._flux_reset()
+            return self._processed(raw), {}
         return self.physical_system.reset(), {}
 
     def step(self, actions, references=None):
@@ -277,23 +365,25 @@ class BatchedElectricMotorEnv:
         installed (`physical_system.set_reward`) and `references [N, n_ref]` are passed, else None.  With auto_reset (default for
         n_envs > 1) an env that terminated restarts from the reset state on its next step; the state it shows
         right after that restart is `physical_system.reset_observation`."""
-        if references is not None:
-            obs = self.physical_system.simulate(actions, references=references)
-            if self.observation_stage is not None:
-                obs = self._processed(obs)
-            return obs, self.physical_system.reward, self.physical_system.done, False, {}
-        obs = self.physical_system.simulate(actions)
+        ps = self.physical_system
+        if self.flux_action:  # launch 1 of 4: the dq actions rotated into the frame the last observation left
+            self.flux.bind_actions(self._dq_to_device(actions), self._abc)()
+            actions = self._abc
+        obs = ps.simulate(actions, references=references) if references is not None else ps.simulate(actions)
+        if self.flux is not None:
+            self.flux.step(ps._obs, ps._done, self._ext)
         if self.observation_stage is not None:
             obs = self._processed(obs)
-        return obs, None, self.physical_system.done, False, {}
+        return obs, (ps.reward if references is not None else None), ps.done, False, {}
 
     def rollout(self, actions, obs_out=None, **kw):
         """PhysicalSystem.rollout; with an observation stage the raw trajectory goes into a scratch tensor and ONE `apply` writes the
         processed `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
+        self._refuse_flux_rollout()
         if self.observation_stage is None:
             return self.physical_system.rollout(actions, obs_out=obs_out, **kw)
         res = self.physical_system.rollout(actions, obs_out=self._scratch(int(actions.shape[0]), kw.get("last_only", False)), **kw)
-        return (self._processed_trajectory(res[0], obs_out),) + tuple(res[1:])
+        return (self._processed_trajectory(res[0], obs_out, res[1]),) + tuple(res[1:])
 
     def _scratch(self, K, last_only=False):
         ps = self.physical_system
@@ -304,26 +394,35 @@ class BatchedElectricMotorEnv:
 
     def rollout_synthetic(self, K, obs_out=None, **kw):
         """K fused steps on random actions generated on the device (PhysicalSystem.rollout_synthetic)."""
+        self._refuse_flux_rollout()
         if self.observation_stage is None:
             return self.physical_system.rollout_synthetic(K, obs_out=obs_out, **kw)
         res = self.physical_system.rollout_synthetic(K, obs_out=self._scratch(K), **kw)
-        return (self._processed_trajectory(res[0], obs_out),) + tuple(res[1:])
+        return (self._processed_trajectory(res[0], obs_out, res[1]),) + tuple(res[1:])
 
     def bind_rollout(self, actions, obs_out, done_out, stream=None):
         """-> zero-argument launch(): the pre-bound `gemx_rollout` call for fixed tensors (PhysicalSystem.bind_rollout); with an
         observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus one `apply`."""
+        self._refuse_flux_rollout()
         if self.observation_stage is None:
             return self.physical_system.bind_rollout(actions, obs_out, done_out, stream=stream)
         ps = self.physical_system
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
         raw = self._scratch(int(actions.shape[0]))
         physics = ps.bind_rollout(actions, raw, done_out, stream=stream)
-        post = self.observation_stage.bind_apply(raw, None, obs_out, stream)
+        observer, src = None, raw
+        if self.flux is not None:
+            src = obs_out if self._flux_only else self._ext_scratch(int(actions.shape[0]))
+            observer = self.flux.bind_rows(raw, done_out, src, stream)
+        post = None if self._flux_only else self.observation_stage.bind_apply(src, None, obs_out, stream)
         out = (obs_out, done_out)
 
         def launch():
             physics()
-            post()
+            if observer is not None:
+                observer()
+            if post is not None:
+                post()
             return out
 
         return launch
@@ -331,6 +430,8 @@ class BatchedElectricMotorEnv:
     def close(self):
         if self.observation_stage is not None:
             self.observation_stage.close()
+        if self.flux is not None:
+            self.flux.close()
         self.physical_system.close()
 
 
@@ -345,8 +446,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     _REWARD_KEYS = ("reward_weights", "gamma", "reward_power", "bias", "violation_reward", "normed_reward_weights")
 
-    def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None):
+    def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None,
+                 flux_action=None):
         super().__init__(physical_system)
+        if flux_action and observation is None:
+            raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
         ps = physical_system
         if observation is not None and getattr(ps, "_obs_layout", "aos") != "aos":
             raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
@@ -379,9 +483,10 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             from .observation import ObservationStage
 
             stage = ObservationStage(ps, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
-                                     n_ref=len(self.reference_names))
+                                     n_ref=len(self.reference_names), flux_action=flux_action)
             self.state_space = stage.observation_space
             self.state_names = list(stage.observation_names)
+            self._init_flux(stage, flux_action, _defer_create)
         self.observation_stage = stage
         self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
         if stage is not None and stage.flatten:  # FlattenObservation of that Tuple: one box, state then reference
@@ -395,14 +500,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps._reward_buf = self._reward  # (`physical_system.reward` shows the same buffer)
         self._refs = gen.references
         self._obs = (ps._obs, self._refs)
-        if stage is not None:
+        if stage is not None and self._flux_only:
+            self._obs = (self._ext, self._refs)
+        elif stage is not None:
             stage.create(ps._device, ps._dtype_name)
             self._pstate = torch.empty((ps.n_envs, stage.n_out), dtype=ps._tdtype, device=ps._tdev)
             self._obs = self._pstate if stage.flatten else (self._pstate, self._refs)
 
     def _stage_launcher(self, stream):
-        """The third launch of a step: the observation stage on the fresh state rows and the references the generators just wrote."""
-        return self.observation_stage.bind_apply(self.physical_system._obs, self._refs, self._pstate, stream)
+        """The last launch of a step: the observation stage on the fresh state rows (the flux observer's extended rows, if there is one) and
+        the references the generators just wrote; None when the extended row is the observation."""
+        if self._flux_only:
+            return None
+        return self.observation_stage.bind_apply(self._ext if self.flux is not None else self.physical_system._obs, self._refs, self._pstate, stream)
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state, all generators restarted and advanced once (core.py:312-313, 485-505).
@@ -411,11 +521,13 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps.reset()
         gen.reset()
         gen.step(None)
-        if self.observation_stage is not None:
-            self.observation_stage.apply(ps._obs, self._refs, out=self._pstate)
+        if self.flux is not None:
+            self._flux_reset()
+        if self.observation_stage is not None and not self._flux_only:
+            self.observation_stage.apply(self._ext if self.flux is not None else ps._obs, self._refs, out=self._pstate)
         return self._obs, {}
 
-    def _launchers(self, action_ptr, stream):
+    def _launchers(self, action_ptr, stream, dq=None):
         """The two launches of a step with everything resolved: physics + fused reward reading the generator's buffer, then the
         generator step on the fresh done mask writing that same buffer."""
         import ctypes as C
@@ -423,6 +535,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps, gen = self.physical_system, self.reference_generator
         L, check = ps._L, bps._lib.check
         n_ref = int(self.reward_config.n_ref)
+        to_abc = observer = None
+        if self.flux_action:  # dq [N, 2 | 4] -> the abc scratch the physics reads
+            to_abc, action_ptr = self.flux.bind_actions(dq, self._abc, stream), self._abc.data_ptr()
+        if self.flux is not None:
+            observer = self.flux.bind_step(ps._obs, ps._done, self._ext, stream)
         args = (C.c_void_p(action_ptr), 1, C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr),
                 C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
         gen_step = gen.bind_step(ps._done, stream=stream)
@@ -431,15 +548,20 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
             def gen_step():
                 gen_only()
-                post()
+                if post is not None:
+                    post()
 
         call = L.gemx_rollout_reward
 
         def physics(_args=args, _call=call):
+            if to_abc is not None:
+                to_abc()
             rc = _call(ps._handle, *_args)
             if rc:
                 check(rc)
             ps._k += 1
+            if observer is not None:
+                observer()
 
         return physics, gen_step
 
@@ -450,11 +572,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             raise TypeError("the complete env generates its references: step(actions)")
         ps = self.physical_system
         torch = bps._torch()
-        a = ps._actions_to_device(actions, (ps._n_envs,))
+        a = self._dq_to_device(actions) if self.flux_action else ps._actions_to_device(actions, (ps._n_envs,))
         stream = torch.cuda.current_stream(ps._tdev)
         key = (a.data_ptr(), stream.cuda_stream)
         if self._bound is None or self._bound[0] != key:  # (a loop that reuses its action tensor and stream resolves the launches once)
-            self._bound = (key, self._launchers(a.data_ptr(), stream), a, stream)
+            self._bound = (key, self._launchers(a.data_ptr(), stream, a), a, stream)
         physics, gen_step = self._bound[1]
         physics()
         gen_step()
@@ -468,10 +590,13 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps = self.physical_system
         torch = bps._torch()
         a = action_buffer
-        if not (torch.is_tensor(a) and a.device == ps._tdev and a.is_contiguous() and a.dtype is ps._want_dtype and a.numel() == ps._act_numel):
-            raise ValueError(f"bind_step needs a contiguous {ps._want_dtype} tensor of {ps._act_numel} elements on {ps._tdev}")
+        numel = ps._n_envs * self.flux.n_action if self.flux_action else ps._act_numel
+        if not (torch.is_tensor(a) and a.device == ps._tdev and a.is_contiguous() and a.dtype is ps._want_dtype and a.numel() == numel):
+            raise ValueError(f"bind_step needs a contiguous {ps._want_dtype} tensor of {numel} elements on {ps._tdev}")
+        if self.flux_action:
+            a = a.view(ps._n_envs, self.flux.n_action)
         stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
-        physics, gen_step = self._launchers(a.data_ptr(), stream)
+        physics, gen_step = self._launchers(a.data_ptr(), stream, a)
         obs = self._obs
 
         def step(_keep=(a, stream)):
@@ -492,6 +617,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
     def _check_complete(self, what, K, actions=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
         """bind_rollout-style validation (K, then per tensor: dtype, shape, contiguity, device) -> K.  Needs no device: it runs
         before anything is launched, and on an env whose handles were never created."""
+        self._refuse_flux_rollout()
         torch = bps._torch()
         ps = self.physical_system
         tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
@@ -546,7 +672,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         stream = torch.cuda.current_stream(ps._tdev)             # 3. reward of row k against the references shown before step k
         bps._lib.check(ps._L.gemx_reward_rows(ps._handle, *self._reward_rows_args(raw, refs, done_out, reward_out, K, stream)))
         if stage is not None:
-            stage.apply(raw, refs, out=state_out)
+            src = raw
+            if self.flux is not None:  # ONE pass of the observer over the stored rows
+                src = self.flux.rows(raw, done_out, out=state_out if self._flux_only else self._ext_scratch(K))
+            if not self._flux_only:
+                stage.apply(src, refs, out=state_out)
         self._refs.copy_(refs[K - 1])  # (after the reward pass has read the old ones: step() and further rollouts continue from row K-1)
         return state_out, refs, reward_out, done_out
 
@@ -596,7 +726,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
         args = self._reward_rows_args(raw, refs_out, done_out, reward_out, K, stream)
         call = L.gemx_reward_rows
-        post = stage.bind_apply(raw, refs_out, state_out, stream) if stage is not None else None
+        observer, src = None, raw
+        if self.flux is not None:
+            src = state_out if self._flux_only else self._ext_scratch(K)
+            observer = self.flux.bind_rows(raw, done_out, src, stream)
+        post = stage.bind_apply(src, refs_out, state_out, stream) if stage is not None and not self._flux_only else None
         shown, last = self._refs, refs_out[K - 1]
         current, on = torch.cuda.current_stream, torch.cuda.stream
         out = (state_out, refs_out, reward_out, done_out)
@@ -608,6 +742,8 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             rc = _call(ps._handle, *_args)
             if rc:
                 check(rc)
+            if observer is not None:
+                observer()
             if post is not None:
                 post()
             if current(ps._tdev) == stream:  # the references shown last: one device-to-device copy on the launch stream
@@ -630,7 +766,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     """Build a batched env.  Component arguments follow the reference's env-arg convention (instance | dict | None).
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
     (or the reference's own instances), which are folded into the kernel's action stage, and of CurrentSumProcessor / CosSinProcessor
-    holders, which become the device-side observation stage; 'default': `default_physical_system_wrappers(env_id)`.
+    holders, which become the device-side observation stage, and of FluxObserver / FluxOrientedDqToAbcActionProcessor holders (induction
+    machines: the flux-observer stage); 'default': `default_physical_system_wrappers(env_id)`.
     observed_states: None | list of state names of the wrapped system -- the reference's `state_filter`, applied last.
     flatten_observation: the complete env hands out ONE tensor [N, n_post + n_ref], the processed state followed by the references.
     reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
@@ -649,8 +786,11 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
             raise ValueError("physical_system_wrappers: a tuple of wrapper holders or 'default'")
         physical_system_wrappers = default_physical_system_wrappers(env_id)
     chain = []
+    flux_action = None
     if physical_system_wrappers:
-        kwargs = dict(kwargs, **fold_wrappers(physical_system_wrappers, observation_chain=chain))
+        folded = fold_wrappers(physical_system_wrappers, observation_chain=chain)
+        flux_action = folded.pop("flux_action", None)  # (served by the flux-observer stage, not by the system's action stage)
+        kwargs = dict(kwargs, **folded)
     observation = None
     if chain or observed_states is not None or flatten_observation:
         if obs_layout != "aos":
@@ -679,7 +819,7 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         **kwargs,
     )
     if reference_generator is None and reward_function is None:
-        return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)))
+        return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)), flux_action=flux_action)
     from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator
 
     modules = default_env_modules(env_id)
@@ -697,4 +837,4 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     if not (reward_function is None or isinstance(reward_function, dict) or (isinstance(reward_function, str) and reward_function == "default")):
         raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
     return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,
-                                           _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation)
+                                           _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation, flux_action=flux_action)

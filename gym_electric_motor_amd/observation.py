@@ -12,6 +12,12 @@ and gymnasium's FlattenObservation do to a state, as ONE kernel launch over the 
   of a bit mask, cos / sin of pi times a column.  The program is one level deep: a processor whose source is itself a derived column
   (`CosSinProcessor(angle='i_sum')`, a current sum over another `i_sum`) is refused by name.
 
+A `FluxObserver` in the chain (`('flux', wrapper)`; induction machines) is a stage of its own IN FRONT of the program (flux_observer.py,
+csrc/gemx_fluxobs.hip): it extends the system's row by `psi_abs` and `psi_angle`, and the program then runs over that extended row of
+`n_in = n_base + 2` columns -- `CosSinProcessor(angle='psi_angle')`, `observed_states=` and `flatten` work as for any other column, at any
+position of the chain.  The observer's own sources (its three currents) must be columns of the base system.  `stage.flux` is the
+`FluxObserverStage`; `evaluate(state [K, (N,) n_base], done=...)` runs its float64 recursion first (stateful over the trajectory).
+
 `remove_angle=True`: the reference's CosSinProcessor deletes the angle in `simulate()` but forgets to in `reset()`
 (cos_sin_processor.py:52-55 against 57-62), so its reset state is one column longer than its step state and than its own state space.
 A batched tensor has one shape: the stage uses `simulate()`'s -- the shape the wrapper's `state_space`, `state_names` and `limits`
@@ -48,10 +54,11 @@ def _source(col, what):
 class ObservationStage:
     """The resolved observation stage of one physical system (see the module docstring)."""
 
-    def __init__(self, physical_system, chain=(), observed_states=None, flatten=False, n_ref=0):
+    def __init__(self, physical_system, chain=(), observed_states=None, flatten=False, n_ref=0, flux_action=None):
         ps = physical_system
         names = [str(n) for n in ps.state_names]
-        self.n_in = len(names)
+        self.n_in = self.n_base = len(names)
+        self.flux = None
         self.n_ref = int(n_ref)
         self.flatten = bool(flatten)
         if not 0 <= self.n_ref <= _lib.MAX_REF:
@@ -82,8 +89,27 @@ class ObservationStage:
                 cols.append(_Column(f"cos({angle})", "cospi", src, 0, 1.0, 1.0, -1.0, 1.0))
                 cols.append(_Column(f"sin({angle})", "sinpi", src, 0, 1.0, 1.0, -1.0, 1.0))
                 positions = {c.name: j for j, c in enumerate(cols)}
+            elif spec[0] == "flux":
+                from .flux_observer import FluxObserverStage
+
+                probe = FluxObserverStage(ps, action_mode=flux_action)  # (the motor check: before any attribute of the wrapper is read)
+                currents = tuple(getattr(spec[1], "_current_names", ("i_sa", "i_sb", "i_sc")))
+                idx = []
+                for c in currents:
+                    src = _source(cols[positions[c]], f"FluxObserver({list(currents)})")  # (KeyError for an unknown name, as flux_observer.py:70)
+                    if src >= self.n_base:
+                        raise ValueError(f"FluxObserver({list(currents)}): its source {c!r} is not a state of the base physical system")
+                    idx.append(src)
+                self.flux = FluxObserverStage(ps, currents, action_mode=flux_action, current_indices=idx)
+                del probe
+                for j, (name, limit, nominal, lo, hi) in enumerate(self.flux.columns):
+                    cols.append(_Column(name, "copy", self.n_base + j, 0, limit, nominal, lo, hi))
+                self.n_in = self.n_base + 2
+                positions = {c.name: j for j, c in enumerate(cols)}
             else:
                 raise ValueError(f"unknown observation-stage spec {spec!r}")
+        if flux_action and self.flux is None:
+            raise ValueError("the flux-oriented dq action processor needs a FluxObserver in the chain")
         # the wrapped system's metadata
         self.state_names = [c.name for c in cols]
         self.state_positions = positions
@@ -101,9 +127,13 @@ class ObservationStage:
         self.n_post = len(self._cols)
         if self.n_post > _lib.OBS_MAX_POST:
             raise ValueError(f"the observation has {self.n_post} columns, the device-side stage at most {_lib.OBS_MAX_POST}")
-        if self.n_in > _lib.MAX_OUT:
-            raise ValueError(f"the physical system has {self.n_in} states, the device-side stage reads at most {_lib.MAX_OUT}")
+        if self.n_base > _lib.MAX_OUT:
+            raise ValueError(f"the physical system has {self.n_base} states, the device-side stage reads at most {_lib.MAX_OUT}")
         self.n_out = self.n_post + (self.n_ref if self.flatten else 0)
+        if self.n_in > _lib.MAX_OUT and not (not self.flatten and self.n_post == self.n_in and all(c.op == "copy" and c.src == j for j, c in enumerate(self._cols))):
+            raise NotImplementedError(f"the column program reads rows of at most {_lib.MAX_OUT} columns (gemx_obsproc_create); the flux observer's extended "
+                                      f"row of this system has {self.n_in}: it can be handed out as it is, but not processed further (CosSinProcessor, "
+                                      "observed_states, flatten_observation)")
         self.program = [(c.op, c.src, c.mask) for c in self._cols]
         self._cfg = self._build_config()
         self._handle = None
@@ -121,9 +151,12 @@ class ObservationStage:
         return cfg
 
     # ------------------------------------------------------------------ host-side evaluator
-    def evaluate(self, state, refs=None, dtype=np.float64):
+    def evaluate(self, state, refs=None, dtype=np.float64, done=None):
         """The program in numpy on `state [..., n_in]` (computed in `dtype`; sums sequentially in ascending column order, as the kernel
-        adds them) -> [..., n_post], or with `flatten` [..., n_post + n_ref]."""
+        adds them) -> [..., n_post], or with `flatten` [..., n_post + n_ref].  With a FluxObserver, rows of the BASE system
+        `[K, (N,) n_base]` first go through its float64 recursion (`done [K, (N)]`: the lanes reset after that row)."""
+        if self.flux is not None and np.shape(state)[-1] == self.n_base:
+            state = self.flux.evaluate(state, done)
         s = np.asarray(state, dtype=dtype)
         if s.shape[-1] != self.n_in:
             raise ValueError(f"state has {s.shape[-1]} columns, the stage reads {self.n_in}")

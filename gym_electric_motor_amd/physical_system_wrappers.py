@@ -13,11 +13,19 @@ kernel (csrc/gemx_obsproc.hip) that reads the state rows the stepping kernels wr
     CurrentSumProcessor(currents[, limit])          physical_system_wrappers/current_sum_processor.py:7-65
     CosSinProcessor([angle][, remove_angle])        physical_system_wrappers/cos_sin_processor.py:7-89
 
+FLUX OBSERVER (induction machines), a stage of its own between the two (flux_observer.py, csrc/gemx_fluxobs.hip): one launch behind
+`simulate()` appends `psi_abs` and `psi_angle` to the row, keeps the flux estimate per env and the frame of the NEXT action; with
+`FluxOrientedDqToAbcActionProcessor` one launch in front of `simulate()` rotates the dq actions by that frame.
+
+    FluxObserver([current_names])                   physical_system_wrappers/flux_observer.py:9-102
+    FluxOrientedDqToAbcActionProcessor(motor_type)  physical_system_wrappers/dq_to_abc_action_processor.py:91-148 ('SCIM', 'DFIM')
+
 As in the reference, wrappers are applied innermost first: `(DeadTimeProcessor(2), DqToAbcActionProcessor.make("PMSM"))`
 delays the abc action by two steps and lets the dq processor advance its angle by 0.5 + 2 steps (lines 83-86); an observation-side
 processor sees the state names of everything listed before it.  The two sides do not interact, so they may be listed in any order.
+The flux-oriented processor reads the observer's angle: it must be listed after a `FluxObserver` and after any `DeadTimeProcessor`.
 Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the NOISY state,
-core.py:344-350, and those are fused into the stepping kernels) and `FluxObserver`.
+core.py:344-350, and those are fused into the stepping kernels).
 """
 
 
@@ -60,15 +68,43 @@ def _reset_action_row(w):
 
 class DqToAbcActionProcessor:
     """(u_d, u_q[, u_e]) actions -> abc converter actions with the Park angle advanced by (0.5 + dead time) * tau * omega * p.
-    Motor types 'PMSM' (any SynchronousMotorSystem) and 'EESM'.  The reference's 'SCIM' / 'DFIM' variants read a
-    'psi_angle' state that only a FluxObserver wrapper provides (observation post-processing: not on the accelerated path)."""
+    Motor types 'PMSM' (any SynchronousMotorSystem) and 'EESM': folded into the stepping kernel's action stage.  The reference's
+    'SCIM' / 'DFIM' variants read a 'psi_angle' state that only a FluxObserver wrapper provides: they are a holder of their own,
+    `FluxOrientedDqToAbcActionProcessor`, served by the flux-observer stage."""
 
     _SUPPORTED = ("PMSM", "EESM")
 
     def __init__(self, motor_type="PMSM"):
         if motor_type not in self._SUPPORTED:
-            raise NotImplementedError(f"DqToAbcActionProcessor for {motor_type!r} needs a flux observer; supported on the accelerated "
-                                      f"path: {self._SUPPORTED}")
+            raise NotImplementedError(f"DqToAbcActionProcessor for {motor_type!r} needs a flux observer; folded into the kernel's "
+                                      f"action stage: {self._SUPPORTED}; for 'SCIM' / 'DFIM' list FluxOrientedDqToAbcActionProcessor(motor_type) "
+                                      "after a FluxObserver()")
+        self.motor_type = motor_type
+
+    @classmethod
+    def make(cls, motor_type, *args, **kwargs):
+        return cls(motor_type)
+
+
+class FluxObserver:
+    """Appends the estimated rotor flux of an induction machine, `psi_abs` and `psi_angle`, to the state vector (flux_observer.py:9-48):
+    an explicit Euler integration of the current model, once per control step, from the three named stator currents and omega."""
+
+    def __init__(self, current_names=("i_sa", "i_sb", "i_sc"), physical_system=None):
+        self._current_names = tuple(current_names)
+
+
+class FluxOrientedDqToAbcActionProcessor:
+    """The reference's `DqToAbcActionProcessor.make('SCIM')` / `.make('DFIM')` (dq_to_abc_action_processor.py:91-148): (u_d, u_q) actions
+    rotated by psi_angle + (0.5 + dead time) * tau * omega * p; 'DFIM' takes four actions, the stator pair rotated by epsilon + that
+    advance, the rotor pair by psi_angle minus the stator's angle.  Must be listed after a `FluxObserver` and after any
+    `DeadTimeProcessor`.  Fused K-step rollouts refuse it: each step's angle depends on the previous step's observation."""
+
+    _SUPPORTED = ("SCIM", "DFIM")
+
+    def __init__(self, motor_type="SCIM"):
+        if motor_type not in self._SUPPORTED:
+            raise ValueError(f"FluxOrientedDqToAbcActionProcessor serves {self._SUPPORTED}, not {motor_type!r} (DqToAbcActionProcessor: 'PMSM', 'EESM')")
         self.motor_type = motor_type
 
     @classmethod
@@ -105,7 +141,10 @@ STATE_NOISE_REFUSAL = ("StateNoiseProcessor is not on the accelerated path: the 
 
 
 def _observation_spec(w, names):
-    """('sum', currents, 'max' | 'sum') | ('cossin', angle, remove_angle) | None for an observation-side wrapper (holder or the reference's instance)."""
+    """('sum', currents, 'max' | 'sum') | ('cossin', angle, remove_angle) | ('flux', wrapper) | None for an observation-side wrapper (holder or
+    the reference's instance).  A FluxObserver travels as it is: ObservationStage checks the motor before it reads any attribute."""
+    if "FluxObserver" in names:
+        return ("flux", w)
     if "CurrentSumProcessor" in names:
         limit = getattr(w, "_limit_name", None)
         if limit is None:  # the reference's instance keeps the function: `max` or `np.sum`
@@ -116,18 +155,42 @@ def _observation_spec(w, names):
     return None
 
 
+def _flux_action_kind(w, names):
+    """'SCIM' | 'DFIM' for a dq processor that reads the flux observer's angle (this module's holder, the reference's
+    _ClassicDqToAbcActionProcessor with _angle_name == 'psi_angle', its _DFIMDqToAbcActionProcessor), else None."""
+    if "FluxOrientedDqToAbcActionProcessor" in names:
+        return w.motor_type
+    if "_DFIMDqToAbcActionProcessor" in names:
+        return "DFIM"
+    if "DqToAbcActionProcessor" in names and getattr(w, "_angle_name", "epsilon") == "psi_angle":
+        return "SCIM"
+    return None
+
+
 def fold_wrappers(wrappers, observation_chain=None):
     """-> dict(action_delay=..., action_frame=...[, action_delay_reset=...]) for BatchedSCMLSystem from a reference-style wrapper tuple (innermost first).
     Accepts this module's holders and the reference's own instances (by class name).  The observation-side processors
-    (CurrentSumProcessor, CosSinProcessor), in any position, are appended to the list `observation_chain` as specs for
+    (CurrentSumProcessor, CosSinProcessor, FluxObserver), in any position, are appended to the list `observation_chain` as specs for
     `observation.ObservationStage`, innermost first; without such a list they are refused like any other wrapper the kernels' action stage
     cannot hold."""
     delay, frame, seen_dq, reset_row = 0, None, False, None  # frame None: leave it to the system's control_space
+    seen_flux, flux_action = False, None
     for w in wrappers:
         names = {c.__name__ for c in type(w).__mro__}
         spec = _observation_spec(w, names)
+        flux_kind = _flux_action_kind(w, names)
         if spec is not None and observation_chain is not None:
+            if spec[0] == "flux":
+                if seen_flux:
+                    raise ValueError("one FluxObserver per system")
+                if flux_action:
+                    raise ValueError("the FluxObserver must be listed BEFORE the flux-oriented dq action processor, which reads its psi_angle")
+                seen_flux = True
             observation_chain.append(spec)
+        elif flux_kind is not None and seen_flux:
+            if seen_dq:
+                raise ValueError("one dq action processor per system")
+            flux_action, seen_dq = flux_kind, True
         elif "StateNoiseProcessor" in names:
             raise NotImplementedError(STATE_NOISE_REFUSAL)
         elif "DeadTimeProcessor" in names:
@@ -139,6 +202,8 @@ def fold_wrappers(wrappers, observation_chain=None):
                 raise NotImplementedError("several DeadTimeProcessors with different reset actions are not on the accelerated path")
             reset_row = row if row is not None else reset_row
             delay += int(getattr(w, "dead_time", getattr(w, "_steps", 0)))
+        elif "FluxOrientedDqToAbcActionProcessor" in names:
+            raise NotImplementedError("FluxOrientedDqToAbcActionProcessor needs a flux observer: list a FluxObserver() before it")
         elif "DqToAbcActionProcessor" in names:
             if "_DFIMDqToAbcActionProcessor" in names or getattr(w, "_angle_name", "epsilon") != "epsilon":
                 raise NotImplementedError("dq processors that need a flux observer (SCIM, DFIM) are not on the accelerated path")
@@ -147,6 +212,8 @@ def fold_wrappers(wrappers, observation_chain=None):
             raise NotImplementedError(f"physical-system wrapper {type(w).__name__} is not on the accelerated path (observation "
                                       "post-processing stays on the host: wrap the n_envs=1 system with the reference's wrapper)")
     out = dict(action_delay=delay, action_frame=frame)
+    if flux_action:
+        out["flux_action"] = flux_action  # (not a BatchedSCMLSystem argument: make() takes it out and hands it to the env)
     if reset_row is not None and any(reset_row):
         out["action_delay_reset"] = reset_row
     return out

@@ -482,6 +482,60 @@ int gemx_obsproc_create(const gemx_obsproc_config *cfg, int dtype, int device, g
 int gemx_obsproc_apply(gemx_obsproc *p, const void *state_dev, const void *refs_dev, int64_t rows, void *out_dev, void *stream);
 int gemx_obsproc_destroy(gemx_obsproc *p);
 
+/* Device-side FLUX OBSERVER and flux-oriented dq actions for the induction machines (new struct and entry points only, ABI number
+ * unchanged): the reference's FluxObserver (physical_system_wrappers/flux_observer.py:80-102) and the 'SCIM' / 'DFIM' variants of its
+ * DqToAbcActionProcessor (dq_to_abc_action_processor.py:57-148) as a stage of its own behind the stepping kernels.  Per env a handle
+ * keeps the rotor-flux estimate Psi (complex, ALWAYS double: the explicit Euler recursion
+ *   Psi += tau [(i_alpha + j i_beta) k_current - Psi (k_flux - j omega p)],   (i_alpha, i_beta) = t_23 of the three named currents,
+ * runs for the whole episode) and the frame(s) the NEXT action will be rotated by; the two new columns and the frames are evaluated from
+ * Psi in the row's precision R:
+ *   psi_abs = |Psi| / psi_limit,   psi_angle = arg(Psi) / pi
+ *   SCIM: frame 0 = arg(Psi) + angle_advance tau omega p
+ *   DFIM: frame 0 = epsilon + angle_advance tau omega p (stator),   frame 1 = arg(Psi) - frame 0 (rotor)
+ * A reset sets Psi = 0 and the frames to those of the system's constant reset observation (psi_angle = 0, reset_omega, reset_epsilon).
+ *   gemx_fluxobs_step: ONE control step.  state_dev [N][n_in] R (the row the stepping kernel wrote) -> ext_out_dev [N][n_in + 2] R: the
+ *     row unchanged (the same bits), then psi_abs, psi_angle; the lane's next frames are stored; LAST, lanes with done_dev[env] != 0 are
+ *     reset when auto_reset = 1 (the terminating step still shows the updated flux, as the reference's does before its reset()).
+ *     done_dev may be NULL.
+ *   gemx_fluxobs_rows: the same recursion over a stored trajectory state_dev [K][N][n_in], done_dev [K][N] (or NULL) -> ext_out_dev
+ *     [K][N][n_in + 2] in ONE launch; a lane walks its K rows in order and the handle is left exactly where K calls of _step leave it,
+ *     rows and state bit for bit (both run one __device__ function per row).
+ *   gemx_fluxobs_actions: abc_out_dev [N][3] = t_32(q(dq_dev [N][2], frame 0)); DFIM: dq_dev [N][4] -> abc_out_dev [N][6], the second
+ *     pair rotated by frame 1.  Continuous actions, not clipped (the inner converter clips, as in the reference).
+ *   gemx_fluxobs_reset: all lanes, or those with mask_dev[env] != 0.
+ *   gemx_fluxobs_get_state / _set_state: double [4][N] -- Psi re, Psi im, frame 0, frame 1 -- for a checkpoint.
+ * The tensors need the alignment of R only (a view at an odd element offset is legal); in and out must not overlap.  Every call is
+ * kernel launches (get / set: one device-to-device copy) on `stream`: no host state, no allocation, no synchronisation -- capturable.
+ * GEMX_ERR_ARG at create: a null pointer, struct_size, n_in outside [4, GEMX_MAX_OUT], a column index outside [0, n_in) (epsilon_index
+ * is read for GEMX_FLUX_ACT_DFIM only), an unknown action_mode, auto_reset not 0 | 1, psi_limit or tau not positive, n_envs < 1. */
+enum { GEMX_FLUX_ACT_NONE = 0, GEMX_FLUX_ACT_SCIM = 1, GEMX_FLUX_ACT_DFIM = 2 };
+typedef struct gemx_fluxobs_config {
+    int32_t struct_size;      /* = sizeof(gemx_fluxobs_config) */
+    int32_t n_in;             /* columns of a state row: 4..GEMX_MAX_OUT */
+    int32_t omega_index;      /* column of omega */
+    int32_t current_index[3]; /* columns of the three observed currents (current_names) */
+    int32_t epsilon_index;    /* column of epsilon (GEMX_FLUX_ACT_DFIM) */
+    int32_t action_mode;      /* GEMX_FLUX_ACT_* */
+    int32_t auto_reset;       /* 1: a done lane restarts on its own (the system's auto_reset) */
+    int32_t reserved;
+    double omega_limit, current_limit[3], epsilon_limit; /* PhysicalSystem.limits of those columns */
+    double psi_limit;         /* l_m * limits[i_sd] */
+    double p, tau;            /* pole pairs, control period */
+    double k_current;         /* r_r l_m / l_r,  l_r = l_m + l_sigr */
+    double k_flux;            /* r_r / l_r */
+    double angle_advance;     /* in control steps: 0.5 + dead time */
+    double reset_omega, reset_epsilon; /* the NORMALISED omega (and epsilon) of the constant reset observation */
+} gemx_fluxobs_config;
+typedef struct gemx_fluxobs gemx_fluxobs;
+int gemx_fluxobs_create(const gemx_fluxobs_config *cfg, int64_t n_envs, int dtype, int device, gemx_fluxobs **out);
+int gemx_fluxobs_destroy(gemx_fluxobs *h);
+int gemx_fluxobs_reset(gemx_fluxobs *h, const uint8_t *mask_dev, void *stream);
+int gemx_fluxobs_step(gemx_fluxobs *h, const void *state_dev, const uint8_t *done_dev, void *ext_out_dev, void *stream);
+int gemx_fluxobs_rows(gemx_fluxobs *h, const void *state_dev, const uint8_t *done_dev, int32_t K, void *ext_out_dev, void *stream);
+int gemx_fluxobs_actions(gemx_fluxobs *h, const void *dq_dev, void *abc_out_dev, void *stream);
+int gemx_fluxobs_get_state(gemx_fluxobs *h, double *out_dev, void *stream);
+int gemx_fluxobs_set_state(gemx_fluxobs *h, const double *in_dev, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
