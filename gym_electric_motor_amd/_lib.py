@@ -254,3 +254,33 @@ def check(rc):
         if rc == -1:
             raise ValueError(msg)
         raise GemxError(msg)
+
+
+def bound_call(fn, owner, args, keep=(), result=None):
+    """-> zero-argument launch() of `fn(owner._handle, *args)` with everything resolved once: a call is the FFI call and nothing else.
+    The handle is read per call (None after `owner.close()` -> the C ABI's "null handle" error, not a stale pointer), a non-zero
+    status goes through `check`, `result` is returned; `keep` holds the tensors and the stream behind the raw pointers in `args` for
+    as long as the launcher lives."""
+
+    def launch(_fn=fn, _owner=owner, _args=args, _result=result, _keep=keep):
+        rc = _fn(_owner._handle, *_args)
+        if rc:
+            check(rc)
+        return _result
+
+    return launch
+
+
+def sequence(*launches, result=None):
+    """-> zero-argument launch() that runs the given launchers in order (None entries are left out) and returns `result`; None when
+    there is nothing to run.  (One launcher and no `result`: that launcher itself -- no frame of its own around it.)"""
+    launches = tuple(f for f in launches if f is not None)
+    if len(launches) < 2 and result is None:
+        return launches[0] if launches else None
+
+    def launch(_launches=launches, _result=result):
+        for f in _launches:
+            f()
+        return _result
+
+    return launch

@@ -46,7 +46,8 @@ Field-oriented control of the induction machines (flux_observer.py, csrc/gemx_fl
 actions into (u_d, u_q) pairs in the estimated flux frame.  A step is then four launches: dq -> abc actions, the physics, the observer,
 the observation stage (when it is not the identity).  The K-step rollouts run with a `FluxObserver` and abc actions (physics, then ONE
 pass of the observer over the stored rows, then the stage); with the flux-oriented action processor they raise: each step's angle depends
-on the previous step's observation.
+on the previous step's observation.  The order of the launches behind the physics is written down once, for every entry point of both
+env classes: `ObservationPipeline.bind_after_step` / `bind_after_rollout` (observation.py) and, for the complete rollouts, `_tail` below.
 
     env = ga.make("Cont-CC-SCIM-v0", n_envs=4096, physical_system_wrappers=(ga.FluxObserver(), ga.FluxOrientedDqToAbcActionProcessor("SCIM")))
     state, _ = env.reset()                              # [N, 14 + 2]
@@ -241,82 +242,17 @@ class BatchedElectricMotorEnv:
     def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None):
         """flux_action: None | 'SCIM' | 'DFIM' -- the flux-oriented dq action processor (needs a FluxObserver in the observation chain).
         observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
-        `step()` and `rollout()` then return the PROCESSED state, `state_space` / `state_names` describe it; `physical_system` stays raw."""
+        `step()` and `rollout()` then return the PROCESSED state, `state_space` / `state_names` describe it; `physical_system` stays raw.
+        Everything behind the physics is the `pipeline` (observation.py: ObservationPipeline)."""
+        from .observation import ObservationPipeline
+
         self.physical_system = physical_system
-        self.action_space = physical_system.action_space
-        self.state_space = physical_system.state_space
-        self.state_names = list(physical_system.state_names)
         self.n_envs = physical_system.n_envs
-        self.observation_stage = None
-        self._raw_scratch = self._ext_scratch_buf = None
-        self.flux, self.flux_action, self._flux_only = None, None, False
-        if flux_action and observation is None:
-            raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
-        if observation is not None:
-            from .observation import ObservationStage
-
-            if getattr(physical_system, "_obs_layout", "aos") != "aos":
-                raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
-            stage = ObservationStage(physical_system, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
-                                     n_ref=_n_ref, flux_action=flux_action)
-            self.observation_stage = stage
-            self.state_space = stage.observation_space
-            self.state_names = list(stage.observation_names)
-            self._init_flux(stage, flux_action, _defer_create)
-            if not _defer_create and not self._flux_only:
-                ps = physical_system
-                stage.create(ps._device, ps._dtype_name)
-                self._pstate = bps._torch().empty((ps.n_envs, stage.n_post), dtype=ps._tdtype, device=ps._tdev)
-
-    def _init_flux(self, stage, flux_action, _defer_create):
-        """The flux-observer stage of the observation chain, if there is one: its handle, the extended row buffer `_ext [N, n_base + 2]`
-        and, with the flux-oriented action processor, the env's dq action space and the abc scratch `_abc [N, 3 | 6]`."""
-        self.flux = stage.flux
-        self.flux_action = flux_action
-        self._flux_only = self.flux is not None and stage.is_identity  # (the extended row IS the observation: no column program to run)
-        if self.flux is None:
-            return
-        ps = self.physical_system
-        if flux_action:
-            if ps._cfg.init_kind != bps._lib.INIT_CONST:
-                raise NotImplementedError("random initial states together with the flux-oriented dq action processor are not on the accelerated path: "
-                                          "the frame of the first action after a reset comes from the reset observation, which would not be a constant")
-            self.action_space = Box(-1, 1, shape=(self.flux.n_action,), dtype=np.float64)
-        if _defer_create:
-            return
-        torch = bps._torch()
-        self.flux.set_reset_observation(ps.reset_observation)
-        self.flux.create(ps.n_envs, ps._device, ps._dtype_name)
-        self._ext = torch.zeros((ps.n_envs, self.flux.n_in + 2), dtype=ps._tdtype, device=ps._tdev)
-        if flux_action:
-            self._abc = torch.zeros((ps.n_envs, self.flux.n_action * 3 // 2), dtype=ps._tdtype, device=ps._tdev)
-
-    def _flux_reset(self):
-        """The observer's reset and the extended reset rows: the system's, then [0, 0] (flux_observer.py:80-83)."""
-        self.flux.reset()
-        nb = self.flux.n_in
-        self._ext[:, :nb].copy_(self.physical_system._obs)
-        self._ext[:, nb:].zero_()
-
-    def _dq_to_device(self, actions):
-        """-> contiguous device tensor [N, 2 | 4] of the dq actions."""
-        ps, torch = self.physical_system, bps._torch()
-        if not torch.is_tensor(actions):
-            actions = torch.as_tensor(np.asarray(actions, dtype=np.float64))
-        return actions.to(device=ps._tdev, dtype=ps._tdtype).reshape(ps.n_envs, self.flux.n_action).contiguous()
-
-    def _ext_scratch(self, K):
-        ps = self.physical_system
-        shape = (K, ps.n_envs, self.flux.n_in + 2)
-        if self._ext_scratch_buf is None or tuple(self._ext_scratch_buf.shape) != shape:
-            self._ext_scratch_buf = bps._torch().empty(shape, dtype=ps._tdtype, device=ps._tdev)
-        return self._ext_scratch_buf
-
-    def _refuse_flux_rollout(self):
-        if self.flux_action:
-            from .flux_observer import ROLLOUT_REFUSAL
-
-            raise NotImplementedError(ROLLOUT_REFUSAL)
+        pipe = self.pipeline = ObservationPipeline(physical_system, observation, _n_ref, flux_action, _defer_create)
+        self.observation_stage, self.flux, self.flux_action, self._flux_only = pipe.stage, pipe.flux, pipe.flux_action, pipe.flux_only
+        self.action_space = pipe.action_space
+        self.state_space = physical_system.state_space if pipe.stage is None else pipe.stage.observation_space
+        self.state_names = list(physical_system.state_names if pipe.stage is None else pipe.stage.observation_names)
 
     def get_checkpoint(self):
         """`physical_system.get_checkpoint()`, plus the flux observer's per-env state (`flux_observer`: float64 [4, N]) when the env has one."""
@@ -335,103 +271,68 @@ class BatchedElectricMotorEnv:
     def unwrapped(self):
         return self
 
-    def _processed(self, raw):
-        """The stage on the system's internal state buffer (n_envs == 1 with numpy in / out keeps numpy)."""
-        out = self._ext if self._flux_only else self.observation_stage.apply(self._ext if self.flux is not None else self.physical_system._obs, out=self._pstate)
-        if isinstance(raw, np.ndarray):
-            return out.reshape(-1).double().cpu().numpy()
-        return out
+    # the pipeline's buffers under the names they had on the env
+    _ext = property(lambda self: self.pipeline.rows)
+    _raw_scratch = property(lambda self: self.pipeline.raw_scratch)
+    _ext_scratch_buf = property(lambda self: self.pipeline.ext_scratch)
 
-    def _processed_trajectory(self, raw, obs_out=None, done=None):
-        if self.flux is not None:  # ONE pass of the observer over the stored rows, then the column program (unless it is the identity)
-            if raw.dim() != 3:
-                raise NotImplementedError("last_only rollouts cannot carry a FluxObserver: its recursion needs every row")
-            raw = self.flux.rows(raw, done, out=obs_out if self._flux_only else self._ext_scratch(int(raw.shape[0])))
-            if self._flux_only:
-                return raw
-        return self.observation_stage.apply(raw, out=obs_out)
+    def _shown(self, raw):
+        """What the env hands out for the system's `raw` state (n_envs == 1 with numpy in / out keeps numpy)."""
+        if self.observation_stage is None:
+            return raw
+        out = self.pipeline.state
+        return out.reshape(-1).double().cpu().numpy() if isinstance(raw, np.ndarray) else out
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state; returns (observations, {})."""
-        if self.observation_stage is not None:
-            raw = self.physical_system.reset()
-            if self.flux is not None:
-                self._flux_reset()
-            return self._processed(raw), {}
-        return self.physical_system.reset(), {}
+        raw = self.physical_system.reset()
+        self.pipeline.reset()
+        return self._shown(raw), {}
 
     def step(self, actions, references=None):
         """-> (obs [N, S_out], reward, terminated [N] uint8, truncated=False, {}).  reward: [N] device tensor when a reward function is
         installed (`physical_system.set_reward`) and `references [N, n_ref]` are passed, else None.  With auto_reset (default for
         n_envs > 1) an env that terminated restarts from the reset state on its next step; the state it shows
         right after that restart is `physical_system.reset_observation`."""
-        ps = self.physical_system
+        ps, pipe = self.physical_system, self.pipeline
         if self.flux_action:  # launch 1 of 4: the dq actions rotated into the frame the last observation left
-            self.flux.bind_actions(self._dq_to_device(actions), self._abc)()
-            actions = self._abc
+            pipe.bind_actions(pipe.dq_to_device(actions))()
+            actions = pipe.abc
         obs = ps.simulate(actions, references=references) if references is not None else ps.simulate(actions)
-        if self.flux is not None:
-            self.flux.step(ps._obs, ps._done, self._ext)
-        if self.observation_stage is not None:
-            obs = self._processed(obs)
-        return obs, (ps.reward if references is not None else None), ps.done, False, {}
+        pipe.after_step()
+        return self._shown(obs), (ps.reward if references is not None else None), ps.done, False, {}
+
+    def _rollout(self, physics, K, obs_out, kw):
+        """A physics rollout into the pipeline's raw rows, then its launches: ONE pass over the stored rows writes the processed
+        `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
+        pipe = self.pipeline
+        pipe.refuse_rollout()
+        res = physics(obs_out=pipe.raw_rows(K, obs_out, kw.get("last_only", False)), **kw)
+        return (pipe.after_rollout(res[0], res[1], None, obs_out),) + tuple(res[1:])
 
     def rollout(self, actions, obs_out=None, **kw):
         """PhysicalSystem.rollout; with an observation stage the raw trajectory goes into a scratch tensor and ONE `apply` writes the
         processed `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
-        self._refuse_flux_rollout()
-        if self.observation_stage is None:
-            return self.physical_system.rollout(actions, obs_out=obs_out, **kw)
-        res = self.physical_system.rollout(actions, obs_out=self._scratch(int(actions.shape[0]), kw.get("last_only", False)), **kw)
-        return (self._processed_trajectory(res[0], obs_out, res[1]),) + tuple(res[1:])
-
-    def _scratch(self, K, last_only=False):
-        ps = self.physical_system
-        shape = tuple(ps._obs.shape) if last_only else (K,) + tuple(ps._obs.shape)
-        if self._raw_scratch is None or tuple(self._raw_scratch.shape) != shape:
-            self._raw_scratch = bps._torch().empty(shape, dtype=ps._tdtype, device=ps._tdev)
-        return self._raw_scratch
+        return self._rollout(lambda **k: self.physical_system.rollout(actions, **k), len(actions), obs_out, kw)
 
     def rollout_synthetic(self, K, obs_out=None, **kw):
         """K fused steps on random actions generated on the device (PhysicalSystem.rollout_synthetic)."""
-        self._refuse_flux_rollout()
-        if self.observation_stage is None:
-            return self.physical_system.rollout_synthetic(K, obs_out=obs_out, **kw)
-        res = self.physical_system.rollout_synthetic(K, obs_out=self._scratch(K), **kw)
-        return (self._processed_trajectory(res[0], obs_out, res[1]),) + tuple(res[1:])
+        return self._rollout(lambda **k: self.physical_system.rollout_synthetic(K, **k), K, obs_out, kw)
 
     def bind_rollout(self, actions, obs_out, done_out, stream=None):
         """-> zero-argument launch(): the pre-bound `gemx_rollout` call for fixed tensors (PhysicalSystem.bind_rollout); with an
-        observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus one `apply`."""
-        self._refuse_flux_rollout()
-        if self.observation_stage is None:
-            return self.physical_system.bind_rollout(actions, obs_out, done_out, stream=stream)
-        ps = self.physical_system
+        observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus the pipeline's launches."""
+        ps, pipe = self.physical_system, self.pipeline
+        pipe.refuse_rollout()
+        if pipe.stage is None:
+            return ps.bind_rollout(actions, obs_out, done_out, stream=stream)
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
-        raw = self._scratch(int(actions.shape[0]))
-        physics = ps.bind_rollout(actions, raw, done_out, stream=stream)
-        observer, src = None, raw
-        if self.flux is not None:
-            src = obs_out if self._flux_only else self._ext_scratch(int(actions.shape[0]))
-            observer = self.flux.bind_rows(raw, done_out, src, stream)
-        post = None if self._flux_only else self.observation_stage.bind_apply(src, None, obs_out, stream)
-        out = (obs_out, done_out)
-
-        def launch():
-            physics()
-            if observer is not None:
-                observer()
-            if post is not None:
-                post()
-            return out
-
-        return launch
+        raw = pipe.raw_rows(int(actions.shape[0]), obs_out)
+        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), pipe.bind_after_rollout(raw, done_out, None, obs_out, stream),
+                                 result=(obs_out, done_out))
 
     def close(self):
-        if self.observation_stage is not None:
-            self.observation_stage.close()
-        if self.flux is not None:
-            self.flux.close()
+        self.pipeline.close()
         self.physical_system.close()
 
 
@@ -448,14 +349,9 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None,
                  flux_action=None):
-        super().__init__(physical_system)
-        if flux_action and observation is None:
-            raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
         ps = physical_system
-        if observation is not None and getattr(ps, "_obs_layout", "aos") != "aos":
-            raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
         d = default_modules or dict(reference_states=(), reward=dict())
-        if getattr(ps, "_obs_layout", "aos") != "aos":
+        if observation is None and getattr(ps, "_obs_layout", "aos") != "aos":
             raise ValueError("the complete env needs obs_layout='aos' (states [N, S_out])")
         rf = dict(d["reward"]) if reward_function in (None, "default") else dict(reward_function)
         unknown = sorted(set(rf) - set(self._REWARD_KEYS))
@@ -478,92 +374,53 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         self.reward_range = ps.reward_range
         lo, hi = gen.reference_space
         self.reference_space = Box(lo, hi, dtype=float)
-        stage = None
-        if observation is not None:  # (after the generator: a flat observation carries its n_ref columns)
-            from .observation import ObservationStage
-
-            stage = ObservationStage(ps, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
-                                     n_ref=len(self.reference_names), flux_action=flux_action)
-            self.state_space = stage.observation_space
-            self.state_names = list(stage.observation_names)
-            self._init_flux(stage, flux_action, _defer_create)
-        self.observation_stage = stage
+        # (after the generator: a flat observation carries its n_ref columns)
+        super().__init__(ps, observation, _n_ref=len(self.reference_names), _defer_create=_defer_create, flux_action=flux_action)
+        flat = self.observation_stage is not None and self.observation_stage.flatten
         self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
-        if stage is not None and stage.flatten:  # FlattenObservation of that Tuple: one box, state then reference
+        if flat:  # FlattenObservation of that Tuple: one box, state then reference
             self.observation_space = Box(np.concatenate((self.state_space.low, self.reference_space.low)),
                                          np.concatenate((self.state_space.high, self.reference_space.high)), dtype=float)
         self._bound = None
         if _defer_create:
             return
-        torch = bps._torch()
-        self._reward = torch.zeros((1, ps.n_envs), dtype=ps._tdtype, device=ps._tdev)
+        self._reward = bps._torch().zeros((1, ps.n_envs), dtype=ps._tdtype, device=ps._tdev)
         ps._reward_buf = self._reward  # (`physical_system.reward` shows the same buffer)
         self._refs = gen.references
-        self._obs = (ps._obs, self._refs)
-        if stage is not None and self._flux_only:
-            self._obs = (self._ext, self._refs)
-        elif stage is not None:
-            stage.create(ps._device, ps._dtype_name)
-            self._pstate = torch.empty((ps.n_envs, stage.n_out), dtype=ps._tdtype, device=ps._tdev)
-            self._obs = self._pstate if stage.flatten else (self._pstate, self._refs)
-
-    def _stage_launcher(self, stream):
-        """The last launch of a step: the observation stage on the fresh state rows (the flux observer's extended rows, if there is one) and
-        the references the generators just wrote; None when the extended row is the observation."""
-        if self._flux_only:
-            return None
-        return self.observation_stage.bind_apply(self._ext if self.flux is not None else self.physical_system._obs, self._refs, self._pstate, stream)
+        self._obs = self.pipeline.state if flat else (self.pipeline.state, self._refs)
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state, all generators restarted and advanced once (core.py:312-313, 485-505).
         -> ((state, ref), {})."""
-        ps, gen = self.physical_system, self.reference_generator
-        ps.reset()
+        gen = self.reference_generator
+        self.physical_system.reset()
         gen.reset()
         gen.step(None)
-        if self.flux is not None:
-            self._flux_reset()
-        if self.observation_stage is not None and not self._flux_only:
-            self.observation_stage.apply(self._ext if self.flux is not None else ps._obs, self._refs, out=self._pstate)
+        self.pipeline.reset(self._refs)
         return self._obs, {}
 
-    def _launchers(self, action_ptr, stream, dq=None):
-        """The two launches of a step with everything resolved: physics + fused reward reading the generator's buffer, then the
-        generator step on the fresh done mask writing that same buffer."""
+    def _launchers(self, a, stream):
+        """-> zero-argument step() on the action tensor `a` with everything resolved, returning the observation: the dq -> abc actions
+        (flux-oriented action processor only), physics + fused reward reading the generator's buffer, then the pipeline's launches
+        around the generator step on the fresh done mask, which writes that same buffer."""
         import ctypes as C
 
-        ps, gen = self.physical_system, self.reference_generator
-        L, check = ps._L, bps._lib.check
-        n_ref = int(self.reward_config.n_ref)
-        to_abc = observer = None
+        ps, pipe = self.physical_system, self.pipeline
+        to_abc, keep = None, (a, stream)
         if self.flux_action:  # dq [N, 2 | 4] -> the abc scratch the physics reads
-            to_abc, action_ptr = self.flux.bind_actions(dq, self._abc, stream), self._abc.data_ptr()
-        if self.flux is not None:
-            observer = self.flux.bind_step(ps._obs, ps._done, self._ext, stream)
-        args = (C.c_void_p(action_ptr), 1, C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr),
-                C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
-        gen_step = gen.bind_step(ps._done, stream=stream)
-        if self.observation_stage is not None:  # generators, then the stage: it reads the references the observation must carry
-            gen_only, post = gen_step, self._stage_launcher(stream)
+            to_abc, a = pipe.bind_actions(a, stream), pipe.abc
+        args = (C.c_void_p(a.data_ptr()), 1, C.c_void_p(self._refs.data_ptr()) if int(self.reward_config.n_ref) else None, C.c_void_p(ps._obs_ptr),
+                C.c_void_p(ps._done_ptr), C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
+        call, check = ps._L.gemx_rollout_reward, bps._lib.check
 
-            def gen_step():
-                gen_only()
-                if post is not None:
-                    post()
-
-        call = L.gemx_rollout_reward
-
-        def physics(_args=args, _call=call):
-            if to_abc is not None:
-                to_abc()
+        def physics(_args=args, _call=call, _keep=keep):  # (hand-written, not `bound_call`: the host's step counter moves with it)
             rc = _call(ps._handle, *_args)
             if rc:
                 check(rc)
             ps._k += 1
-            if observer is not None:
-                observer()
 
-        return physics, gen_step
+        after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(ps._done, stream=stream))
+        return bps._lib.sequence(to_abc, physics, after, result=self._obs)
 
     def step(self, actions, references=None):
         """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches; three with
@@ -571,16 +428,12 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         if references is not None:
             raise TypeError("the complete env generates its references: step(actions)")
         ps = self.physical_system
-        torch = bps._torch()
-        a = self._dq_to_device(actions) if self.flux_action else ps._actions_to_device(actions, (ps._n_envs,))
-        stream = torch.cuda.current_stream(ps._tdev)
+        a = self.pipeline.dq_to_device(actions) if self.flux_action else ps._actions_to_device(actions, (ps._n_envs,))
+        stream = bps._torch().cuda.current_stream(ps._tdev)
         key = (a.data_ptr(), stream.cuda_stream)
         if self._bound is None or self._bound[0] != key:  # (a loop that reuses its action tensor and stream resolves the launches once)
-            self._bound = (key, self._launchers(a.data_ptr(), stream, a), a, stream)
-        physics, gen_step = self._bound[1]
-        physics()
-        gen_step()
-        return self._obs, self._reward[0], ps._done, False, {}
+            self._bound = (key, self._launchers(a, stream))
+        return self._bound[1](), self._reward[0], ps._done, False, {}
 
     def bind_step(self, action_buffer, stream=None):
         """A zero-argument `step()` for a closed loop that reuses ONE action tensor: -> `(step, (state, ref), reward, done)`; `step()`
@@ -596,15 +449,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         if self.flux_action:
             a = a.view(ps._n_envs, self.flux.n_action)
         stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
-        physics, gen_step = self._launchers(a.data_ptr(), stream, a)
-        obs = self._obs
-
-        def step(_keep=(a, stream)):
-            physics()
-            gen_step()
-            return obs
-
-        return step, obs, self._reward[0], ps._done
+        return self._launchers(a, stream), self._obs, self._reward[0], ps._done
 
     # ------------------------------------------------------------------ complete K-step rollouts: physics -> references -> reward
     def _complete_shapes(self, K):
@@ -617,7 +462,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
     def _check_complete(self, what, K, actions=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
         """bind_rollout-style validation (K, then per tensor: dtype, shape, contiguity, device) -> K.  Needs no device: it runs
         before anything is launched, and on an env whose handles were never created."""
-        self._refuse_flux_rollout()
+        self.pipeline.refuse_rollout()
         torch = bps._torch()
         ps = self.physical_system
         tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
@@ -649,36 +494,43 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 check(t, name, dtype, shape)
         return K
 
-    def _reward_rows_args(self, raw, refs, done, reward, K, stream):
+    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False):
+        """-> the launchers that follow the physics of a complete K-step rollout, in order, on fixed tensors: the generators in the shell's
+        order on the done mask; the reward of row k against the references shown before step k; the pipeline's launches over the stored
+        rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
+        rollouts continue from it)."""
         import ctypes as C
 
-        n_ref = int(self.reward_config.n_ref)
-        return (C.c_void_p(raw.data_ptr()), C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(refs.data_ptr()) if n_ref else None,
-                C.c_void_p(done.data_ptr()), K, C.c_void_p(reward.data_ptr()), C.c_void_p(stream.cuda_stream))
-
-    def _rollout_complete(self, what, K, physics, state_out, refs_out, reward_out, done_out):
         torch = bps._torch()
-        ps, gen, stage = self.physical_system, self.reference_generator, self.observation_stage
-        s_shape, r_shape, w_shape, d_shape = self._complete_shapes(K)
-        if state_out is None:
-            state_out = torch.empty(s_shape, dtype=ps._tdtype, device=ps._tdev)
-        if reward_out is None:
-            reward_out = torch.empty(w_shape, dtype=ps._tdtype, device=ps._tdev)
-        if done_out is None:
-            done_out = torch.empty(d_shape, dtype=torch.uint8, device=ps._tdev)
-        raw = state_out if stage is None else self._scratch(K)
-        physics(raw, done_out)                                   # 1. physics: state rows and done bytes
-        refs = gen.rollout_shell(K, done_out, out=refs_out)      # 2. generators in the shell's order: restart on done[k], advance
-        stream = torch.cuda.current_stream(ps._tdev)             # 3. reward of row k against the references shown before step k
-        bps._lib.check(ps._L.gemx_reward_rows(ps._handle, *self._reward_rows_args(raw, refs, done_out, reward_out, K, stream)))
-        if stage is not None:
-            src = raw
-            if self.flux is not None:  # ONE pass of the observer over the stored rows
-                src = self.flux.rows(raw, done_out, out=state_out if self._flux_only else self._ext_scratch(K))
-            if not self._flux_only:
-                stage.apply(src, refs, out=state_out)
-        self._refs.copy_(refs[K - 1])  # (after the reward pass has read the old ones: step() and further rollouts continue from row K-1)
-        return state_out, refs, reward_out, done_out
+        ps, gen = self.physical_system, self.reference_generator
+        if eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
+            generators = lambda: gen.rollout_shell(K, done_out, out=refs_out)  # noqa: E731
+        else:
+            generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
+        n_ref = int(self.reward_config.n_ref)
+        args = (C.c_void_p(raw.data_ptr()), C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(refs_out.data_ptr()) if n_ref else None,
+                C.c_void_p(done_out.data_ptr()), K, C.c_void_p(reward_out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        reward = bps._lib.bound_call(ps._L.gemx_reward_rows, ps, args, (raw, refs_out, done_out, reward_out, stream))
+        shown, last = self._refs, refs_out[K - 1]
+
+        def show(_current=torch.cuda.current_stream, _on=torch.cuda.stream):
+            if _current(ps._tdev) == stream:  # one device-to-device copy on the launch stream
+                shown.copy_(last)
+            else:
+                with _on(stream):
+                    shown.copy_(last)
+
+        return generators, reward, self.pipeline.bind_after_rollout(raw, done_out, refs_out, state_out, stream), show
+
+    def _rollout_complete(self, K, physics, outs):
+        """The eager entry points: allocate what was not given, run `physics(raw, done_out)` and then the tail, once."""
+        torch = bps._torch()
+        ps = self.physical_system
+        outs = tuple(torch.empty(shape, dtype=torch.uint8 if i == 3 else ps._tdtype, device=ps._tdev) if t is None else t
+                     for i, (t, shape) in enumerate(zip(outs, self._complete_shapes(K))))
+        raw = self.pipeline.raw_rows(K, outs[0])
+        physics(raw, outs[3])
+        return bps._lib.sequence(*self._tail(K, raw, *outs, torch.cuda.current_stream(ps._tdev), eager=True), result=outs)()
 
     def rollout_complete(self, actions, state_out=None, refs_out=None, reward_out=None, done_out=None):
         """K complete control steps in THREE launches (four with an observation stage) instead of K x (two or three):
@@ -694,15 +546,15 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         K = self._check_complete("rollout_complete", actions.shape[0], None, state_out, refs_out, reward_out, done_out)
         ps = self.physical_system
         a = ps._actions_to_device(actions, (K, ps._n_envs))
-        return self._rollout_complete("rollout_complete", K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), state_out, refs_out, reward_out, done_out)
+        return self._rollout_complete(K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), (state_out, refs_out, reward_out, done_out))
 
     def rollout_complete_synthetic(self, K, seed=0, step0=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
         """`rollout_complete` on the device-side action source (`physical_system.rollout_synthetic(K, seed, step0)`): no action tensor is
         read.  Equal, bit for bit, to `rollout_complete(physical_system.synthetic_actions(K, seed, step0))`."""
         K = self._check_complete("rollout_complete_synthetic", K, None, state_out, refs_out, reward_out, done_out)
         ps = self.physical_system
-        return self._rollout_complete("rollout_complete_synthetic", K, lambda raw, done: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done),
-                                      state_out, refs_out, reward_out, done_out)
+        return self._rollout_complete(K, lambda raw, done: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done),
+                                      (state_out, refs_out, reward_out, done_out))
 
     def bind_rollout_complete(self, actions, state_out, refs_out, reward_out, done_out, stream=None):
         """-> zero-argument launch() of `rollout_complete` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
@@ -711,53 +563,21 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         replays advance the physics and the generators.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
         if not hasattr(actions, "shape") or len(actions.shape) < 1:
             raise ValueError("bind_rollout_complete needs a device tensor of actions [K, N, A] / [K, N]")
-        for t, name in ((state_out, "state_out"), (refs_out, "refs_out"), (reward_out, "reward_out"), (done_out, "done_out")):
+        outs = (state_out, refs_out, reward_out, done_out)
+        for t, name in zip(outs, ("state_out", "refs_out", "reward_out", "done_out")):
             if t is None:
                 raise ValueError(f"bind_rollout_complete: {name} must be given (a bound launch allocates nothing)")
-        K = self._check_complete("bind_rollout_complete", actions.shape[0], actions, state_out, refs_out, reward_out, done_out)
+        K = self._check_complete("bind_rollout_complete", actions.shape[0], actions, *outs)
         if isinstance(self.reference_generator, ReplayReferenceGenerator):
             self.reference_generator.bind_rollout_shell(done_out, refs_out)  # (raises: cannot be captured)
-        torch = bps._torch()
-        ps, gen, stage = self.physical_system, self.reference_generator, self.observation_stage
-        L, check = ps._L, bps._lib.check
-        stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
-        raw = state_out if stage is None else self._scratch(K)
-        physics = ps.bind_rollout(actions, raw, done_out, stream=stream)
-        generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
-        args = self._reward_rows_args(raw, refs_out, done_out, reward_out, K, stream)
-        call = L.gemx_reward_rows
-        observer, src = None, raw
-        if self.flux is not None:
-            src = state_out if self._flux_only else self._ext_scratch(K)
-            observer = self.flux.bind_rows(raw, done_out, src, stream)
-        post = stage.bind_apply(src, refs_out, state_out, stream) if stage is not None and not self._flux_only else None
-        shown, last = self._refs, refs_out[K - 1]
-        current, on = torch.cuda.current_stream, torch.cuda.stream
-        out = (state_out, refs_out, reward_out, done_out)
-        keep = (actions, raw, stream)
-
-        def launch(_args=args, _call=call, _keep=keep):
-            physics()
-            generators()
-            rc = _call(ps._handle, *_args)
-            if rc:
-                check(rc)
-            if observer is not None:
-                observer()
-            if post is not None:
-                post()
-            if current(ps._tdev) == stream:  # the references shown last: one device-to-device copy on the launch stream
-                shown.copy_(last)
-            else:
-                with on(stream):
-                    shown.copy_(last)
-            return out
-
-        return launch
+        ps = self.physical_system
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        raw = self.pipeline.raw_rows(K, state_out)
+        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), *self._tail(K, raw, *outs, stream), result=outs)
 
     def close(self):
         self.reference_generator.close()
-        super().close()  # (closes the observation stage too)
+        super().close()  # (closes the observation pipeline too)
 
 
 def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, load=None, ode_solver=None, tau=None,

@@ -203,14 +203,7 @@ class FluxObserverStage:
         if done is not None:
             self._check(done, (self.n_envs,), "done", torch.uint8)
         args = (C.c_void_p(state.data_ptr()), C.c_void_p(done.data_ptr()) if done is not None else None, C.c_void_p(out.data_ptr()), self._st(stream))
-        call, check = self._L.gemx_fluxobs_step, _lib.check
-
-        def launch(_args=args, _call=call, _keep=(state, done, out, stream)):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
-
-        return launch
+        return _lib.bound_call(self._L.gemx_fluxobs_step, self, args, (state, done, out, stream))
 
     def step(self, state, done, out, stream=None):
         self.bind_step(state, done, out, stream)()
@@ -226,14 +219,7 @@ class FluxObserverStage:
         if done is not None:
             self._check(done, (K, self.n_envs), "done", torch.uint8)
         args = (C.c_void_p(state.data_ptr()), C.c_void_p(done.data_ptr()) if done is not None else None, K, C.c_void_p(out.data_ptr()), self._st(stream))
-        call, check = self._L.gemx_fluxobs_rows, _lib.check
-
-        def launch(_args=args, _call=call, _keep=(state, done, out, stream)):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
-
-        return launch
+        return _lib.bound_call(self._L.gemx_fluxobs_rows, self, args, (state, done, out, stream))
 
     def rows(self, state, done, out=None, stream=None):
         import torch
@@ -248,14 +234,7 @@ class FluxObserverStage:
         self._check(dq, (self.n_envs, self.n_action), "dq actions")
         self._check(abc, (self.n_envs, self.n_action * 3 // 2), "abc actions")
         args = (C.c_void_p(dq.data_ptr()), C.c_void_p(abc.data_ptr()), self._st(stream))
-        call, check = self._L.gemx_fluxobs_actions, _lib.check
-
-        def launch(_args=args, _call=call, _keep=(dq, abc, stream)):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
-
-        return launch
+        return _lib.bound_call(self._L.gemx_fluxobs_actions, self, args, (dq, abc, stream))
 
     def get_state(self, stream=None):
         """float64 device tensor [4, N]: Psi re, Psi im, frame 0, frame 1."""

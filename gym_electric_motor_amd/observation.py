@@ -211,6 +211,11 @@ class ObservationStage:
         """state [..., n_in] (contiguous device tensor) -> out [..., n_post] (or [..., n_post + n_ref] with `flatten`, reading refs
         [..., n_ref]).  One kernel launch on `stream` (default: the current one); `out` is allocated unless given and must not alias
         the inputs."""
+        return self.bind_apply(state, refs, out, stream)()
+
+    def bind_apply(self, state, refs, out, stream=None):
+        """-> zero-argument launch() of `apply` on fixed tensors, returning `out`: everything is checked and resolved here, once (`out`
+        None: allocated here; `stream` None: the one current now)."""
         import torch
 
         if self._handle is None:
@@ -230,32 +235,151 @@ class ObservationStage:
             self._check(out, self.n_out, "out")
             if tuple(out.shape[:-1]) != lead:
                 raise ValueError(f"out {tuple(out.shape)} does not match state {tuple(state.shape)}")
-        rows = state.numel() // self.n_in
-        st = (stream if stream is not None else torch.cuda.current_stream(self._tdev)).cuda_stream
-        _lib.check(self._L.gemx_obsproc_apply(self._handle, C.c_void_p(state.data_ptr()), C.c_void_p(refs.data_ptr()) if need_refs else None, rows,
-                                              C.c_void_p(out.data_ptr()), C.c_void_p(st)))
-        return out
-
-    def bind_apply(self, state, refs, out, stream):
-        """-> zero-argument launch() of `apply` on fixed tensors: everything is checked and resolved here, once."""
-        if self._handle is None:
-            raise _lib.GemxError("the observation stage has no device handle (built with _defer_create, or closed)")
-        self._check(state, self.n_in, "state")
-        self._check(out, self.n_out, "out")
-        if self.flatten and self.n_ref > 0:
-            self._check(refs, self.n_ref, "refs")
-            if tuple(refs.shape[:-1]) != tuple(state.shape[:-1]):
-                raise ValueError(f"refs {tuple(refs.shape)} do not match state {tuple(state.shape)}")
-        if tuple(out.shape[:-1]) != tuple(state.shape[:-1]):
-            raise ValueError(f"out {tuple(out.shape)} does not match state {tuple(state.shape)}")
-        need_refs = self.flatten and self.n_ref > 0
+        stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
         args = (C.c_void_p(state.data_ptr()), C.c_void_p(refs.data_ptr()) if need_refs else None, state.numel() // self.n_in, C.c_void_p(out.data_ptr()),
                 C.c_void_p(stream.cuda_stream))
-        call, check = self._L.gemx_obsproc_apply, _lib.check
+        return _lib.bound_call(self._L.gemx_obsproc_apply, self, args, (state, refs, out, stream), out)
 
-        def launch(_args=args, _call=call, _keep=(state, refs, out, stream)):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
 
-        return launch
+class ObservationPipeline:
+    """Everything between a physical system's raw state rows and the state an env hands out, for BOTH env shells, and the one place
+    where the order of the launches after the physics lives:
+
+        the flux observer on the raw rows -> `rows` [.., n_base + 2]      (when the chain holds a FluxObserver)
+        the column program on those rows, reading the references when the observation is flat -> `state`   (unless it is the identity)
+
+    `observation`: None (no stage: `state` is the system's own buffer and nothing is launched) or dict(chain=, observed_states=,
+    flatten=); `n_ref`: the reference columns a flat observation carries; `flux_action`: None | 'SCIM' | 'DFIM', the flux-oriented dq
+    action processor.  Owns the stage, the observer, `rows`, the dq processor's `abc` scratch, the `state` buffer and the raw and
+    extended scratch trajectories of the K-step rollouts; every refusal of a combination is raised here."""
+
+    def __init__(self, physical_system, observation=None, n_ref=0, flux_action=None, defer_create=False):
+        ps = self.physical_system = physical_system
+        self.stage = self.flux = self.flux_action = self.raw_scratch = self.ext_scratch = None
+        self.flux_only = self.has_program = False
+        self.action_space = ps.action_space
+        if observation is None:
+            if flux_action:
+                raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
+        else:
+            if getattr(ps, "_obs_layout", "aos") != "aos":
+                raise ValueError("the observation stage reads state rows: it needs obs_layout='aos', not 'soa'")
+            stage = self.stage = ObservationStage(ps, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
+                                                  n_ref=n_ref, flux_action=flux_action)
+            self.flux, self.flux_action = stage.flux, flux_action
+            self.flux_only = self.flux is not None and stage.is_identity  # (the extended row IS the observation: no column program to run)
+            self.has_program = not self.flux_only
+            if flux_action:
+                if ps._cfg.init_kind != _lib.INIT_CONST:
+                    raise NotImplementedError("random initial states together with the flux-oriented dq action processor are not on the accelerated path: "
+                                              "the frame of the first action after a reset comes from the reset observation, which would not be a constant")
+                self.action_space = Box(-1, 1, shape=(self.flux.n_action,), dtype=np.float64)
+        if defer_create:
+            return
+        import torch
+
+        new = lambda *shape: torch.zeros(shape, dtype=ps._tdtype, device=ps._tdev)  # noqa: E731
+        self.rows = self.state = ps._obs
+        if self.flux is not None:
+            self.flux.set_reset_observation(ps.reset_observation)
+            self.flux.create(ps.n_envs, ps._device, ps._dtype_name)
+            self.rows = self.state = new(ps.n_envs, self.flux.n_in + 2)
+            if flux_action:
+                self.abc = new(ps.n_envs, self.flux.n_action * 3 // 2)
+        if self.has_program:
+            self.stage.create(ps._device, ps._dtype_name)
+            self.state = new(ps.n_envs, self.stage.n_out)
+
+    def refuse_rollout(self):
+        if self.flux_action:
+            from .flux_observer import ROLLOUT_REFUSAL
+
+            raise NotImplementedError(ROLLOUT_REFUSAL)
+
+    def _scratch(self, name, shape):
+        ps, buf = self.physical_system, getattr(self, name)
+        if buf is None or tuple(buf.shape) != shape:
+            import torch
+
+            buf = torch.empty(shape, dtype=ps._tdtype, device=ps._tdev)
+            setattr(self, name, buf)
+        return buf
+
+    def raw_rows(self, K, out, last_only=False):
+        """Where the physics of a K-step rollout writes: `out` itself without a stage, else the raw scratch trajectory."""
+        if self.stage is None:
+            return out
+        shape = tuple(self.physical_system._obs.shape)
+        return self._scratch("raw_scratch", shape if last_only else (K,) + shape)
+
+    # ------------------------------------------------------------------ the launches after the physics
+    def bind_after_step(self, refs=None, stream=None, generators=None):
+        """-> zero-argument launch() of what follows a step's physics, or None when there is nothing to run: the observer on the system's
+        fresh rows and done mask, then `generators` (the complete env's reference step: a flat observation carries what it writes into
+        `refs` [N, n_ref]), then the column program into `state`."""
+        ps = self.physical_system
+        observer = self.flux.bind_step(ps._obs, ps._done, self.rows, stream) if self.flux is not None else None
+        return _lib.sequence(observer, generators, self.stage.bind_apply(self.rows, refs, self.state, stream) if self.has_program else None)
+
+    def after_step(self, refs=None):
+        """`bind_after_step` on the current stream, run once -> `state`."""
+        launch = self.bind_after_step(refs)
+        if launch is not None:
+            launch()
+        return self.state
+
+    def bind_after_rollout(self, raw, done, refs, out, stream=None):
+        """-> zero-argument launch() of what follows a K-step rollout's physics, returning `out` (None: allocated here), or None without a
+        stage (`raw` is the result): ONE pass of the observer over the stored rows `raw` [K, N, n_base] and `done` [K, N], then the column
+        program, reading `refs` [K, N, n_ref] when the observation is flat."""
+        if self.stage is None:
+            return None
+        lead = tuple(raw.shape[:-1])
+        if out is None:
+            import torch
+
+            out = torch.empty(lead + (self.stage.n_out,), dtype=raw.dtype, device=raw.device)
+        observer, src = None, raw
+        if self.flux is not None:
+            if raw.dim() != 3:
+                raise NotImplementedError("last_only rollouts cannot carry a FluxObserver: its recursion needs every row")
+            src = out if self.flux_only else self._scratch("ext_scratch", lead + (self.flux.n_in + 2,))
+            observer = self.flux.bind_rows(raw, done, src, stream)
+        return _lib.sequence(observer, self.stage.bind_apply(src, refs, out, stream) if self.has_program else None, result=out)
+
+    def after_rollout(self, raw, done, refs=None, out=None):
+        """`bind_after_rollout` on the current stream, run once -> the processed trajectory."""
+        launch = self.bind_after_rollout(raw, done, refs, out)
+        return raw if launch is None else launch()
+
+    def reset(self, refs=None):
+        """After the system's reset: the observer's, the extended reset rows -- the system's, then [0, 0] (flux_observer.py:80-83) --
+        and the column program -> `state`."""
+        if self.flux is not None:
+            self.flux.reset()
+            nb = self.flux.n_in
+            self.rows[:, :nb].copy_(self.physical_system._obs)
+            self.rows[:, nb:].zero_()
+        if self.has_program:
+            self.stage.apply(self.rows, refs, out=self.state)
+        return self.state
+
+    # ------------------------------------------------------------------ flux-oriented dq actions
+    def dq_to_device(self, actions):
+        """-> contiguous device tensor [N, 2 | 4] of the dq actions."""
+        import torch
+
+        ps = self.physical_system
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions, dtype=np.float64))
+        return actions.to(device=ps._tdev, dtype=ps._tdtype).reshape(ps.n_envs, self.flux.n_action).contiguous()
+
+    def bind_actions(self, dq, stream=None):
+        """-> zero-argument launch(): the dq actions [N, 2 | 4] rotated into the frame the last observation left -> `abc` [N, 3 | 6]."""
+        return self.flux.bind_actions(dq, self.abc, stream)
+
+    def close(self):
+        if self.stage is not None:
+            self.stage.close()
+        if self.flux is not None:
+            self.flux.close()

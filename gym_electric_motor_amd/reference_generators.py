@@ -120,14 +120,7 @@ class _DeviceGenerators:
         `step(done[k])` returns -- the generators of the envs with done[k, env] != 0 restart first, then every generator advances.  (`rollout`
         resets AFTER row k.)  done: [K, N] uint8 device tensor, e.g. a physics rollout's done mask, or None.  `references` is not
         touched; may be mixed freely with `step` and `rollout`."""
-        import torch
-
-        K = self._check_shell(K, done, out, "rollout_shell")
-        if out is None:
-            out = torch.empty((K, self._n_envs, int(self._cfg.n_ref)), dtype=self._tdtype, device=self._tdev)
-        _lib.check(self._L.gemx_refgen_rollout_shell(self._handle, C.c_void_p(done.data_ptr()) if done is not None else None, K,
-                                                     C.c_void_p(out.data_ptr()), self._stream()))
-        return out
+        return self._bind_shell(K, done, out, None, "rollout_shell")()
 
     def bind_rollout_shell(self, done, out, stream=None):
         """-> zero-argument launch(): `gemx_refgen_rollout_shell(done) -> out` with the handle, both pointers and the stream resolved once."""
@@ -135,19 +128,18 @@ class _DeviceGenerators:
 
         if done is None or out is None:
             raise ValueError("bind_rollout_shell needs the done [K, N] and out [K, N, n_ref] tensors")
-        K = self._check_shell(done.shape[0] if torch.is_tensor(done) and done.dim() == 2 else 0, done, out, "bind_rollout_shell")
+        return self._bind_shell(done.shape[0] if torch.is_tensor(done) and done.dim() == 2 else 0, done, out, stream, "bind_rollout_shell")
+
+    def _bind_shell(self, K, done, out, stream, what):
+        """The one validation and the one launcher behind `rollout_shell` (out None: allocated here, once) and `bind_rollout_shell`."""
+        import torch
+
+        K = self._check_shell(K, done, out, what)
+        if out is None:
+            out = torch.empty((K, self._n_envs, int(self._cfg.n_ref)), dtype=self._tdtype, device=self._tdev)
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
-        call, check = self._L.gemx_refgen_rollout_shell, _lib.check
-        args = (C.c_void_p(done.data_ptr()), K, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        keep = (done, out, stream)
-
-        def launch(_args=args, _call=call, _keep=keep):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
-            return out
-
-        return launch
+        args = (C.c_void_p(done.data_ptr()) if done is not None else None, K, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        return _lib.bound_call(self._L.gemx_refgen_rollout_shell, self, args, (done, out, stream), out)
 
     def step(self, done=None, out=None):
         """One env-shell step in ONE launch (gemx_refgen_step): the generators of the envs with done[env] != 0 restart, then every
@@ -159,13 +151,12 @@ class _DeviceGenerators:
             out = self._refs
         elif not (torch.is_tensor(out) and tuple(out.shape) == tuple(self._refs.shape) and out.dtype == self._tdtype and out.device == self._tdev and out.is_contiguous()):
             raise ValueError(f"step: out must be a contiguous {self._tdtype} tensor of shape {tuple(self._refs.shape)} on {self._tdev}")
-        d = None
         if done is not None:
-            d = done if (done.dtype == torch.uint8 and done.device == self._tdev and done.is_contiguous()) else done.to(device=self._tdev, dtype=torch.uint8).contiguous()
-            if d.numel() != self._n_envs:
+            if not (done.dtype == torch.uint8 and done.device == self._tdev and done.is_contiguous()):
+                done = done.to(device=self._tdev, dtype=torch.uint8).contiguous()
+            if done.numel() != self._n_envs:
                 raise ValueError(f"step: done must have {self._n_envs} elements")
-        _lib.check(self._L.gemx_refgen_step(self._handle, C.c_void_p(d.data_ptr()) if d is not None else None, C.c_void_p(out.data_ptr()), self._stream()))
-        return out
+        return self._bind_step(done, out, None)()
 
     def bind_step(self, done, stream=None):
         """-> zero-argument step(): `gemx_refgen_step(done) -> references` with the handle, both pointers and the stream resolved once."""
@@ -173,18 +164,14 @@ class _DeviceGenerators:
 
         if not (torch.is_tensor(done) and done.dtype == torch.uint8 and done.device == self._tdev and done.is_contiguous() and done.numel() == self._n_envs):
             raise ValueError(f"bind_step needs a contiguous uint8 tensor of {self._n_envs} elements on {self._tdev}")
+        return self._bind_step(done, self._refs, stream)
+
+    def _bind_step(self, done, out, stream):
+        import torch
+
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
-        call, check, refs = self._L.gemx_refgen_step, _lib.check, self._refs
-        args = (C.c_void_p(done.data_ptr()), C.c_void_p(refs.data_ptr()), C.c_void_p(stream.cuda_stream))
-        keep = (done, stream)
-
-        def step(_args=args, _call=call, _keep=keep):
-            rc = _call(self._handle, *_args)
-            if rc:
-                check(rc)
-            return refs
-
-        return step
+        args = (C.c_void_p(done.data_ptr()) if done is not None else None, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        return _lib.bound_call(self._L.gemx_refgen_step, self, args, (done, out, stream), out)
 
     def apply_done(self, done):
         """After a rollout: envs with any termination in `done` ([K, N] or [N]) restart their generators (closed-loop use)."""

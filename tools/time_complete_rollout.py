@@ -12,6 +12,17 @@ Cont-CC-PMSM-v0 complete env (default Wiener generators, default reward) at --en
 Device time between two events on the launching stream, median over --windows windows (an untimed window first).
 
     python tools/time_complete_rollout.py [--envs 16384] [--steps 1000] [--windows 9]
+
+`--host`: instead, the HOST's share of a call -> the tables of profiles/env_shell_refactor.md.  Python time per call (perf_counter
+around --calls enqueues, the synchronise outside the clock; median, min and max over --repeats such batches, after a warm-up batch)
+of the complete env's `bind_step` closure, its `bind_rollout_complete` closure at K = 1 and eager `step()` on a reused action tensor,
+and of the eager `apply` / `rollout_shell` / `step(done)` of the stage and the generators, for the env without an observation stage
+(PMSM) and with observer + column program (SCIM, FluxObserver, observed_states); one JSON line.
+
+`--against DIR` (a second checkout of the package, e.g. the parent commit's) times both in ONE process, batch by batch alternately:
+host clocks and core placement move a whole process by 20 % from run to run, which is more than any difference between two shells.
+
+    python tools/time_complete_rollout.py --host [--envs 4096] [--calls 200] [--repeats 60] [--against DIR]
 """
 import argparse
 import ctypes as C
@@ -39,6 +50,68 @@ def timed(fn, windows, stream=None):
     return statistics.median(ms)
 
 
+def _load_package(root, name):
+    """The package of another checkout under another module name (its imports are relative; both use the library loaded first)."""
+    import importlib.util
+
+    pkg = os.path.join(root, "gym_electric_motor_amd")
+    spec = importlib.util.spec_from_file_location(name, os.path.join(pkg, "__init__.py"), submodule_search_locations=[pkg])
+    mod = importlib.util.module_from_spec(spec)
+    sys.modules[name] = mod
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def host_overhead(packages, torch, n, calls, repeats):
+    """packages: {label: package}; every row is timed on all of them alternately, batch by batch."""
+    import json
+    import time
+
+    def per_call(fns):
+        us = {label: [] for label in fns}
+        for r in range(repeats + 1):
+            for label, fn in (list(fns.items())[::-1] if r % 2 else fns.items()):  # (the order within a pair alternates too)
+                t0 = time.perf_counter()
+                for _ in range(calls):
+                    fn()
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                if r:
+                    us[label].append((t1 - t0) / calls * 1e6)
+        return {label: dict(median=round(statistics.median(v), 3), min=round(min(v), 3), max=round(max(v), 3)) for label, v in us.items()}
+
+    def rows_of(ga, env_id, kw):
+        env = ga.make(env_id, n_envs=n, reference_generator="default", seed=1, **kw(ga))
+        env.reset()
+        action = torch.full((n, 3), 0.01, device="cuda")
+        sh = env._complete_shapes(1)
+        outs = [torch.empty(s, device="cuda") for s in sh[:3]] + [torch.empty(sh[3], dtype=torch.uint8, device="cuda")]
+        gen, stage = env.reference_generator, env.observation_stage
+        done = torch.zeros(n, dtype=torch.uint8, device="cuda")
+        done1, refs1 = done.view(1, n), outs[1]
+        rows = {"bind_step closure": env.bind_step(action)[0],
+                "bind_rollout_complete closure, K = 1": env.bind_rollout_complete(action.view(1, n, 3), *outs),
+                "eager step(), reused action tensor": lambda: env.step(action),
+                "eager generator step(done)": lambda: gen.step(done),
+                "eager generator rollout_shell(1, done, out)": lambda: gen.rollout_shell(1, done1, out=refs1)}
+        if stage is not None:
+            state, post = torch.zeros((n, stage.n_in), device="cuda"), torch.zeros((n, stage.n_out), device="cuda")
+            rows["eager stage apply(state, refs, out)"] = lambda: stage.apply(state, gen.references, out=post)
+        return env, rows
+
+    shapes = {"no stage": ("Cont-CC-PMSM-v0", lambda ga: dict()),
+              "observer + program": ("Cont-CC-SCIM-v0", lambda ga: dict(physical_system_wrappers=(ga.FluxObserver(),),
+                                                                        observed_states=["omega", "i_sd", "i_sq", "psi_abs", "psi_angle"]))}
+    out = dict(envs=n, calls=calls, repeats=repeats, unit="us of Python per call", rows={})
+    for name, (env_id, kw) in shapes.items():
+        built = {label: rows_of(ga, env_id, kw) for label, ga in packages.items()}
+        first = next(iter(built.values()))[1]
+        out["rows"][name] = {row: per_call({label: rows[row] for label, (_, rows) in built.items()}) for row in first}
+        for env, _ in built.values():
+            env.close()
+    print(json.dumps(out))
+
+
 def main():
     import torch
 
@@ -46,11 +119,20 @@ def main():
     from gym_electric_motor_amd import _lib
 
     ap = argparse.ArgumentParser()
-    ap.add_argument("--envs", type=int, default=16384)
+    ap.add_argument("--envs", type=int, default=None, help="default: 16384, with --host 4096")
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--windows", type=int, default=9)
+    ap.add_argument("--host", action="store_true", help="Python time per call of the env shell's bound and eager forms (one JSON line)")
+    ap.add_argument("--calls", type=int, default=200)
+    ap.add_argument("--repeats", type=int, default=60)
+    ap.add_argument("--against", metavar="DIR", default=None, help="with --host: another checkout whose package is timed alternately in the same process")
     args = ap.parse_args()
-    n, K = args.envs, args.steps
+    if args.host:
+        packages = {"this": ga}
+        if args.against:
+            packages["against"] = _load_package(args.against, "gym_electric_motor_amd_against")
+        return host_overhead(packages, torch, args.envs or 4096, args.calls, args.repeats)
+    n, K = args.envs or 16384, args.steps
 
     def make():
         env = ga.make("Cont-CC-PMSM-v0", n_envs=n, reference_generator="default", seed=1)
