@@ -5,20 +5,21 @@ import sys
 import numpy as np
 import pytest
 
-from flux_fixtures import CASES, DQ_CASES, holders, load
+from flux_fixtures import CASES, DQ_CASES, DQ_RUNS, PARAM_CASES, RUNS, holders, load_any, load_runs, make_kwargs
+from parity_contract import FLUX_FLOOR, TOL_FP32
 
 TOL = 1e-12  # what the oracle is held to
 
 
 def _env(ga, d, **kw):
-    return ga.make(d["meta"]["env_id"], n_envs=4, _defer_create=True, physical_system_wrappers=holders(ga, d["meta"]["chain"]), **kw)
+    return ga.make(d["meta"]["env_id"], n_envs=4, _defer_create=True, physical_system_wrappers=holders(ga, d["meta"]["chain"]), **make_kwargs(d), **kw)
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + RUNS)
 def test_host_evaluate_reproduces_the_reference(case):
     import gym_electric_motor_amd as ga
 
-    d = load(case)
+    d = load_any(case)
     env = _env(ga, d)
     flux, nb = env.flux, env.flux.n_in
     assert flux.auto_reset and flux.angle_advance == 0.5 + d["meta"]["dead_time"]
@@ -32,11 +33,11 @@ def test_host_evaluate_reproduces_the_reference(case):
     assert err.max() <= TOL
 
 
-@pytest.mark.parametrize("case", DQ_CASES)
+@pytest.mark.parametrize("case", DQ_CASES + DQ_RUNS)
 def test_host_actions_reproduce_the_reference(case):
     import gym_electric_motor_amd as ga
 
-    d = load(case)
+    d = load_any(case)
     flux = _env(ga, d).flux
     nb = flux.n_in
     flux.set_reset_observation(d["reset_state"])
@@ -50,11 +51,11 @@ def test_host_actions_reproduce_the_reference(case):
     assert worst <= TOL
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + RUNS)
 def test_metadata_matches_the_reference(case):
     import gym_electric_motor_amd as ga
 
-    d = load(case)
+    d = load_any(case)
     env = _env(ga, d)
     st = env.observation_stage
     assert st.state_names == d["state_names"] and env.state_names == d["state_names"]
@@ -63,6 +64,84 @@ def test_metadata_matches_the_reference(case):
     width = d["actions"].shape[1]
     assert env.action_space.shape == (width,) and np.all(env.action_space.low == -1) and np.all(env.action_space.high == 1)
     assert list(env.physical_system.state_names) == d["state_names"][:-2]  # (the system itself stays raw)
+
+
+def _host_misses(flux, d):
+    """How far the host restatement of `flux` is from one recorded run: (psi_abs, psi_angle -- circular, weighted as the contract weighs
+    it --, abc actions), each in the normalised units the tolerances are stated in."""
+    nb = flux.n_in
+    flux.set_reset_observation(d["reset_state"])
+    flux.host_reset(1)
+    K = len(d["actions"])
+    got, abc = np.empty((K, 2)), 0.0
+    for k in range(K):
+        if flux.action_mode:
+            abc = max(abc, float(np.abs(flux.host_actions(d["actions"][k])[0] - d["abc_actions"][k]).max()))
+        got[k] = flux.evaluate(d["state"][k:k + 1, :nb], done=d["terminated"][k:k + 1])[0, nb:]
+    ref = d["state"][:, nb:]
+    circ = np.abs(got[:, 1] - ref[:, 1])
+    circ = np.minimum(circ, 2.0 - circ) * np.minimum(1.0, ref[:, 0] / (FLUX_FLOOR * ref[:, 0].max()))
+    return float(np.abs(got[:, 0] - ref[:, 0]).max()), float(circ.max()), abc
+
+
+def _mutants(flux, d):
+    """name -> (attribute, deliberately wrong value | None where the wrong value is the right one) for the stage of one fixture"""
+    mp = d["meta"]["overrides"].get("motor", {}).get("motor_parameter", {})
+    names = d["state_names"]
+    nominal_psi = flux.l_m * float(d["nominal_state"][names.index("i_sd")])
+    plain = [names.index(c) for c in ("i_sa", "i_sb", "i_sc")]
+
+    def other(value, wrong):
+        return None if value == wrong else wrong
+
+    return {
+        "l_r from l_sigs": ("l_r", other(flux.l_r, flux.l_m + mp["l_sigs"]) if mp else None),
+        "p = 2": ("p", other(flux.p, 2.0)),
+        "tau = 1e-4": ("tau", other(flux.tau, 1e-4)),
+        "dead time forgotten": ("angle_advance", other(flux.angle_advance, 0.5)),
+        "currents unpermuted": ("current_indices", other(flux.current_indices, plain)),
+        "psi_limit from the nominal i_sd": ("psi_limit", other(flux.psi_limit, nominal_psi)),
+    }
+
+
+def test_every_mutant_is_seen_by_a_new_fixture():
+    """The new recordings can see a folding mistake: one deliberately wrong attribute on the FluxObserverStage instance (the product code
+    stays as it is) puts the host restatement more than 10 * TOL_FP32 away from at least one run, in psi_abs, psi_angle or the abc
+    actions -- ten times what the device is allowed, so the GPU comparison against the same recordings sees it as well.  Unmutated, every
+    run is reproduced to 1e-12 (test_host_evaluate_reproduces_the_reference, test_host_actions_reproduce_the_reference)."""
+    import gym_electric_motor_amd as ga
+
+    need = 10 * TOL_FP32
+    worst, seen_by = {}, {}
+    for case in PARAM_CASES:
+        runs = load_runs(case)
+        for name in _mutants(_env(ga, runs[0]).flux, runs[0]):
+            for r, d in enumerate(runs):
+                flux = _env(ga, d).flux
+                attr, wrong = _mutants(flux, d)[name]
+                if wrong is None:  # (this fixture's machine has the wrong value as its right one)
+                    continue
+                setattr(flux, attr, wrong)
+                miss = max(_host_misses(flux, d))
+                worst[name] = max(worst.get(name, 0.0), miss)
+                if miss > need:
+                    seen_by.setdefault(name, []).append(f"{case}-run{r}")
+    for name, miss in worst.items():
+        print(f"mutant '{name}': worst miss {miss:.2e}, seen by {seen_by.get(name, [])}")
+    expected = {"l_r from l_sigs", "p = 2", "tau = 1e-4", "dead time forgotten", "currents unpermuted", "psi_limit from the nominal i_sd"}
+    if "psi_limit from the nominal i_sd" not in worst:
+        print("NOTE: the nominal and the limit of i_sd are equal in every new fixture: the psi_limit mutant cannot be told apart and is skipped")
+        expected.discard("psi_limit from the nominal i_sd")
+    assert set(worst) >= expected, sorted(expected - set(worst))
+    assert all(name in seen_by for name in expected), {n: worst[n] for n in expected if n not in seen_by}
+    # each mistake has a fixture made for it: the pole pairs and the control step in every `param` case, the leakage swap in the two
+    # with tau = 2e-4 (at 5e-5 the 200 steps are 10 ms, too short for the rotor time constant to show beyond 1e-3), the dead time in the
+    # dead-time case, the current order in the permuted one
+    for name in ("p = 2", "tau = 1e-4"):
+        assert all(any(s.startswith(c) for s in seen_by[name]) for c in PARAM_CASES[:3]), name
+    assert all(any(s.startswith(c) for s in seen_by["l_r from l_sigs"]) for c in PARAM_CASES[1:3])
+    assert any(s.startswith("flux_param_scim_dq_dead2") for s in seen_by["dead time forgotten"])
+    assert any(s.startswith("flux_scim_abc_perm") for s in seen_by["currents unpermuted"])
 
 
 def test_chain_order():

@@ -1,15 +1,32 @@
 """FluxObserver and flux-oriented dq actions on the device (csrc/gemx_fluxobs.hip) against the float64 host restatement and the
 reference's recorded runs.  Shapes: N in {1, 65, 257} (one lane, a partial wave, a partial second workgroup... of 64-lane workgroups: 1, 2
-and 5 of them), K in {1, 2, 37}, SCIM rows of 14 and DFIM rows of 24 columns, fp32 and fp64."""
+and 5 of them), K in {1, 2, 37} and, around the ring of four tiles, {3, 4, 5, 8}, SCIM rows of 14 and DFIM rows of 24 columns, fp32 and
+fp64.  The actions kernel (256-thread workgroups) at N in {1, 257, 600}; the closed loops with distinct lanes at N = 67 and 259."""
 import numpy as np
 import pytest
 
-from flux_fixtures import DQ_CASES, holders, load
+from flux_fixtures import DQ_CASES, PARAM_CASES, holders, load, load_runs, make_kwargs
 from parity_contract import DONE_MARGIN, FLUX_FLOOR, REL_FLOOR, TOL_FP32, TOL_FP64_SAME_INTEGRATOR
 
 pytestmark = pytest.mark.gpu
 TOL = {"float32": TOL_FP32, "float64": TOL_FP64_SAME_INTEGRATOR}
+TOL_RECORDED = {"float32": TOL_FP32, "float64": 1e-7}  # against a recording with the same integrator (as tests/test_gpu_constraints.py: TOL_FP64)
+EPS = {"float32": 2.0 ** -24, "float64": 2.0 ** -53}
 ENV = {"SCIM": "Cont-CC-SCIM-v0", "DFIM": "Cont-CC-DFIM-v0"}
+_T32 = np.array([[1.0, 0.0], [-0.5, 0.5 * np.sqrt(3.0)], [-0.5, -0.5 * np.sqrt(3.0)]])
+
+
+def _handle(motor, dtype, n, auto_reset=True, reset_row=None):
+    """A device handle of the observer with the dq action stage, as test_rows_equal_steps_bit_for_bit creates it; reset_row: the
+    system's (normalised) reset observation, which sets the frames a reset leaves."""
+    import gym_electric_motor_amd as ga
+
+    flux = ga.make(ENV[motor], n_envs=n, dtype=dtype, auto_reset=auto_reset, _defer_create=True,
+                   physical_system_wrappers=(ga.FluxObserver(), ga.FluxOrientedDqToAbcActionProcessor(motor))).flux
+    assert flux.auto_reset == auto_reset
+    if reset_row is not None:
+        flux.set_reset_observation(reset_row)
+    return flux.create(n, 0, dtype)
 
 
 def _col_err(got, ref, dtype):
@@ -82,7 +99,8 @@ def test_rows_equal_steps_bit_for_bit(motor, dtype, n):
         numel = int(np.prod(shape))
         return torch.empty(numel + 4, dtype=tdtype, device="cuda")[off:off + numel].view(shape)
 
-    for K, off in ((1, 0), (2, 1), (37, 0), (37, 1)):
+    # (at N = 65 also around the ring of FLUX_DEPTH = 4 tiles: below its depth, equal to it, one beyond it, twice it)
+    for K, off in ((1, 0), (2, 1), (37, 0), (37, 1)) + (((3, 0), (4, 1), (5, 0), (8, 1)) if n == 65 else ()):
         state = view((K, n, nb), off)
         state.copy_(torch.rand((K, n, nb), generator=g, device="cuda", dtype=tdtype) * 2 - 1)
         done = (torch.rand((K, n), generator=g, device="cuda") < 0.1).to(torch.uint8)
@@ -140,6 +158,193 @@ def test_closed_loop_against_the_reference(case):
     print(case, {k: f"{v:.2e}" for k, v in worst.items()})
     assert max(worst.values()) <= TOL_FP32, worst
     env.close()
+
+
+CLOSED_LOOPS = [(case, 67, dtype) for case in PARAM_CASES for dtype in ("float32", "float64")] + [("flux_param_scim_dq_dead2", 259, "float32")]
+
+
+@pytest.mark.parametrize("case,n,dtype", CLOSED_LOOPS)
+def test_closed_loop_against_the_new_recordings(case, n, dtype):
+    """Non-default machines, a negative speed, a dead time of two steps, permuted currents; lane i replays run i % 3 of the fixture and is
+    compared with its own recording.  N = 67: a partial second wave of the rows kernel; N = 259: two workgroups of the actions kernel.
+    The env integrates with the EulerSolver, as the recording did."""
+    import torch
+
+    import gym_electric_motor_amd as ga
+
+    runs = load_runs(case)
+    d0 = runs[0]
+    tdtype = getattr(torch, dtype)
+    env = ga.make(d0["meta"]["env_id"], n_envs=n, dtype=dtype, ode_solver=ga.EulerSolver(), physical_system_wrappers=holders(ga, d0["meta"]["chain"]), **make_kwargs(d0))
+    nb, names = env.flux.n_in, d0["state_names"]
+    assert env.physical_system.tau == d0["meta"]["tau"] and env.flux.angle_advance == 0.5 + d0["meta"]["dead_time"]
+    K = len(d0["actions"])
+    a = torch.as_tensor(np.stack([runs[i % 3]["actions"] for i in range(n)], axis=1), dtype=tdtype, device="cuda")
+    state, _ = env.reset()
+    torch.cuda.synchronize()
+    assert np.abs(state.double().cpu().numpy() - d0["reset_state"]).max() <= TOL_RECORDED[dtype]
+    rows, dones = torch.empty((K, n, nb + 2), dtype=tdtype, device="cuda"), torch.empty((K, n), dtype=torch.uint8, device="cuda")
+    for k in range(K):
+        state, _, done, _, _ = env.step(a[k])
+        rows[k].copy_(state)
+        dones[k].copy_(done)
+    torch.cuda.synchronize()
+    for i in range(3, n):  # lanes of the same run: the same bits
+        assert torch.equal(rows[:, i], rows[:, i % 3]) and torch.equal(dones[:, i], dones[:, i % 3]), i
+    for i, j in ((0, 1), (0, 2), (1, 2)):  # lanes of different runs: different trajectories
+        assert not torch.equal(rows[:, i], rows[:, j])
+    rows, dones = rows.double().cpu().numpy(), dones.cpu().numpy()
+    worst = {}
+    for r in range(3):
+        got, ref, term = rows[:, r], runs[r]["state"], runs[r]["terminated"]
+        # done flags: exact outside the contract's margin (the squared current constraint of the reference, on normalised currents)
+        radius = np.hypot(ref[:, names.index("i_sd")], ref[:, names.index("i_sq")])
+        clear = np.abs(radius - 1.0) > DONE_MARGIN
+        assert np.array_equal(dones[clear, r] != 0, term[clear] != 0), r
+        for j, name in enumerate(names[:nb]):
+            delta = np.abs(got[:, j] - ref[:, j])
+            if name == "epsilon":
+                delta = np.minimum(delta, 2.0 - delta)
+            e = float(delta.max()) / max(float(np.abs(ref[:, j]).max()), REL_FLOOR) if dtype == "float32" else float(delta.max())
+            worst[name] = max(worst.get(name, 0.0), e)
+        for key, e in zip(("psi_abs", "Psi", "psi_angle"), _flux_errors(got[:, nb:], ref[:, nb:], dtype)):
+            worst[key] = max(worst.get(key, 0.0), e)
+    top = max(worst, key=worst.get)
+    print(f"{case} {dtype} N={n}: worst column {top} {worst[top]:.2e}; psi_abs {worst['psi_abs']:.2e} Psi {worst['Psi']:.2e} psi_angle {worst['psi_angle']:.2e}; "
+          f"{int(dones[:, :3].sum())} terminations in three runs")
+    assert max(worst.values()) <= TOL_RECORDED[dtype], worst
+    env.close()
+
+
+@pytest.mark.parametrize("n", [1, 257, 600])
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("motor", ["SCIM", "DFIM"])
+def test_actions_kernel_lane_by_lane(motor, dtype, n):
+    """abc = t_32(q(dq, frame)) of every lane against numpy float64, with per-lane frames in +-3 pi and per-lane dq actions.  The bound
+    is derived: the frame is read as the kernel reads it (rounded to the tensor's type), so what is left is sincos (at most 2 ulp of a
+    value of at most 1) and the roundings of two short product chains (the rotation, then -al / 2 +- sqrt(3) / 2 be with the constant
+    rounded to the type): 16 eps hypot(d, q) per pair."""
+    import torch
+
+    tdtype = getattr(torch, dtype)
+    flux = _handle(motor, dtype, n)
+    pairs = {"SCIM": 1, "DFIM": 2}[motor]
+    rng = np.random.default_rng(21)
+    st = np.concatenate((rng.uniform(-1.0, 1.0, (2, n)), rng.uniform(-3.0 * np.pi, 3.0 * np.pi, (2, n))))
+    flux.set_state(st)
+    dq = torch.as_tensor(rng.uniform(-1.0, 1.0, (n, 2 * pairs)), dtype=tdtype, device="cuda")
+    sentinel = -7.25
+    buf = torch.full((n + 1, 3 * pairs), sentinel, dtype=tdtype, device="cuda")  # one row beyond N: must stay untouched
+    flux.bind_actions(dq, buf[:n])()
+    torch.cuda.synchronize()
+    assert bool((buf[n] == sentinel).all())
+    assert np.array_equal(flux.get_state().cpu().numpy(), st)  # (the kernel only reads the lane state)
+    got, dqv = buf[:n].double().cpu().numpy(), dq.double().cpu().numpy()
+    frames = torch.as_tensor(st[2:]).to(tdtype).double().numpy()
+    worst = 0.0
+    for j in range(pairs):
+        d, q, c, s_ = dqv[:, 2 * j], dqv[:, 2 * j + 1], np.cos(frames[j]), np.sin(frames[j])
+        want = np.stack((c * d - s_ * q, s_ * d + c * q), axis=-1) @ _T32.T
+        ratio = np.abs(got[:, 3 * j:3 * j + 3] - want).max(axis=-1) / (EPS[dtype] * np.hypot(d, q))
+        worst = max(worst, float(ratio.max()))
+    print(f"{motor} {dtype} N={n}: actions kernel, worst error {worst:.2f} eps hypot(d, q)")
+    assert worst <= 16.0
+    flux.close()
+
+
+@pytest.mark.parametrize("n", [65, 257])
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("motor", ["SCIM", "DFIM"])
+def test_frames_after_a_rows_pass(motor, dtype, n):
+    """The lane state a rows pass leaves (Psi and the frames the next action is rotated by) against the host restatement on the same
+    rows.  Psi is fp64 on both sides; the frames are evaluated in the row's type, from Psi rounded to it."""
+    import torch
+
+    tdtype = getattr(torch, dtype)
+    rng = np.random.default_rng(31)
+    nb = {"SCIM": 14, "DFIM": 24}[motor]
+    flux = _handle(motor, dtype, n, reset_row=rng.uniform(-0.5, 0.5, nb))
+    assert flux.n_in == nb
+    fresh = flux.get_state().cpu().numpy()  # what a reset leaves: Psi = 0 and the reset frames, every lane the same
+    assert np.all(fresh[:2] == 0.0) and np.all(fresh[2:] == fresh[2:, :1]) and fresh[2, 0] != 0.0
+    flux.host_reset(n)
+    assert np.all(np.abs(fresh[2:] - flux._frame) <= 16.0 * EPS[dtype] * (np.abs(flux._frame) + np.pi))
+    worst_psi, worst_frame, n_reset = 0.0, 0.0, 0
+    for K in (1, 5, 37):
+        state = torch.as_tensor(rng.uniform(-1.0, 1.0, (K, n, nb)), dtype=tdtype, device="cuda")
+        done = torch.as_tensor((rng.uniform(size=(K, n)) < 0.1).astype(np.uint8), device="cuda")
+        flux.rows(state, done)
+        torch.cuda.synchronize()
+        flux.evaluate(state.double().cpu().numpy(), done.cpu().numpy())
+        st = flux.get_state().cpu().numpy()
+        e_psi = max(float(np.abs(st[0] - flux._psi.real).max()), float(np.abs(st[1] - flux._psi.imag).max())) / flux.psi_limit
+        host = flux._frame
+        e_frame = np.maximum(np.abs(np.cos(st[2:]) - np.cos(host)), np.abs(np.sin(st[2:]) - np.sin(host))) / (EPS[dtype] * (np.abs(host) + np.pi))
+        worst_psi, worst_frame = max(worst_psi, e_psi), max(worst_frame, float(e_frame.max()))
+        last = done[K - 1].cpu().numpy() != 0  # lanes reset behind the last row: exactly 0 and the reset frames
+        assert np.all(st[:2, last] == 0.0) and np.array_equal(st[2:, last], fresh[2:, last]), K
+        assert np.all(st[:2, ~last] != 0.0)
+        n_reset += int(last.sum())
+    print(f"{motor} {dtype} N={n}: Psi {worst_psi:.2e} psi_limit, frames {worst_frame:.2f} eps (|frame| + pi); {n_reset} lanes reset behind a last row")
+    assert n_reset > 0 and worst_psi <= 1e-12 and worst_frame <= 16.0
+    flux.close()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("motor", ["SCIM", "DFIM"])
+def test_done_none_equals_an_all_zero_done(motor, dtype):
+    """`done = None` (the `safe` pointer path of flux_tile_load) gives the bits of an all-zero done tensor: `rows` around the ring depth
+    and `step`, outputs and lane state."""
+    import torch
+
+    tdtype, n = getattr(torch, dtype), 65
+    fa, fb = _handle(motor, dtype, n), _handle(motor, dtype, n)
+    nb = fa.n_in
+    g = torch.Generator(device="cuda").manual_seed(13)
+    for K in (1, 5, 8):
+        state = torch.rand((K, n, nb), generator=g, device="cuda", dtype=tdtype) * 2 - 1
+        out_a = fa.rows(state, None)
+        out_b = fb.rows(state, torch.zeros((K, n), dtype=torch.uint8, device="cuda"))
+        torch.cuda.synchronize()
+        assert torch.equal(out_a, out_b) and torch.equal(out_a[..., :nb], state), K
+        assert torch.equal(fa.get_state(), fb.get_state()), K
+    state = torch.rand((n, nb), generator=g, device="cuda", dtype=tdtype) * 2 - 1
+    out_a = fa.step(state, None, torch.empty((n, nb + 2), dtype=tdtype, device="cuda"))
+    out_b = fb.step(state, torch.zeros(n, dtype=torch.uint8, device="cuda"), torch.empty((n, nb + 2), dtype=tdtype, device="cuda"))
+    torch.cuda.synchronize()
+    assert torch.equal(out_a, out_b) and torch.equal(fa.get_state(), fb.get_state())
+    assert bool((fa.get_state()[:2] != 0).all())  # (nothing was reset)
+    fa.close()
+    fb.close()
+
+
+@pytest.mark.parametrize("dtype", ["float32", "float64"])
+@pytest.mark.parametrize("motor", ["SCIM", "DFIM"])
+def test_auto_reset_off_ignores_the_done_mask(motor, dtype):
+    """A handle created with auto_reset = False and fed a done mask gives the bits of `done = None`, and what the host restatement gives
+    (within the tolerances of test_observer_arithmetic_alone)."""
+    import torch
+
+    tdtype, n = getattr(torch, dtype), 65
+    fa, fb = _handle(motor, dtype, n, auto_reset=False), _handle(motor, dtype, n, auto_reset=False)
+    nb = fa.n_in
+    g = torch.Generator(device="cuda").manual_seed(17)
+    fa.host_reset(n)
+    worst = np.zeros(3)
+    for K in (5, 37):
+        state = torch.rand((K, n, nb), generator=g, device="cuda", dtype=tdtype) * 2 - 1
+        done = (torch.rand((K, n), generator=g, device="cuda") < 0.1).to(torch.uint8)
+        assert int(done.sum()) > 0 and int(done[K - 1].sum()) > 0
+        out_a, out_b = fa.rows(state, done), fb.rows(state, None)
+        torch.cuda.synchronize()
+        assert torch.equal(out_a, out_b) and torch.equal(fa.get_state(), fb.get_state()), K
+        want = fa.evaluate(state.double().cpu().numpy(), done.cpu().numpy())
+        worst = np.maximum(worst, _flux_errors(out_a[..., nb:].double().cpu().numpy(), want[..., nb:], dtype))
+    print(f"{motor} {dtype} auto_reset off: psi_abs {worst[0]:.2e} Psi {worst[1]:.2e} psi_angle {worst[2]:.2e}")
+    assert worst.max() <= TOL[dtype], worst
+    assert bool((fa.get_state()[:2] != 0).all())
+    fa.close()
+    fb.close()
 
 
 def _complete(ga, n, **kw):
