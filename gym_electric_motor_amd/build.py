@@ -6,7 +6,8 @@ Sources (gym_electric_motor_amd/csrc):
                                         libgemx_u<S>_<C>_<F>.so, which gemx_create loads with dlopen (round 6: a handle maps the C ABI and
                                         the one unit it runs, not all 38)
     gemx_capi.hip                       C ABI (include/gemx.h), validation, small kernels, unit loader  } libgemx.so
-    gemx_refgen.hip                     device-side Wiener-process reference generation (gemx_refgen_*) }
+    gemx_support.hpp                    row tile in LDS and entry-point checks of the four support units below (SUPPORT) }
+    gemx_refgen.hip                     device-side reference generators: Wiener, the other kinds, switched (gemx_refgen_*) }
     gemx_obsproc.hip                    device-side observation stage (gemx_obsproc_*)                  }
     gemx_fluxobs.hip                    device-side FluxObserver and flux-oriented dq actions (gemx_fluxobs_*) }
     gemx_rewardpass.hip                 reward pass over a stored trajectory (gemx_reward_rows)         }
@@ -22,7 +23,10 @@ import subprocess
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
-SOURCES = [os.path.join(CSRC, f) for f in ("gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_refgen.hip", "gemx_obsproc.hip", "gemx_fluxobs.hip", "gemx_rewardpass.hip")]
+# the support objects of libgemx.so beside the C ABI: (name, source, headers beside gemx_common.hpp, compile cost)
+SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc", "gemx_obsproc.hip", ["gemx_support.hpp"], 0.1),
+           ("fluxobs", "gemx_fluxobs.hip", ["gemx_support.hpp"], 0.1), ("rewardpass", "gemx_rewardpass.hip", ["gemx_support.hpp"], 0.1)]
+SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")
 
@@ -59,8 +63,7 @@ def _digest(sources=None, header=None):
 
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
 _DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_capi.hip"],
-         "refgen": ["gemx_common.hpp", "gemx_refgen.hip"], "obsproc": ["gemx_common.hpp", "gemx_obsproc.hip"], "fluxobs": ["gemx_common.hpp", "gemx_fluxobs.hip"],
-         "rewardpass": ["gemx_common.hpp", "gemx_rewardpass.hip"]}
+         **{name: ["gemx_common.hpp"] + headers + [src] for name, src, headers, _ in SUPPORT}}
 # compile cost of an fp32 unit by system kind (object size, MB: induction > synchronous > DC); fp64 units take the single-wave kernel only
 _COST = {7: 6.0, 2: 5.3, 6: 4.9, 1: 4.5, 5: 4.0, 4: 3.9, 3: 3.5, 0: 3.5}
 
@@ -114,16 +117,11 @@ def _build_locked(hipcc, force, verbose, jobs):
             out = unit_lib(s, c, f64)
             cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", f"-DGEMX_INST_F64={f64}", "-fvisibility=hidden",
                                                       "-shared", os.path.join(csrc, "gemx_inst.hip"), "-o", out], "inst", _COST[s] * (0.15 if f64 else 1.0)))
-    capi_obj = os.path.join(OBJ_DIR, "gemx_capi.o")
-    cmds.append((capi_obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, "gemx_capi.hip"), "-o", capi_obj], "capi", 0.3))
-    refgen_obj = os.path.join(OBJ_DIR, "gemx_refgen.o")
-    cmds.append((refgen_obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, "gemx_refgen.hip"), "-o", refgen_obj], "refgen", 0.2))
-    obsproc_obj = os.path.join(OBJ_DIR, "gemx_obsproc.o")
-    cmds.append((obsproc_obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, "gemx_obsproc.hip"), "-o", obsproc_obj], "obsproc", 0.1))
-    fluxobs_obj = os.path.join(OBJ_DIR, "gemx_fluxobs.o")
-    cmds.append((fluxobs_obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, "gemx_fluxobs.hip"), "-o", fluxobs_obj], "fluxobs", 0.1))
-    rewardpass_obj = os.path.join(OBJ_DIR, "gemx_rewardpass.o")
-    cmds.append((rewardpass_obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, "gemx_rewardpass.hip"), "-o", rewardpass_obj], "rewardpass", 0.1))
+    objects = []  # of libgemx.so
+    for name, src, cost in [("capi", "gemx_capi.hip", 0.3)] + [(u[0], u[1], u[3]) for u in SUPPORT]:
+        obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
+        objects.append(obj)
+        cmds.append((obj, [hipcc] + FLAGS + inc + ["-c", os.path.join(csrc, src), "-o", obj], name, cost))
     digests = {k: _digest([os.path.join(csrc, f) for f in v], snap_header) for k, v in _DEPS.items()}
 
     def run(cmd):
@@ -143,7 +141,7 @@ def _build_locked(hipcc, force, verbose, jobs):
     jobs = jobs or min(len(cmds), os.cpu_count() or 4)
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:  # longest first: the big induction-machine units do not end up as the tail
         list(ex.map(compile_one, sorted(cmds, key=lambda j: -j[3])))
-    run([hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-o", LIB, capi_obj, refgen_obj, obsproc_obj, fluxobs_obj, rewardpass_obj, "-ldl"])
+    run([hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-o", LIB] + objects + ["-ldl"])
     for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
         if stale not in [j[0] for j in cmds]:
             os.remove(stale)

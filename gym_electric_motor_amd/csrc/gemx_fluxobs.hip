@@ -20,30 +20,25 @@
 // multiple of four dwords) and for no k at all in a view at an odd element offset: EVERY tile is moved as up to three single dwords
 // up to the first 16-byte boundary, whole 16-byte units, and up to three single dwords behind the last one.  Nothing outside the tile
 // is read or written; a lane with no unit of its own loads from the handle's own state array instead of branching around the load.
-#include "gemx_common.hpp"
-
-void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
+#include "gemx_support.hpp"
 
 namespace {
+
+using namespace gemx;  // the row tile: gemx_support.hpp
 
 constexpr int FLUX_LANES = 64;  // one wave per workgroup
 constexpr int FLUX_DEPTH = 4;   // tiles in flight ahead of the recursion in gemx_fluxobs_rows
 
 struct FluxParams {
     int32_t n_in, omega, cur[3], eps, mode, auto_reset;
-    uint32_t magic_in, magic_out;  // floor(2^32 / L) + 1 for the row length L in dwords, as in gemx_obsproc.hip
+    uint32_t magic_in, magic_out;  // tile_magic of the row lengths in dwords
     double lim_omega, lim_cur[3], lim_eps, psi_limit;
     double p, tau, k_i, k_psi, adv_tau_p;  // adv_tau_p = (0.5 + dead time) tau p
     double reset_f0, reset_f1;             // the frames right after a reset
 };
 
-// tile-local dword index d < 2^14 of a row-major [rows][L] tile -> row (exact for L <= 72)
-__device__ inline uint32_t flux_row_of(uint32_t d, uint32_t magic) { return magic ? __umulhi(d, magic) : d; }
+static_assert(tile_fits(FLUX_LANES, 2 * (GEMX_MAX_OUT + 2)), "the longest output row (fp64) is within tile_row's exactness bound");
 
-__device__ inline float flux_get(const uint32_t *p, float) { return __uint_as_float(p[0]); }
-__device__ inline double flux_get(const uint32_t *p, double) { return __hiloint2double((int)p[1], (int)p[0]); }
-__device__ inline void flux_put(uint32_t *p, float v) { p[0] = __float_as_uint(v); }
-__device__ inline void flux_put(uint32_t *p, double v) { p[0] = (uint32_t)__double2loint(v); p[1] = (uint32_t)__double2hiint(v); }
 __device__ inline float flux_hypot(float a, float b) { return hypotf(a, b); }
 __device__ inline double flux_hypot(double a, double b) { return hypot(a, b); }
 __device__ inline float flux_atan2(float a, float b) { return atan2f(a, b); }
@@ -123,7 +118,8 @@ __device__ inline void flux_tile_load(FluxTile<NV> &t, const uint32_t *g, uint32
     t.done = done ? (uint32_t)*pd : 0u;
 }
 
-// registers -> LDS tile with rows of L dwords at `stride`
+// registers -> LDS tile with rows of L dwords at `stride`.  (This loop and flux_tile_store's are the unit loops of gemx_support.hpp's
+// stagers once more: calling shared unit helpers here, gemx_fluxobs_rows measured 1 - 2 % slower, profiles/support_units_refactor.md.)
 template <int NV>
 __device__ inline void flux_tile_scatter(const FluxTile<NV> &t, uint32_t *tile, uint32_t stride, uint32_t L, uint32_t magic, const uint32_t *g, uint32_t cnt) {
     const FluxSplit s = flux_split(g, cnt);
@@ -132,7 +128,7 @@ __device__ inline void flux_tile_scatter(const FluxTile<NV> &t, uint32_t *tile, 
         const uint32_t v = threadIdx.x + (uint32_t)i * FLUX_LANES;
         if (v < s.nvec) {
             const uint32_t w[4] = {t.v[i].x, t.v[i].y, t.v[i].z, t.v[i].w};
-            const uint32_t d = s.head + v * 4u, row = flux_row_of(d, magic);
+            const uint32_t d = s.head + v * 4u, row = tile_row(d, magic);
             uint32_t col = d - row * L, a = row * stride + col;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -144,7 +140,7 @@ __device__ inline void flux_tile_scatter(const FluxTile<NV> &t, uint32_t *tile, 
     }
     const uint32_t l = threadIdx.x;
     if (l < s.head + s.tail) {
-        const uint32_t d = l < s.head ? l : s.head + s.nvec * 4u + (l - s.head), row = flux_row_of(d, magic);
+        const uint32_t d = l < s.head ? l : s.head + s.nvec * 4u + (l - s.head), row = tile_row(d, magic);
         tile[row * stride + (d - row * L)] = t.e;
     }
 }
@@ -154,7 +150,7 @@ __device__ inline void flux_tile_store(const uint32_t *tile, uint32_t stride, ui
     const FluxSplit s = flux_split(g, cnt);
     uint4 *gv = reinterpret_cast<uint4 *>(g + s.head);
     for (uint32_t v = threadIdx.x; v < s.nvec; v += FLUX_LANES) {
-        const uint32_t d = s.head + v * 4u, row = flux_row_of(d, magic);
+        const uint32_t d = s.head + v * 4u, row = tile_row(d, magic);
         uint32_t col = d - row * L, a = row * stride + col;
         uint32_t w[4];
 #pragma unroll
@@ -167,7 +163,7 @@ __device__ inline void flux_tile_store(const uint32_t *tile, uint32_t stride, ui
     }
     const uint32_t l = threadIdx.x;
     if (l < s.head + s.tail) {
-        const uint32_t d = l < s.head ? l : s.head + s.nvec * 4u + (l - s.head), row = flux_row_of(d, magic);
+        const uint32_t d = l < s.head ? l : s.head + s.nvec * 4u + (l - s.head), row = tile_row(d, magic);
         g[d] = tile[row * stride + (d - row * L)];
     }
 }
@@ -213,13 +209,13 @@ __global__ __launch_bounds__(FLUX_LANES) void flux_rows_kernel(const R *__restri
             __syncthreads();
             if (mine) {
                 uint32_t *row = flux_smem + threadIdx.x * SO;
-                const R w = flux_get(row + (uint32_t)P.omega * DW, R(0));
-                const R ia = flux_get(row + (uint32_t)P.cur[0] * DW, R(0)), ib = flux_get(row + (uint32_t)P.cur[1] * DW, R(0)), ic = flux_get(row + (uint32_t)P.cur[2] * DW, R(0));
-                const R eps = P.eps >= 0 ? flux_get(row + (uint32_t)P.eps * DW, R(0)) : R(0);
+                const R w = tile_get(row + (uint32_t)P.omega * DW, R(0));
+                const R ia = tile_get(row + (uint32_t)P.cur[0] * DW, R(0)), ib = tile_get(row + (uint32_t)P.cur[1] * DW, R(0)), ic = tile_get(row + (uint32_t)P.cur[2] * DW, R(0));
+                const R eps = P.eps >= 0 ? tile_get(row + (uint32_t)P.eps * DW, R(0)) : R(0);
                 R pa, pg;
                 flux_row<R>(P, s, w, ia, ib, ic, eps, dn != 0u, pa, pg);
-                flux_put(row + Li, pa);
-                flux_put(row + Li + DW, pg);
+                tile_put(row + Li, pa);
+                tile_put(row + Li + DW, pg);
             }
             __syncthreads();
             flux_tile_store(flux_smem, SO, Lo, P.magic_out, gout + k * pitch_out, cnt_out);
@@ -256,8 +252,6 @@ __global__ void flux_actions_kernel(const double *__restrict__ hs, const R *__re
         o[2] = R(-0.5) * al - h * be;
     }
 }
-
-uint32_t flux_magic(uint32_t L) { return L <= 1u ? 0u : (uint32_t)((1ull << 32) / L) + 1u; }
 
 }  // namespace
 
@@ -296,8 +290,7 @@ static int flux_launch(gemx_fluxobs *h, const void *state, const uint8_t *done, 
 static int flux_run(gemx_fluxobs *h, const void *state, const uint8_t *done, int32_t K, void *out, void *stream, bool rows) {
     if (!h || !state || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
     if (K < 1) return gemx::fail(GEMX_ERR_ARG, "K must be >= 1");
-    const uintptr_t am = h->f64 ? 7u : 3u;
-    if (((uintptr_t)state & am) || ((uintptr_t)out & am)) return gemx::fail(GEMX_ERR_ARG, "tensors must be aligned to their element size");
+    if (!gemx::elem_aligned(h->f64, state, out)) return gemx::fail_unaligned();
     gemx::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
     return h->f64 ? flux_launch<double>(h, state, done, K, out, st, rows) : flux_launch<float>(h, state, done, K, out, st, rows);
@@ -319,10 +312,7 @@ int gemx_fluxobs_create(const gemx_fluxobs_config *cfg, int64_t n_envs, int dtyp
     if (cfg->action_mode == GEMX_FLUX_ACT_DFIM && (cfg->epsilon_index < 0 || cfg->epsilon_index >= cfg->n_in))
         return gemx::fail(GEMX_ERR_ARG, "the DFIM action mode needs epsilon_index in [0, %d)", cfg->n_in);
     if (!(cfg->psi_limit > 0.0) || !(cfg->tau > 0.0)) return gemx::fail(GEMX_ERR_ARG, "psi_limit and tau must be positive");
-    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
-    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
+    if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     gemx_fluxobs *h = new (std::nothrow) gemx_fluxobs();
     if (!h) return gemx::fail(GEMX_ERR_ALLOC, "out of host memory");
     h->cfg = *cfg; h->n = n_envs; h->device = device; h->f64 = dtype == GEMX_F64; h->hs = nullptr;
@@ -332,7 +322,7 @@ int gemx_fluxobs_create(const gemx_fluxobs_config *cfg, int64_t n_envs, int dtyp
     P.n_in = cfg->n_in; P.omega = cfg->omega_index; P.mode = cfg->action_mode; P.auto_reset = cfg->auto_reset;
     P.eps = cfg->action_mode == GEMX_FLUX_ACT_DFIM ? cfg->epsilon_index : -1;
     for (int i = 0; i < 3; ++i) { P.cur[i] = cfg->current_index[i]; P.lim_cur[i] = cfg->current_limit[i]; }
-    P.magic_in = flux_magic((uint32_t)P.n_in * dw); P.magic_out = flux_magic(((uint32_t)P.n_in + 2u) * dw);
+    P.magic_in = tile_magic((uint32_t)P.n_in * dw); P.magic_out = tile_magic(((uint32_t)P.n_in + 2u) * dw);
     P.lim_omega = cfg->omega_limit; P.lim_eps = cfg->epsilon_limit; P.psi_limit = cfg->psi_limit;
     P.p = cfg->p; P.tau = cfg->tau; P.k_i = cfg->k_current; P.k_psi = cfg->k_flux;
     P.adv_tau_p = cfg->angle_advance * cfg->tau * cfg->p;
@@ -393,8 +383,7 @@ int gemx_fluxobs_rows(gemx_fluxobs *h, const void *state_dev, const uint8_t *don
 int gemx_fluxobs_actions(gemx_fluxobs *h, const void *dq_dev, void *abc_out_dev, void *stream) {
     if (!h || !dq_dev || !abc_out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
     if (h->prm.mode == GEMX_FLUX_ACT_NONE) return gemx::fail(GEMX_ERR_ARG, "the handle was created with action_mode = GEMX_FLUX_ACT_NONE");
-    const uintptr_t am = h->f64 ? 7u : 3u;
-    if (((uintptr_t)dq_dev & am) || ((uintptr_t)abc_out_dev & am)) return gemx::fail(GEMX_ERR_ARG, "tensors must be aligned to their element size");
+    if (!gemx::elem_aligned(h->f64, dq_dev, abc_out_dev)) return gemx::fail_unaligned();
     gemx::DeviceGuard guard(h->device);
     const int32_t pairs = h->prm.mode == GEMX_FLUX_ACT_DFIM ? 2 : 1;
     const int64_t blocks = (h->n + 255) / 256;

@@ -24,11 +24,11 @@
 // element-aligned (a view at an odd offset) takes the dword loop for the whole call, per tensor.  The last, partial tile moves its
 // whole 16-byte units and then single dwords: nothing beyond rows * n_in is read, nothing beyond rows * n_out is written.
 // fp64 rows are moved as pairs of dwords (TILE = 128 rows keeps the two tiles within 64 KiB of LDS for every program).
-#include "gemx_common.hpp"
-
-void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
+#include "gemx_support.hpp"
 
 namespace {
+
+using namespace gemx;  // the row tile: gemx_support.hpp
 
 struct ObsProg {
     int32_t n_in, n_post, n_ref, n_out;      // n_ref: reference columns the kernel appends (0 unless flat); n_out = n_post + n_ref
@@ -38,56 +38,10 @@ struct ObsProg {
 };
 
 template <class R> struct ObsTile { static constexpr int rows = 1024 / (int)sizeof(R); };
+static_assert(tile_fits(ObsTile<double>::rows, 2 * (GEMX_OBS_MAX_POST + GEMX_MAX_REF)) && tile_fits(ObsTile<float>::rows, GEMX_OBS_MAX_POST + GEMX_MAX_REF) &&
+                  GEMX_MAX_OUT <= GEMX_OBS_MAX_POST,
+              "the longest row of either tile is within tile_row's exactness bound");
 
-// tile-local dword index d < 2^14 of a row-major [rows][L] tile -> row (exact: d * (magic * L - 2^32) < 2^32 for L <= 72)
-__device__ inline uint32_t obs_row(uint32_t d, uint32_t magic) { return magic ? __umulhi(d, magic) : d; }
-
-// global (contiguous, `cnt` dwords) -> LDS tile with rows of L dwords at `stride`
-template <int NT> __device__ inline void obs_stage_in(uint32_t *tile, uint32_t stride, uint32_t L, uint32_t magic, const uint32_t *g, uint32_t cnt, int vec) {
-    const uint32_t nvec = vec ? cnt >> 2 : 0u;
-    for (uint32_t v = threadIdx.x; v < nvec; v += NT) {
-        const uint4 q = reinterpret_cast<const uint4 *>(g)[v];
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t d = v * 4u, row = obs_row(d, magic);
-        uint32_t col = d - row * L, a = row * stride + col;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            tile[a] = w[i];
-            ++col; ++a;
-            if (col == L) { col = 0; a += stride - L; }
-        }
-    }
-    for (uint32_t d = nvec * 4u + threadIdx.x; d < cnt; d += NT) {
-        const uint32_t row = obs_row(d, magic);
-        tile[row * stride + (d - row * L)] = g[d];
-    }
-}
-
-template <int NT> __device__ inline void obs_stage_out(const uint32_t *tile, uint32_t stride, uint32_t L, uint32_t magic, uint32_t *g, uint32_t cnt, int vec) {
-    const uint32_t nvec = vec ? cnt >> 2 : 0u;
-    for (uint32_t v = threadIdx.x; v < nvec; v += NT) {
-        const uint32_t d = v * 4u, row = obs_row(d, magic);
-        uint32_t col = d - row * L, a = row * stride + col;
-        uint32_t w[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            w[i] = tile[a];
-            ++col; ++a;
-            if (col == L) { col = 0; a += stride - L; }
-        }
-        reinterpret_cast<uint4 *>(g)[v] = make_uint4(w[0], w[1], w[2], w[3]);
-    }
-    for (uint32_t d = nvec * 4u + threadIdx.x; d < cnt; d += NT) {
-        const uint32_t row = obs_row(d, magic);
-        g[d] = tile[row * stride + (d - row * L)];
-    }
-}
-
-// one value of this lane's row (the tiles hold dwords: a double sits at an odd dword offset in every other row)
-__device__ inline float obs_get(const uint32_t *p, float) { return __uint_as_float(p[0]); }
-__device__ inline double obs_get(const uint32_t *p, double) { return __hiloint2double((int)p[1], (int)p[0]); }
-__device__ inline void obs_put(uint32_t *p, float v) { p[0] = __float_as_uint(v); }
-__device__ inline void obs_put(uint32_t *p, double v) { p[0] = (uint32_t)__double2loint(v); p[1] = (uint32_t)__double2hiint(v); }
 // cos / sin of pi x, evaluated in half-turns (no product with a rounded pi)
 __device__ inline float obs_cospi(float x) { return cospif(x); }
 __device__ inline double obs_cospi(double x) { return cospi(x); }
@@ -105,8 +59,8 @@ __global__ __launch_bounds__(ObsTile<R>::rows) void obs_post_kernel(const R *__r
     const int64_t tile0 = (int64_t)blockIdx.x * T;  // (64-bit: rows * n_in may exceed 2^31)
     const uint32_t rows_t = (uint32_t)(rows - tile0 < (int64_t)T ? rows - tile0 : (int64_t)T);
 
-    obs_stage_in<T>(tin, SI, Li, P.magic_in, reinterpret_cast<const uint32_t *>(state + tile0 * P.n_in), rows_t * Li, vec_in);
-    if (Lr) obs_stage_in<T>(tout + (uint32_t)P.n_post * DW, SO, Lr, P.magic_ref, reinterpret_cast<const uint32_t *>(refs + tile0 * P.n_ref), rows_t * Lr, vec_ref);
+    tile_stage_in<T>(tin, SI, Li, P.magic_in, reinterpret_cast<const uint32_t *>(state + tile0 * P.n_in), rows_t * Li, vec_in);
+    if (Lr) tile_stage_in<T>(tout + (uint32_t)P.n_post * DW, SO, Lr, P.magic_ref, reinterpret_cast<const uint32_t *>(refs + tile0 * P.n_ref), rows_t * Lr, vec_ref);
     __syncthreads();
     if (threadIdx.x < rows_t) {
         const uint32_t *mine = tin + threadIdx.x * SI;
@@ -116,21 +70,19 @@ __global__ __launch_bounds__(ObsTile<R>::rows) void obs_post_kernel(const R *__r
             R v;
             if (op == GEMX_OBS_SUM) {
                 uint32_t m = P.mask[c];
-                v = obs_get(mine + (uint32_t)(__ffs(m) - 1) * DW, R(0));
-                for (m &= m - 1u; m; m &= m - 1u) v = v + obs_get(mine + (uint32_t)(__ffs(m) - 1) * DW, R(0));  // ascending j, plain adds
+                v = tile_get(mine + (uint32_t)(__ffs(m) - 1) * DW, R(0));
+                for (m &= m - 1u; m; m &= m - 1u) v = v + tile_get(mine + (uint32_t)(__ffs(m) - 1) * DW, R(0));  // ascending j, plain adds
             } else {
-                v = obs_get(mine + src * DW, R(0));
+                v = tile_get(mine + src * DW, R(0));
                 if (op == GEMX_OBS_COSPI) v = obs_cospi(v);
                 else if (op == GEMX_OBS_SINPI) v = obs_sinpi(v);
             }
-            obs_put(res + (uint32_t)c * DW, v);
+            tile_put(res + (uint32_t)c * DW, v);
         }
     }
     __syncthreads();
-    obs_stage_out<T>(tout, SO, Lo, P.magic_out, reinterpret_cast<uint32_t *>(out + tile0 * P.n_out), rows_t * Lo, vec_out);
+    tile_stage_out<T>(tout, SO, Lo, P.magic_out, reinterpret_cast<uint32_t *>(out + tile0 * P.n_out), rows_t * Lo, vec_out);
 }
-
-uint32_t obs_magic(uint32_t L) { return L <= 1u ? 0u : (uint32_t)((1ull << 32) / L) + 1u; }
 
 }  // namespace
 
@@ -175,10 +127,7 @@ int gemx_obsproc_create(const gemx_obsproc_config *cfg, int dtype, int device, g
             return gemx::fail(GEMX_ERR_ARG, "column %d: src %d outside [0, %d)", c, e.src, cfg->n_in);
         }
     }
-    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
-    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
+    if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     gemx_obsproc *p = new (std::nothrow) gemx_obsproc();
     if (!p) return gemx::fail(GEMX_ERR_ALLOC, "out of host memory");
     p->cfg = *cfg; p->device = device; p->f64 = dtype == GEMX_F64;
@@ -186,7 +135,7 @@ int gemx_obsproc_create(const gemx_obsproc_config *cfg, int dtype, int device, g
     memset(&P, 0, sizeof(P));
     const uint32_t dw = p->f64 ? 2u : 1u;
     P.n_in = cfg->n_in; P.n_post = cfg->n_post; P.n_ref = cfg->flat ? cfg->n_ref : 0; P.n_out = P.n_post + P.n_ref;
-    P.magic_in = obs_magic((uint32_t)P.n_in * dw); P.magic_ref = obs_magic((uint32_t)P.n_ref * dw); P.magic_out = obs_magic((uint32_t)P.n_out * dw);
+    P.magic_in = tile_magic((uint32_t)P.n_in * dw); P.magic_ref = tile_magic((uint32_t)P.n_ref * dw); P.magic_out = tile_magic((uint32_t)P.n_out * dw);
     for (int c = 0; c < cfg->n_post; ++c) {
         const gemx_obsproc_entry &e = cfg->entries[c];
         P.ent[c] = (uint32_t)e.op | (e.op == GEMX_OBS_SUM ? 0u : (uint32_t)e.src << 8);
@@ -200,9 +149,7 @@ int gemx_obsproc_apply(gemx_obsproc *p, const void *state_dev, const void *refs_
     if (!p || !state_dev || !out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
     if (p->prog.n_ref > 0 && !refs_dev) return gemx::fail(GEMX_ERR_ARG, "a flat observation with n_ref = %d needs refs_dev", p->prog.n_ref);
     if (rows < 0) return gemx::fail(GEMX_ERR_ARG, "rows must be >= 0");
-    const uintptr_t am = p->f64 ? 7u : 3u;
-    if (((uintptr_t)state_dev & am) || ((uintptr_t)out_dev & am) || (p->prog.n_ref > 0 && ((uintptr_t)refs_dev & am)))
-        return gemx::fail(GEMX_ERR_ARG, "tensors must be aligned to their element size");
+    if (!gemx::elem_aligned(p->f64, state_dev, out_dev, p->prog.n_ref > 0 ? refs_dev : nullptr)) return gemx::fail_unaligned();
     if (rows == 0) return GEMX_OK;
     gemx::DeviceGuard guard(p->device);
     hipStream_t st = (hipStream_t)stream;

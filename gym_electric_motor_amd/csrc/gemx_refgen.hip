@@ -26,9 +26,7 @@
 // SwitchedReferenceGenerator (gemx_refgen_create_switched; last part of the kernels): a column that runs one of several alternatives per
 // super-episode.  A kernel of its own (refgen_switched_kernel) beside the kinds kernel, on the same helpers; handles without such a column
 // launch what they launched before.
-#include "gemx_common.hpp"
-
-void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
+#include "gemx_support.hpp"
 
 struct gemx_refgen {
     gemx_refgen_config cfg;
@@ -240,15 +238,28 @@ template <class R> int step(gemx_refgen *r, void *out, const uint8_t *done, hipS
 enum { DRAW_SUB2 = 3 };
 enum { PAR_AMP = 0, PAR_FREQ = 1, PAR_OFF = 2, PAR_PHASE = 3, PAR_WIDTH = 4, PAR_ROLL = 5, N_PAR = 6 };
 
-struct RefgenKindsDev {
+// The description of a handle's columns, a kernel argument: S slots of one generator kind each.  A kinds handle has one slot per column
+// (RefgenKindsDev); a switched handle has GEMX_MAX_ALT per column, alternative a of column g at slot g * GEMX_MAX_ALT + a, and -- only
+// it -- the super-episodes' description (RefgenSwitchedDev, 2560 B).
+constexpr int ALT_SLOTS = GEMX_MAX_REF * GEMX_MAX_ALT;
+struct NoSuperDev {};
+struct SuperDev {
+    int32_t n_alt[GEMX_MAX_REF], sup_lo[GEMX_MAX_REF], sup_hi[GEMX_MAX_REF];  // n_alt = 0: a plain column
+    double cdf[ALT_SLOTS];                                                    // running sums of p
+};
+struct DescriptionHead {
     int32_t n_ref;
     uint64_t seed;
     int64_t env_base;
     double tau;
-    int32_t kind[GEMX_MAX_REF], len_lo[GEMX_MAX_REF], len_hi[GEMX_MAX_REF];
-    double log_sig_lo[GEMX_MAX_REF], log_sig_hi[GEMX_MAX_REF], m_lo[GEMX_MAX_REF], m_hi[GEMX_MAX_REF], i_lo[GEMX_MAX_REF], i_hi[GEMX_MAX_REF];
-    double a_lo[GEMX_MAX_REF], a_hi[GEMX_MAX_REF], f_lo[GEMX_MAX_REF], f_hi[GEMX_MAX_REF], o_lo[GEMX_MAX_REF], o_hi[GEMX_MAX_REF], c[GEMX_MAX_REF];
 };
+template <int S> struct RefgenDescription : DescriptionHead, std::conditional_t<S == ALT_SLOTS, SuperDev, NoSuperDev> {
+    int32_t kind[S], len_lo[S], len_hi[S];
+    double log_sig_lo[S], log_sig_hi[S], m_lo[S], m_hi[S], i_lo[S], i_hi[S];
+    double a_lo[S], a_hi[S], f_lo[S], f_hi[S], o_lo[S], o_hi[S], c[S];
+};
+using RefgenKindsDev = RefgenDescription<GEMX_MAX_REF>;
+using RefgenSwitchedDev = RefgenDescription<ALT_SLOTS>;
 
 struct KindLane {  // the state of one (column, env), in registers
     double v, sg, amp, freq, off, phase, width, roll;
@@ -297,7 +308,7 @@ template <class Dev> __device__ inline void kinds_new_subepisode(const Dev &G, i
 }
 
 // reset(): Wiener draws its initial value (wiener ... :43-49), every other sub-episoded kind restarts from 0 (subepisoded ... :80-86);
-// a new sub-episode starts with the next step.  (Constant columns never get here: refgen_kinds_kernel writes their value and returns.)
+// a new sub-episode starts with the next step.  (Constant columns never get here: the kernels write their value and return.)
 template <class Dev> __device__ inline void kinds_reset(const Dev &G, int64_t env, int g, int c, KindLane &s) {
     const int kind = G.kind[c];
     if (kind == GEMX_REF_WIENER) {
@@ -344,53 +355,6 @@ template <class R, class Dev> __device__ inline double kinds_advance(const Dev &
     return v;
 }
 
-// reset (K = 0: the envs of reset_mask, or all), rollout (K steps, reset AFTER step k where done_post[k][env]), step (K = 1, reset
-// BEFORE the step where done_pre[env]) and shell-order rollout (K steps, reset BEFORE step k where done_pre[k][env]): out[k][env][g],
-// adjacent lanes write adjacent columns.
-template <class R>
-__global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
-                                    int K, RefgenKindsDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
-                                    uint64_t *t, int32_t *len, double *par) {
-    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N * G.n_ref) return;
-    const int g = (int)(idx % G.n_ref);
-    const int64_t env = idx / G.n_ref;
-    const int64_t si = (int64_t)g * N + env, stride = (int64_t)G.n_ref * N;
-    const int kind = G.kind[g];
-    if (kind == GEMX_REF_CONST) {  // no state at all
-        for (int k = 0; k < K; ++k) out[((int64_t)k * N + env) * G.n_ref + g] = (R)G.c[g];
-        return;
-    }
-    // the waveform's parameters are read by the waveform kinds only, and -- like sigma and the length -- written back only by a lane that
-    // started a sub-episode in this launch (one launch in hundreds): a step moves ~50 B per lane instead of ~180
-    const bool wave = kind != GEMX_REF_WIENER && kind != GEMX_REF_LAPLACE;
-    KindLane s;
-    s.v = value[si]; s.sg = sigma[si]; s.lf = left[si]; s.ns = n_sub[si]; s.nr = n_reset[si]; s.t = t[si]; s.len = len[si];
-    s.amp = s.freq = s.off = s.phase = s.roll = 0.0; s.width = 1.0;
-    if (wave) {
-        s.amp = par[PAR_AMP * stride + si]; s.freq = par[PAR_FREQ * stride + si]; s.off = par[PAR_OFF * stride + si];
-        s.phase = par[PAR_PHASE * stride + si]; s.width = par[PAR_WIDTH * stride + si]; s.roll = par[PAR_ROLL * stride + si];
-    }
-    const uint32_t ns0 = s.ns, nr0 = s.nr;
-    if (K == 0) {
-        if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, g, s);
-    }
-    for (int k = 0; k < K; ++k) {
-        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
-        out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, g, s);
-        if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
-    }
-    value[si] = s.v; left[si] = s.lf; t[si] = s.t;
-    if (s.nr != nr0) n_reset[si] = s.nr;
-    if (s.ns != ns0) {
-        n_sub[si] = s.ns; sigma[si] = s.sg; len[si] = s.len;
-        if (wave) {
-            par[PAR_AMP * stride + si] = s.amp; par[PAR_FREQ * stride + si] = s.freq; par[PAR_OFF * stride + si] = s.off;
-            par[PAR_PHASE * stride + si] = s.phase; par[PAR_WIDTH * stride + si] = s.width; par[PAR_ROLL * stride + si] = s.roll;
-        }
-    }
-}
-
 // description slot `s` of G from column / alternative `j` of a config (gemx_refgen_kinds_config, gemx_refgen_switched_config: the same fields)
 template <class Dev, class Cfg> void set_description(Dev &G, int s, const Cfg &c, int j) {
     G.kind[s] = c.kind[j]; G.len_lo[s] = c.episode_len_lo[j]; G.len_hi[s] = c.episode_len_hi[j];
@@ -406,22 +370,16 @@ template <class Dev, class Cfg> void set_description(Dev &G, int s, const Cfg &c
     }
 }
 
-RefgenKindsDev make_kinds_dev(const gemx_refgen_kinds_config &c) {
-    RefgenKindsDev G;
+template <class Dev, class Cfg> Dev make_description(const Cfg &c) {  // (the slots: set_description, by the caller)
+    Dev G;
     memset(&G, 0, sizeof(G));
     G.n_ref = c.n_ref; G.seed = c.seed; G.env_base = c.env_base; G.tau = c.tau;
-    for (int g = 0; g < c.n_ref; ++g) set_description(G, g, c, g);
     return G;
 }
-
-template <class R>
-int kinds_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
-    const int64_t lanes = r->n * r->kcfg.n_ref;
-    gemx_cov_note(sizeof(R) == 4 ? "refgen_kinds_kernel<float>" : "refgen_kinds_kernel<double>");
-    hipLaunchKernelGGL(refgen_kinds_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
-                       make_kinds_dev(r->kcfg), r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par);
-    GEMX_HIP_TRY(hipGetLastError());
-    return GEMX_OK;
+RefgenKindsDev make_kinds_dev(const gemx_refgen_kinds_config &c) {
+    RefgenKindsDev G = make_description<RefgenKindsDev>(c);
+    for (int g = 0; g < c.n_ref; ++g) set_description(G, g, c, g);
+    return G;
 }
 
 // small kernel of gemx_refgen_get_params: kind / step index / length per (column, env)
@@ -440,20 +398,6 @@ __global__ void refgen_kinds_index_kernel(int32_t *out, int64_t N, int n_ref, in
 // slot column * GEMX_MAX_ALT with no super-episodes: the kinds kernel's draws and arithmetic.
 //   DRAW_SUPER index n_super  word 0: super-episode length, integers(lo, hi); word 1: the alternative, inverse distribution function of p
 enum { DRAW_SUPER = 4 };
-constexpr int ALT_SLOTS = GEMX_MAX_REF * GEMX_MAX_ALT;
-
-struct RefgenSwitchedDev {  // 2560 B, a kernel argument
-    int32_t n_ref;
-    uint64_t seed;
-    int64_t env_base;
-    double tau;
-    int32_t n_alt[GEMX_MAX_REF], sup_lo[GEMX_MAX_REF], sup_hi[GEMX_MAX_REF];  // n_alt = 0: a plain column
-    double cdf[ALT_SLOTS];                                                    // running sums of p
-    int32_t kind[ALT_SLOTS], len_lo[ALT_SLOTS], len_hi[ALT_SLOTS];
-    double log_sig_lo[ALT_SLOTS], log_sig_hi[ALT_SLOTS], m_lo[ALT_SLOTS], m_hi[ALT_SLOTS], i_lo[ALT_SLOTS], i_hi[ALT_SLOTS];
-    double a_lo[ALT_SLOTS], a_hi[ALT_SLOTS], f_lo[ALT_SLOTS], f_hi[ALT_SLOTS], o_lo[ALT_SLOTS], o_hi[ALT_SLOTS], c[ALT_SLOTS];
-};
-
 __device__ inline bool is_wave(int kind) { return kind >= GEMX_REF_SINUS && kind <= GEMX_REF_SAWTOOTH; }
 
 struct SuperLane {  // the super-episode state of one (column, env), in registers
@@ -493,8 +437,54 @@ template <class R> __device__ inline double switched_advance(const RefgenSwitche
     return kinds_advance<R>(G, env, g, c, s);
 }
 
-// the four uses of refgen_kinds_kernel (reset, rollout, step, shell-order rollout), same lane mapping: out[k][env][g].  Launched with
-// 256 threads, and told so: without the bound the compiler keeps to 128 VGPRs and spills
+// reset (K = 0: the envs of reset_mask, or all), rollout (K steps, reset AFTER step k where done_post[k][env]), step (K = 1, reset
+// BEFORE the step where done_pre[env]) and shell-order rollout (K steps, reset BEFORE step k where done_pre[k][env]): out[k][env][g],
+// adjacent lanes write adjacent columns.  (This kernel and refgen_switched_kernel share the description template and the kinds_*
+// helpers but not their skeleton: merged into one template, or over common load / write-back helpers, neither compiled to the
+// instructions it had, and the kinds kernel's launches measured over their allowance: profiles/support_units_refactor.md.)
+template <class R>
+__global__ void refgen_kinds_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
+                                    int K, RefgenKindsDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
+                                    uint64_t *t, int32_t *len, double *par) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= N * G.n_ref) return;
+    const int g = (int)(idx % G.n_ref);
+    const int64_t env = idx / G.n_ref;
+    const int64_t si = (int64_t)g * N + env, stride = (int64_t)G.n_ref * N;
+    const int kind = G.kind[g];
+    if (kind == GEMX_REF_CONST) {  // no state at all
+        for (int k = 0; k < K; ++k) out[((int64_t)k * N + env) * G.n_ref + g] = (R)G.c[g];
+        return;
+    }
+    const bool wave = kind != GEMX_REF_WIENER && kind != GEMX_REF_LAPLACE;
+    KindLane s;
+    s.v = value[si]; s.sg = sigma[si]; s.lf = left[si]; s.ns = n_sub[si]; s.nr = n_reset[si]; s.t = t[si]; s.len = len[si];
+    s.amp = s.freq = s.off = s.phase = s.roll = 0.0; s.width = 1.0;
+    if (wave) {
+        s.amp = par[PAR_AMP * stride + si]; s.freq = par[PAR_FREQ * stride + si]; s.off = par[PAR_OFF * stride + si];
+        s.phase = par[PAR_PHASE * stride + si]; s.width = par[PAR_WIDTH * stride + si]; s.roll = par[PAR_ROLL * stride + si];
+    }
+    const uint32_t ns0 = s.ns, nr0 = s.nr;
+    if (K == 0) {
+        if (reset_all || (reset_mask != nullptr && reset_mask[env])) kinds_reset(G, env, g, g, s);
+    }
+    for (int k = 0; k < K; ++k) {
+        if (done_pre != nullptr && done_pre[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
+        out[((int64_t)k * N + env) * G.n_ref + g] = (R)kinds_advance<R>(G, env, g, g, s);
+        if (done_post != nullptr && done_post[(int64_t)k * N + env]) kinds_reset(G, env, g, g, s);
+    }
+    value[si] = s.v; left[si] = s.lf; t[si] = s.t;
+    if (s.nr != nr0) n_reset[si] = s.nr;
+    if (s.ns != ns0) {
+        n_sub[si] = s.ns; sigma[si] = s.sg; len[si] = s.len;
+        if (wave) {
+            par[PAR_AMP * stride + si] = s.amp; par[PAR_FREQ * stride + si] = s.freq; par[PAR_OFF * stride + si] = s.off;
+            par[PAR_PHASE * stride + si] = s.phase; par[PAR_WIDTH * stride + si] = s.width; par[PAR_ROLL * stride + si] = s.roll;
+        }
+    }
+}
+
+// launched with 256 threads, and told so: without the bound the compiler keeps to 128 VGPRs and spills
 template <class R>
 __global__ void __launch_bounds__(256) refgen_switched_kernel(R *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *reset_mask, int reset_all, int64_t N,
                                        int K, RefgenSwitchedDev G, double *value, double *sigma, int32_t *left, uint32_t *n_sub, uint32_t *n_reset,
@@ -513,14 +503,14 @@ __global__ void __launch_bounds__(256) refgen_switched_kernel(R *out, const uint
     SuperLane u = {0, 0, 0, 0u};
     if (switched) { u.alt = alt[si]; u.sk = sk[si]; u.slen = slen[si]; u.nsup = n_super[si]; }
     const SuperLane u0 = u;
-    // the waveform's parameters: read where the lane's current kind is a waveform (a newly chosen alternative draws all of them before it
-    // reads any); written back -- like sigma and the length -- only by a lane that started a sub-episode in this launch: the parameters of
-    // its last one, zeros where that was a walk's, so that the stored state does not depend on how the steps were cut into launches
+    // `wave`: the kind of the last sub-episode started in this launch is a waveform's.  A newly chosen alternative draws all its parameters
+    // before it reads any; what is written back are the parameters of the LAST sub-episode, zeros where that was a walk's, so that the
+    // stored state does not depend on how the steps were cut into launches
     const int kind0 = G.kind[c0 + u.alt];
     KindLane s;
     s.v = value[si]; s.sg = sigma[si]; s.lf = left[si]; s.ns = n_sub[si]; s.nr = n_reset[si]; s.t = t[si]; s.len = len[si];
     s.amp = s.freq = s.off = s.phase = s.roll = 0.0; s.width = 1.0;
-    bool wave = is_wave(kind0);  // (from here on: the kind of the last sub-episode started in this launch)
+    bool wave = is_wave(kind0);
     if (wave) {
         s.amp = par[PAR_AMP * stride + si]; s.freq = par[PAR_FREQ * stride + si]; s.off = par[PAR_OFF * stride + si];
         s.phase = par[PAR_PHASE * stride + si]; s.width = par[PAR_WIDTH * stride + si]; s.roll = par[PAR_ROLL * stride + si];
@@ -557,9 +547,7 @@ __global__ void __launch_bounds__(256) refgen_switched_kernel(R *out, const uint
 }
 
 RefgenSwitchedDev make_switched_dev(const gemx_refgen_switched_config &c) {
-    RefgenSwitchedDev G;
-    memset(&G, 0, sizeof(G));
-    G.n_ref = c.n_ref; G.seed = c.seed; G.env_base = c.env_base; G.tau = c.tau;
+    RefgenSwitchedDev G = make_description<RefgenSwitchedDev>(c);
     for (int g = 0; g < c.n_ref; ++g) {
         G.n_alt[g] = c.n_alt[g]; G.sup_lo[g] = c.super_len_lo[g]; G.sup_hi[g] = c.super_len_hi[g];
         double sum = 0.0;
@@ -572,21 +560,24 @@ RefgenSwitchedDev make_switched_dev(const gemx_refgen_switched_config &c) {
     return G;
 }
 
+// every entry point's dispatch for the handles that run one kernel for all four uses: the switched kernel, else the kinds kernel
 template <class R>
-int switched_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
-    const int64_t lanes = r->n * r->cfg.n_ref;
-    gemx_cov_note(sizeof(R) == 4 ? "refgen_switched_kernel<float>" : "refgen_switched_kernel<double>");
-    hipLaunchKernelGGL(refgen_switched_kernel<R>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
-                       *(const RefgenSwitchedDev *)r->sdev, r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par, r->alt, r->sk, r->slen,
-                       r->n_super);
+int kinds_launch(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
+    const dim3 grid((unsigned)((r->n * r->cfg.n_ref + 255) / 256)), block(256);
+    if (r->switched) {
+        gemx_cov_note(sizeof(R) == 4 ? "refgen_switched_kernel<float>" : "refgen_switched_kernel<double>");
+        hipLaunchKernelGGL(refgen_switched_kernel<R>, grid, block, 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
+                           *(const RefgenSwitchedDev *)r->sdev, r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par, r->alt, r->sk,
+                           r->slen, r->n_super);
+    } else {
+        gemx_cov_note(sizeof(R) == 4 ? "refgen_kinds_kernel<float>" : "refgen_kinds_kernel<double>");
+        hipLaunchKernelGGL(refgen_kinds_kernel<R>, grid, block, 0, st, (R *)out, done_pre, done_post, mask, reset_all, r->n, K,
+                           make_kinds_dev(r->kcfg), r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t, r->len, r->par);
+    }
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
 }
-// every entry point's dispatch for the handles that run one kernel for all four uses: the switched kernel, else the kinds kernel
 int kinds(gemx_refgen *r, void *out, const uint8_t *done_pre, const uint8_t *done_post, const uint8_t *mask, int reset_all, int K, hipStream_t st) {
-    if (r->switched)
-        return r->f64 ? switched_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
-                      : switched_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
     return r->f64 ? kinds_launch<double>(r, out, done_pre, done_post, mask, reset_all, K, st)
                   : kinds_launch<float>(r, out, done_pre, done_post, mask, reset_all, K, st);
 }
@@ -607,6 +598,30 @@ __global__ void refgen_switched_index_kernel(int32_t *out, int64_t N, int n_ref,
 
 }  // namespace
 
+// THE table of a handle's per-(column, env) arrays: pointer member, bytes per lane, which handles own it.  It drives allocation,
+// zeroing and gemx_refgen_destroy.
+enum { OWN_ALL = 1, OWN_KINDS = 2, OWN_SWITCHED = 4 };
+struct LaneArrayRow { void **p; size_t bytes; int owner; };
+template <class F> static void refgen_lane_arrays(gemx_refgen *r, F f) {
+    const LaneArrayRow rows[] = {{(void **)&r->value, 8, OWN_ALL},      {(void **)&r->sigma, 8, OWN_ALL},    {(void **)&r->left, 4, OWN_ALL},
+                                 {(void **)&r->n_sub, 4, OWN_ALL},      {(void **)&r->n_reset, 4, OWN_ALL},  {(void **)&r->t, 8, OWN_ALL},
+                                 {(void **)&r->len, 4, OWN_KINDS},      {(void **)&r->par, 8 * N_PAR, OWN_KINDS},
+                                 {(void **)&r->alt, 4, OWN_SWITCHED},   {(void **)&r->sk, 4, OWN_SWITCHED},  {(void **)&r->slen, 4, OWN_SWITCHED},
+                                 {(void **)&r->n_super, 4, OWN_SWITCHED}};
+    for (const LaneArrayRow &row : rows) f(row);
+}
+// allocate and zero the arrays of `owners`; false: a hipMalloc failed (the caller destroys the handle)
+static bool refgen_alloc_arrays(gemx_refgen *r, int owners) {
+    const size_t m = (size_t)r->n * r->cfg.n_ref;
+    bool ok = true;
+    refgen_lane_arrays(r, [&](const LaneArrayRow &a) {
+        if (!ok || !(a.owner & owners)) return;
+        ok = hipMalloc(a.p, m * a.bytes) == hipSuccess;
+        if (ok) (void)hipMemset(*a.p, 0, m * a.bytes);
+    });
+    return ok;
+}
+
 // the handle and its zeroed per-(column, env) arrays; kcfg != NULL: a gemx_refgen_create_kinds handle (cfg: the Wiener view of its columns)
 static int gemx_refgen_alloc(const gemx_refgen_config &cfg, const gemx_refgen_kinds_config *kcfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
     gemx::DeviceGuard guard(device);
@@ -615,18 +630,22 @@ static int gemx_refgen_alloc(const gemx_refgen_config &cfg, const gemx_refgen_ki
     r->cfg = cfg; r->n = n_envs; r->device = device; r->f64 = dtype == GEMX_F64;
     memset(&r->kcfg, 0, sizeof(r->kcfg));
     if (kcfg) { r->kcfg = *kcfg; r->has_kinds = 1; }
-    const size_t m = (size_t)n_envs * cfg.n_ref;
-    if (hipMalloc((void **)&r->value, m * 8) != hipSuccess || hipMalloc((void **)&r->sigma, m * 8) != hipSuccess ||
-        hipMalloc((void **)&r->left, m * 4) != hipSuccess || hipMalloc((void **)&r->n_sub, m * 4) != hipSuccess ||
-        hipMalloc((void **)&r->n_reset, m * 4) != hipSuccess || hipMalloc((void **)&r->t, m * 8) != hipSuccess ||
-        (kcfg && (hipMalloc((void **)&r->len, m * 4) != hipSuccess || hipMalloc((void **)&r->par, m * 8 * N_PAR) != hipSuccess))) {
+    if (!refgen_alloc_arrays(r, OWN_ALL | (kcfg ? OWN_KINDS : 0))) {
         gemx_refgen_destroy(r);
         return gemx::fail(GEMX_ERR_ALLOC, "hipMalloc(refgen) failed");
     }
-    (void)hipMemset(r->value, 0, m * 8); (void)hipMemset(r->sigma, 0, m * 8); (void)hipMemset(r->left, 0, m * 4);
-    (void)hipMemset(r->n_sub, 0, m * 4); (void)hipMemset(r->n_reset, 0, m * 4); (void)hipMemset(r->t, 0, m * 8);
-    if (kcfg) { (void)hipMemset(r->len, 0, m * 4); (void)hipMemset(r->par, 0, m * 8 * N_PAR); }
     *out = r;
+    return GEMX_OK;
+}
+
+// what every create function checks first; `name`: of its config struct, for the size message
+template <class Cfg> static int refgen_check_create(const Cfg *cfg, const char *name, int64_t n_envs, gemx_refgen **out) {
+    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(Cfg)) return gemx::fail(GEMX_ERR_ARG, "%s size mismatch", name);
+    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
+    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
+    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
     return GEMX_OK;
 }
 
@@ -660,47 +679,26 @@ static int refgen_check_columns(const gemx_refgen_kinds_config &c, gemx_refgen_c
     }
     return GEMX_OK;
 }
-static int refgen_check_device(int device, int dtype) {
-    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
-    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
-    return GEMX_OK;
-}
-
 extern "C" {
 
 int gemx_refgen_create(const gemx_refgen_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
-    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(gemx_refgen_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_config size mismatch");
-    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
-    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
-    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
+    if (int rc = refgen_check_create(cfg, "gemx_refgen_config", n_envs, out)) return rc;
     if (cfg->episode_len_lo < 1 || cfg->episode_len_hi < cfg->episode_len_lo) return gemx::fail(GEMX_ERR_ARG, "episode lengths must satisfy 1 <= lo <= hi");
     for (int g = 0; g < cfg->n_ref; ++g) {
         if (!(cfg->sigma_lo[g] > 0) || cfg->sigma_hi[g] < cfg->sigma_lo[g]) return gemx::fail(GEMX_ERR_ARG, "sigma range %d must satisfy 0 < lo <= hi", g);
         if (cfg->margin_hi[g] < cfg->margin_lo[g] || cfg->initial_hi[g] < cfg->initial_lo[g]) return gemx::fail(GEMX_ERR_ARG, "empty margin / initial range %d", g);
     }
-    if (dtype != GEMX_F32 && dtype != GEMX_F64) return gemx::fail(GEMX_ERR_ARG, "unknown dtype");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return gemx::fail(GEMX_ERR_DEVICE, "no HIP device visible: there is no CPU fallback");
-    if (device < 0 || device >= ndev) return gemx::fail(GEMX_ERR_ARG, "device %d out of range", device);
+    if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     return gemx_refgen_alloc(*cfg, nullptr, n_envs, device, dtype, out);
 }
 
 int gemx_refgen_create_kinds(const gemx_refgen_kinds_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
-    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(gemx_refgen_kinds_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_kinds_config size mismatch");
-    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
-    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
-    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
+    if (int rc = refgen_check_create(cfg, "gemx_refgen_kinds_config", n_envs, out)) return rc;
     if (!(cfg->tau > 0)) return gemx::fail(GEMX_ERR_ARG, "tau must be positive");
     gemx_refgen_config w;
     int all_wiener = 1;
     if (int rc = refgen_check_columns(*cfg, w, all_wiener)) return rc;
-    if (int rc = refgen_check_device(device, dtype)) return rc;
+    if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     const int rc = gemx_refgen_alloc(w, cfg, n_envs, device, dtype, out);
     if (rc == GEMX_OK) (*out)->mixed = !all_wiener;  // all Wiener, one length range: the kernels (and bits) of a gemx_refgen_create handle
     return rc;
@@ -717,12 +715,7 @@ static void refgen_alternative(const gemx_refgen_switched_config &c, int g, int 
 }
 
 int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t n_envs, int device, int dtype, gemx_refgen **out) {
-    if (!cfg || !out) return gemx::fail(GEMX_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (cfg->struct_size != (int32_t)sizeof(gemx_refgen_switched_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_refgen_switched_config size mismatch");
-    if (cfg->env_base < 0) return gemx::fail(GEMX_ERR_ARG, "env_base must be >= 0");
-    if (cfg->n_ref < 1 || cfg->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [1, %d]", GEMX_MAX_REF);
-    if (n_envs <= 0) return gemx::fail(GEMX_ERR_ARG, "n_envs must be positive");
+    if (int rc = refgen_check_create(cfg, "gemx_refgen_switched_config", n_envs, out)) return rc;
     if (!(cfg->tau > 0)) return gemx::fail(GEMX_ERR_ARG, "tau must be positive");
     int any = 0, most = 1;
     for (int g = 0; g < cfg->n_ref; ++g) {
@@ -756,21 +749,18 @@ int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t 
         if (a == 0) { k0 = k; w0 = w; }
     }
     if (!any) return gemx_refgen_create_kinds(&k0, n_envs, device, dtype, out);  // no switched column: that handle, and its kernels
-    if (int rc = refgen_check_device(device, dtype)) return rc;
+    if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     const int rc = gemx_refgen_alloc(w0, &k0, n_envs, device, dtype, out);
     if (rc != GEMX_OK) return rc;
     gemx_refgen *r = *out;
     gemx::DeviceGuard guard(device);
-    const size_t m = (size_t)n_envs * cfg->n_ref;
     RefgenSwitchedDev *G = new (std::nothrow) RefgenSwitchedDev(make_switched_dev(*cfg));
     r->sdev = G;
-    if (!G || hipMalloc((void **)&r->alt, m * 4) != hipSuccess || hipMalloc((void **)&r->sk, m * 4) != hipSuccess ||
-        hipMalloc((void **)&r->slen, m * 4) != hipSuccess || hipMalloc((void **)&r->n_super, m * 4) != hipSuccess) {
+    if (!G || !refgen_alloc_arrays(r, OWN_SWITCHED)) {
         gemx_refgen_destroy(r);
         *out = nullptr;
         return gemx::fail(GEMX_ERR_ALLOC, "allocation (switched refgen) failed");
     }
-    (void)hipMemset(r->alt, 0, m * 4); (void)hipMemset(r->sk, 0, m * 4); (void)hipMemset(r->slen, 0, m * 4); (void)hipMemset(r->n_super, 0, m * 4);
     r->mixed = 1;
     r->switched = 1;
     return GEMX_OK;
@@ -779,18 +769,9 @@ int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t 
 int gemx_refgen_destroy(gemx_refgen *r) {
     if (!r) return GEMX_OK;
     gemx::DeviceGuard guard(r->device);
-    if (r->value) (void)hipFree(r->value);
-    if (r->sigma) (void)hipFree(r->sigma);
-    if (r->left) (void)hipFree(r->left);
-    if (r->n_sub) (void)hipFree(r->n_sub);
-    if (r->n_reset) (void)hipFree(r->n_reset);
-    if (r->t) (void)hipFree(r->t);
-    if (r->len) (void)hipFree(r->len);
-    if (r->par) (void)hipFree(r->par);
-    if (r->alt) (void)hipFree(r->alt);
-    if (r->sk) (void)hipFree(r->sk);
-    if (r->slen) (void)hipFree(r->slen);
-    if (r->n_super) (void)hipFree(r->n_super);
+    refgen_lane_arrays(r, [](const LaneArrayRow &a) {
+        if (*a.p) (void)hipFree(*a.p);
+    });
     delete (RefgenSwitchedDev *)r->sdev;
     delete r;
     return GEMX_OK;

@@ -20,46 +20,17 @@
 // loop; the last, partial tile moves its whole 16-byte units and then single dwords: nothing beyond K * N rows is read or written.
 // The whole reward description (all GEMX_MAX_OUT terms) is a kernel argument BY VALUE: kernel arguments are read with scalar loads, so
 // no uniform-address vector load of the description waits behind the stores (gemx_common.hpp, RewardHot, has the measurement).
-#include "gemx_common.hpp"
+#include "gemx_support.hpp"
 
 #include <mutex>
 #include <unordered_map>
 
-void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
-
 namespace {
 
-using gemx::RewardDev;
+using namespace gemx;  // RewardDev; the row tile: gemx_support.hpp
 
 template <class R> struct RewTile { static constexpr int rows = 1024 / (int)sizeof(R); };  // 256 fp32 rows | 128 fp64 rows: 1 KiB per column
-
-// tile-local dword index d < 2^14 of a row-major [rows][L] tile -> row (exact: d * (magic * L - 2^32) < 2^32 for L <= 72)
-__device__ inline uint32_t rew_row(uint32_t d, uint32_t magic) { return magic ? __umulhi(d, magic) : d; }
-
-// global (contiguous, `cnt` dwords) -> LDS tile with rows of L dwords at `stride`
-template <int NT> __device__ inline void rew_stage_in(uint32_t *tile, uint32_t stride, uint32_t L, uint32_t magic, const uint32_t *g, uint32_t cnt, int vec) {
-    const uint32_t nvec = vec ? cnt >> 2 : 0u;
-    for (uint32_t v = threadIdx.x; v < nvec; v += NT) {
-        const uint4 q = reinterpret_cast<const uint4 *>(g)[v];
-        const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-        const uint32_t d = v * 4u, row = rew_row(d, magic);
-        uint32_t col = d - row * L, a = row * stride + col;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            tile[a] = w[i];
-            ++col; ++a;
-            if (col == L) { col = 0; a += stride - L; }
-        }
-    }
-    for (uint32_t d = nvec * 4u + threadIdx.x; d < cnt; d += NT) {
-        const uint32_t row = rew_row(d, magic);
-        tile[row * stride + (d - row * L)] = g[d];
-    }
-}
-
-// one value of this lane's row (the tile holds dwords: a double sits at an odd dword offset in every other row)
-__device__ inline float rew_get(const uint32_t *p, float) { return __uint_as_float(p[0]); }
-__device__ inline double rew_get(const uint32_t *p, double) { return __hiloint2double((int)p[1], (int)p[0]); }
+static_assert(tile_fits(RewTile<double>::rows, 2 * GEMX_MAX_OUT) && tile_fits(RewTile<float>::rows, GEMX_MAX_OUT), "the longest row is within tile_row's exactness bound");
 
 // reward_term of gemx_kernels.hpp, restated.  GENERAL: reward_power other than 1 or 2 allowed (pow())
 template <bool GENERAL, class R> __device__ __forceinline__ R rew_term(R o, R ref, R inv_len, int kind, R power, R coef) {
@@ -82,7 +53,7 @@ __global__ __launch_bounds__(RewTile<R>::rows) void reward_rows_kernel(const R *
     const int64_t tile0 = (int64_t)blockIdx.x * T;        // (64-bit: rows * n_out may exceed 2^31)
     const uint32_t rows_t = (uint32_t)(rows - tile0 < (int64_t)T ? rows - tile0 : (int64_t)T);
 
-    rew_stage_in<T>(rew_smem, S, L, magic, reinterpret_cast<const uint32_t *>(obs + tile0 * n_out), rows_t * L, vec);
+    tile_stage_in<T>(rew_smem, S, L, magic, reinterpret_cast<const uint32_t *>(obs + tile0 * n_out), rows_t * L, vec);
     // this lane's references and done byte, in flight across the barrier
     const bool valid = threadIdx.x < rows_t;
     const int64_t g = tile0 + threadIdx.x;
@@ -107,7 +78,7 @@ __global__ __launch_bounds__(RewTile<R>::rows) void reward_rows_kernel(const R *
             const bool used = t < W.n_term;  // unused hot terms: column 0, kind 1, weight 0 (reward_hot_from)
             const int col = used ? W.col[t] : 0, kind = used ? W.kind[t] : 1;
             const R coef = used ? W.coef[t] : R(0), inv_len = used ? W.inv_len[t] : R(0), power = used ? W.power[t] : R(1);
-            acc += rew_term<false, R>(rew_get(mine + (uint32_t)col * DW, R(0)), rv[t], inv_len, kind, power, coef);
+            acc += rew_term<false, R>(tile_get(mine + (uint32_t)col * DW, R(0)), rv[t], inv_len, kind, power, coef);
         }
     }
     // terms beyond the hot ones, and EVERY term when some reward_power is not 1 or 2 (one pow() site)
@@ -116,13 +87,11 @@ __global__ __launch_bounds__(RewTile<R>::rows) void reward_rows_kernel(const R *
         R ref = R(0);
 #pragma unroll
         for (int j = 0; j < GEMX_MAX_REF; ++j) ref = (t == j) ? rv[j] : ref;
-        acc += rew_term<true, R>(rew_get(mine + (uint32_t)W.col[t] * DW, R(0)), ref, W.inv_len[t], W.kind[t], W.power[t], W.coef[t]);
+        acc += rew_term<true, R>(tile_get(mine + (uint32_t)W.col[t] * DW, R(0)), ref, W.inv_len[t], W.kind[t], W.power[t], W.coef[t]);
     }
     const R wse = W.bias - acc;
     reward[g] = dn ? W.violation_reward : wse;  // (1 - v) * wse + v * violation_reward, v in {0, 1}
 }
-
-uint32_t rew_magic(uint32_t L) { return L <= 1u ? 0u : (uint32_t)((1ull << 32) / L) + 1u; }
 
 // The reward descriptions as gemx_set_reward built them, by handle, on the HOST: the handle itself keeps the full description in device
 // memory only (the fused reward reads it there), and a kernel argument has to come from the host without a copy back per call.
@@ -148,7 +117,7 @@ int rew_launch(const gemx_handle *h, const RewardDev<R> &W, const void *obs, con
     for (int t = 0; t < W.n_term; ++t) general |= W.kind[t] == 3;
     gemx_cov_note(sizeof(R) == 4 ? "reward_rows_kernel<float>" : "reward_rows_kernel<double>");
     hipLaunchKernelGGL(reward_rows_kernel<R>, dim3((unsigned)tiles), dim3(T), lds, st, (const R *)obs, (const R *)refs_first, (const R *)refs_rows, done, (R *)reward,
-                       rows, h->n, h->nout, rew_magic(L), (int)(((uintptr_t)obs & 15u) == 0), general, W);
+                       rows, h->n, h->nout, tile_magic(L), (int)(((uintptr_t)obs & 15u) == 0), general, W);
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
 }
@@ -178,9 +147,8 @@ extern "C" int gemx_reward_rows(gemx_handle *h, const void *obs_dev, const void 
     if (h->rw_n_ref > 0 && (!refs_first_dev || (K > 1 && !refs_rows_dev)))
         return gemx::fail(GEMX_ERR_ARG, "a reward with n_ref = %d needs refs_first_dev (and refs_rows_dev when K > 1)", h->rw_n_ref);
     const bool f64 = h->cfg.dtype == GEMX_F64;
-    const uintptr_t am = f64 ? 7u : 3u;
-    if (((uintptr_t)obs_dev & am) || ((uintptr_t)reward_out_dev & am) || (h->rw_n_ref > 0 && (((uintptr_t)refs_first_dev & am) || ((uintptr_t)refs_rows_dev & am))))
-        return gemx::fail(GEMX_ERR_ARG, "tensors must be aligned to their element size");
+    const bool refs = h->rw_n_ref > 0;
+    if (!gemx::elem_aligned(f64, obs_dev, reward_out_dev, refs ? refs_first_dev : nullptr, refs ? refs_rows_dev : nullptr)) return gemx::fail_unaligned();
     RewDesc desc;
     {
         std::lock_guard<std::mutex> lock(g_rew_mutex);

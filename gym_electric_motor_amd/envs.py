@@ -499,18 +499,13 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         order on the done mask; the reward of row k against the references shown before step k; the pipeline's launches over the stored
         rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
         rollouts continue from it)."""
-        import ctypes as C
-
         torch = bps._torch()
         ps, gen = self.physical_system, self.reference_generator
         if eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
             generators = lambda: gen.rollout_shell(K, done_out, out=refs_out)  # noqa: E731
         else:
             generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
-        n_ref = int(self.reward_config.n_ref)
-        args = (C.c_void_p(raw.data_ptr()), C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(refs_out.data_ptr()) if n_ref else None,
-                C.c_void_p(done_out.data_ptr()), K, C.c_void_p(reward_out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        reward = bps._lib.bound_call(ps._L.gemx_reward_rows, ps, args, (raw, refs_out, done_out, reward_out, stream))
+        reward = self.bind_reward_rows(raw, refs_out, done_out, reward_out, stream=stream)
         shown, last = self._refs, refs_out[K - 1]
 
         def show(_current=torch.cuda.current_stream, _on=torch.cuda.stream):
@@ -521,6 +516,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                     shown.copy_(last)
 
         return generators, reward, self.pipeline.bind_after_rollout(raw, done_out, refs_out, state_out, stream), show
+
+    def bind_reward_rows(self, rows, refs_rows, done, reward_out, stream=None):
+        """-> zero-argument launch() of the reward pass (`gemx_reward_rows`) on fixed tensors: the base system's rows [K, N, S] of a
+        physics rollout, rewarded against the references shown now (row 0) and refs_rows [K, N, n_ref] (row k + 1 against refs_rows[k]),
+        with done [K, N] -> reward_out [K, N].  The tensors are the caller's to get right: contiguous, of the env's dtype, on its device."""
+        import ctypes as C
+
+        ps = self.physical_system
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        n_ref = int(self.reward_config.n_ref)
+        args = (C.c_void_p(rows.data_ptr()), C.c_void_p(self._refs.data_ptr()) if n_ref else None, C.c_void_p(refs_rows.data_ptr()) if n_ref else None,
+                C.c_void_p(done.data_ptr()), int(rows.shape[0]), C.c_void_p(reward_out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        return bps._lib.bound_call(ps._L.gemx_reward_rows, ps, args, (rows, refs_rows, done, reward_out, stream))
 
     def _rollout_complete(self, K, physics, outs):
         """The eager entry points: allocate what was not given, run `physics(raw, done_out)` and then the tail, once."""
