@@ -36,7 +36,9 @@ from .reference_generators import (  # noqa: F401
     SinusoidalReferenceGenerator, StepReferenceGenerator, SwitchedReferenceGenerator, TriangularReferenceGenerator, WienerProcessReferenceGenerator,
 )
 from .physical_system_wrappers import CosSinProcessor, CurrentSumProcessor, DeadTimeProcessor, DqToAbcActionProcessor, FluxObserver, FluxOrientedDqToAbcActionProcessor  # noqa: F401
+from .physical_system_wrappers import StateNoiseProcessor  # noqa: F401
 from .flux_observer import FluxObserverStage  # noqa: F401
+from .state_noise import StateNoiseStage  # noqa: F401
 from .observation import ObservationStage  # noqa: F401
 from .physical_systems import (  # noqa: F401
     BatchedDcMotorSystem,

@@ -154,6 +154,20 @@ class GemxFluxobsConfig(C.Structure):
     ]
 
 
+NOISE_NORMAL, NOISE_UNIFORM, NOISE_LAPLACE = range(3)  # GEMX_NOISE_*
+
+
+class GemxNoiseConfig(C.Structure):
+    """Mirror of `gemx_noise_config` (include/gemx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_in", C.c_int32), ("n_noisy", C.c_int32), ("has_reward", C.c_int32),
+        ("index", C.c_int32 * MAX_OUT), ("dist", C.c_int32 * MAX_OUT), ("param0", C.c_double * MAX_OUT), ("param1", C.c_double * MAX_OUT),
+        ("seed", C.c_uint64), ("env_base", C.c_int64), ("limit_mask", C.c_uint32), ("squared_mask", C.c_uint32),
+        ("reward", GemxRewardConfig),
+    ]
+
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
@@ -165,6 +179,7 @@ EXPORTS = (
     "gemx_refgen_create_switched", "gemx_refgen_get_switch_state",
     "gemx_fluxobs_create", "gemx_fluxobs_destroy", "gemx_fluxobs_reset", "gemx_fluxobs_step", "gemx_fluxobs_rows", "gemx_fluxobs_actions",
     "gemx_fluxobs_get_state", "gemx_fluxobs_set_state",
+    "gemx_noise_create", "gemx_noise_destroy", "gemx_noise_step", "gemx_noise_draws", "gemx_noise_get_position", "gemx_noise_set_position",
 )
 
 
@@ -233,6 +248,12 @@ def load():
     L.gemx_fluxobs_actions.argtypes = [vp, vp, vp, vp]
     L.gemx_fluxobs_get_state.argtypes = [vp, vp, vp]
     L.gemx_fluxobs_set_state.argtypes = [vp, vp, vp]
+    L.gemx_noise_create.argtypes = [C.POINTER(GemxNoiseConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_noise_destroy.argtypes = [vp]
+    L.gemx_noise_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.gemx_noise_draws.argtypes = [vp, C.c_uint64, i32, vp, vp]
+    L.gemx_noise_get_position.argtypes = [vp, C.POINTER(C.c_uint64), vp]
+    L.gemx_noise_set_position.argtypes = [vp, C.c_uint64, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

@@ -53,8 +53,18 @@ env classes: `ObservationPipeline.bind_after_step` / `bind_after_rollout` (obser
     state, _ = env.reset()                              # [N, 14 + 2]
     state, _, terminated, _, _ = env.step(dq_actions)   # dq_actions [N, 2]
 
-Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the noisy state, which
-the fused kernels cannot reproduce in a post-pass), reward weights or constraints on appended columns (`i_sum`,
+Measurement noise (state_noise.py, csrc/gemx_statenoise.hip): `ga.StateNoiseProcessor(states, random_dist, random_kwargs)` -- 'normal',
+'uniform' or 'laplace' -- listed before every observation-side processor.  The reference checks the constraints and computes the reward
+on the NOISY state, so the physics then runs without constraints, auto-reset and fused reward and a step is: the masked reset of the envs
+the last noisy row terminated, the physics, ONE launch that adds the noise and decides `terminated` and the reward on the noisy row, then
+the generators and the other stages as above -- two launches more than without the wrapper (one with `auto_reset=False`).  `terminated`,
+`reward` and the returned state are the noisy ones; `reset()` noises the reset state too.  The fused K-step rollouts raise: a K-step
+launch cannot restart an env on a done mask it has not seen.
+
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator="default",
+                  physical_system_wrappers=(ga.StateNoiseProcessor(["i_sd", "i_sq"], "normal", dict(scale=0.01)),))
+
+Outside the accelerated path: reward weights or constraints on appended columns (`i_sum`,
 `cos(...)`, `psi_abs`, `psi_angle`) and visualisation; an instance of the reference's own `SwitchedReferenceGenerator` is refused (pass the holder of that
 name).  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
 `physical_system=` to the reference's own `ElectricMotorEnvironment`.
@@ -239,8 +249,10 @@ def default_ode_solver(env_id, tau=None, load=None):
 class BatchedElectricMotorEnv:
     """Vector-env style shell around a batched physical system (physics + done mask only)."""
 
-    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None):
+    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None, state_noise=None, _reward_config=None):
         """flux_action: None | 'SCIM' | 'DFIM' -- the flux-oriented dq action processor (needs a FluxObserver in the observation chain).
+        state_noise: None | the StateNoiseProcessor's spec with the constraint masks and the auto-reset asked for (`make` builds it; the
+        system itself then has no constraints and no auto-reset): `terminated` and the returned state are the noisy ones.
         observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
         `step()` and `rollout()` then return the PROCESSED state, `state_space` / `state_names` describe it; `physical_system` stays raw.
         Everything behind the physics is the `pipeline` (observation.py: ObservationPipeline)."""
@@ -248,17 +260,22 @@ class BatchedElectricMotorEnv:
 
         self.physical_system = physical_system
         self.n_envs = physical_system.n_envs
-        pipe = self.pipeline = ObservationPipeline(physical_system, observation, _n_ref, flux_action, _defer_create)
+        pipe = self.pipeline = ObservationPipeline(physical_system, observation, _n_ref, flux_action, _defer_create, noise=state_noise,
+                                                   reward_config=_reward_config)
         self.observation_stage, self.flux, self.flux_action, self._flux_only = pipe.stage, pipe.flux, pipe.flux_action, pipe.flux_only
+        self.state_noise = pipe.noise
         self.action_space = pipe.action_space
         self.state_space = physical_system.state_space if pipe.stage is None else pipe.stage.observation_space
         self.state_names = list(physical_system.state_names if pipe.stage is None else pipe.stage.observation_names)
 
     def get_checkpoint(self):
-        """`physical_system.get_checkpoint()`, plus the flux observer's per-env state (`flux_observer`: float64 [4, N]) when the env has one."""
+        """`physical_system.get_checkpoint()`, plus the flux observer's per-env state (`flux_observer`: float64 [4, N]) when the env has one,
+        plus, with a StateNoiseProcessor, `state_noise`: the stream position and the done mask whose envs restart in front of the next step."""
         ck = self.physical_system.get_checkpoint()
         if self.flux is not None:
             ck["flux_observer"] = self.flux.get_state()
+        if self.state_noise is not None:
+            ck["state_noise"] = dict(position=self.state_noise.get_position(), done=self.physical_system._done.clone())
         return ck
 
     def set_checkpoint(self, ckpt):
@@ -266,6 +283,9 @@ class BatchedElectricMotorEnv:
         self.physical_system.set_checkpoint(ckpt)
         if self.flux is not None:
             self.flux.set_state(ckpt["flux_observer"])
+        if self.state_noise is not None:
+            self.state_noise.set_position(ckpt["state_noise"]["position"])
+            self.physical_system._done.copy_(ckpt["state_noise"]["done"])
 
     @property
     def unwrapped(self):
@@ -278,7 +298,7 @@ class BatchedElectricMotorEnv:
 
     def _shown(self, raw):
         """What the env hands out for the system's `raw` state (n_envs == 1 with numpy in / out keeps numpy)."""
-        if self.observation_stage is None:
+        if self.observation_stage is None and self.state_noise is None:
             return raw
         out = self.pipeline.state
         return out.reshape(-1).double().cpu().numpy() if isinstance(raw, np.ndarray) else out
@@ -295,9 +315,13 @@ class BatchedElectricMotorEnv:
         n_envs > 1) an env that terminated restarts from the reset state on its next step; the state it shows
         right after that restart is `physical_system.reset_observation`."""
         ps, pipe = self.physical_system, self.pipeline
+        if self.state_noise is not None and references is not None:
+            raise NotImplementedError("step(actions, references=...) with a StateNoiseProcessor: the reward is computed on the noisy state by the complete "
+                                      "env (make(..., reward_function=...)), not by the physics launch")
         if self.flux_action:  # launch 1 of 4: the dq actions rotated into the frame the last observation left
             pipe.bind_actions(pipe.dq_to_device(actions))()
             actions = pipe.abc
+        pipe.before_step()  # (a StateNoiseProcessor: the envs the last noisy row terminated restart)
         obs = ps.simulate(actions, references=references) if references is not None else ps.simulate(actions)
         pipe.after_step()
         return self._shown(obs), (ps.reward if references is not None else None), ps.done, False, {}
@@ -348,7 +372,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
     _REWARD_KEYS = ("reward_weights", "gamma", "reward_power", "bias", "violation_reward", "normed_reward_weights")
 
     def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None,
-                 flux_action=None):
+                 flux_action=None, state_noise=None):
         ps = physical_system
         d = default_modules or dict(reference_states=(), reward=dict())
         if observation is None and getattr(ps, "_obs_layout", "aos") != "aos":
@@ -370,12 +394,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             missing = sorted(set(rf["reward_weights"]) - set(ps.state_names))
             if missing:
                 raise ValueError(f"reward_weights name {missing}, which are not states of the physical system {list(ps.state_names)}")
-        self.reward_config = ps.set_reward(referenced_states=self.reference_names, **rf)
+        if state_noise is None:
+            self.reward_config = ps.set_reward(referenced_states=self.reference_names, **rf)
+        else:  # the reward is the noise stage's, on the noisy row: nothing is installed in the stepping kernels
+            kw = dict(reward_weights=None, normed_reward_weights=False, violation_reward=None, gamma=0.9, reward_power=1, bias=0.0)
+            kw.update(rf)
+            self.reward_config = ps._build_reward_config(kw["reward_weights"], self.reference_names, kw["normed_reward_weights"], kw["violation_reward"],
+                                                         kw["gamma"], kw["reward_power"], kw["bias"])
         self.reward_range = ps.reward_range
         lo, hi = gen.reference_space
         self.reference_space = Box(lo, hi, dtype=float)
         # (after the generator: a flat observation carries its n_ref columns)
-        super().__init__(ps, observation, _n_ref=len(self.reference_names), _defer_create=_defer_create, flux_action=flux_action)
+        super().__init__(ps, observation, _n_ref=len(self.reference_names), _defer_create=_defer_create, flux_action=flux_action, state_noise=state_noise,
+                         _reward_config=self.reward_config if state_noise is not None else None)
         flat = self.observation_stage is not None and self.observation_stage.flatten
         self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
         if flat:  # FlattenObservation of that Tuple: one box, state then reference
@@ -412,6 +443,9 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         args = (C.c_void_p(a.data_ptr()), 1, C.c_void_p(self._refs.data_ptr()) if int(self.reward_config.n_ref) else None, C.c_void_p(ps._obs_ptr),
                 C.c_void_p(ps._done_ptr), C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
         call, check = ps._L.gemx_rollout_reward, bps._lib.check
+        noisy = self.state_noise is not None
+        if noisy:  # the plain physics step: done and reward come from the noise stage behind it, on the noisy row
+            args, call = (C.c_void_p(a.data_ptr()), C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr), C.c_void_p(stream.cuda_stream)), ps._L.gemx_step
 
         def physics(_args=args, _call=call, _keep=keep):  # (hand-written, not `bound_call`: the host's step counter moves with it)
             rc = _call(ps._handle, *_args)
@@ -419,8 +453,9 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 check(rc)
             ps._k += 1
 
-        after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(ps._done, stream=stream))
-        return bps._lib.sequence(to_abc, physics, after, result=self._obs)
+        after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(ps._done, stream=stream),
+                                     reward=self._reward[0] if noisy else None)
+        return bps._lib.sequence(to_abc, pipe.bind_before_step(stream), physics, after, result=self._obs)
 
     def step(self, actions, references=None):
         """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches; three with
@@ -595,7 +630,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
     (or the reference's own instances), which are folded into the kernel's action stage, and of CurrentSumProcessor / CosSinProcessor
     holders, which become the device-side observation stage, and of FluxObserver / FluxOrientedDqToAbcActionProcessor holders (induction
-    machines: the flux-observer stage); 'default': `default_physical_system_wrappers(env_id)`.
+    machines: the flux-observer stage), and of at most one StateNoiseProcessor holder, listed before the observation-side ones (the
+    state-noise stage: constraints, auto-reset and reward then act on the noisy state); 'default': `default_physical_system_wrappers(env_id)`.
     observed_states: None | list of state names of the wrapped system -- the reference's `state_filter`, applied last.
     flatten_observation: the complete env hands out ONE tensor [N, n_post + n_ref], the processed state followed by the references.
     reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
@@ -614,11 +650,16 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
             raise ValueError("physical_system_wrappers: a tuple of wrapper holders or 'default'")
         physical_system_wrappers = default_physical_system_wrappers(env_id)
     chain = []
-    flux_action = None
+    flux_action = state_noise = None
     if physical_system_wrappers:
         folded = fold_wrappers(physical_system_wrappers, observation_chain=chain)
         flux_action = folded.pop("flux_action", None)  # (served by the flux-observer stage, not by the system's action stage)
+        state_noise = folded.pop("state_noise", None)  # (served by the state-noise stage behind the physics)
         kwargs = dict(kwargs, **folded)
+    if state_noise is not None and obs_layout != "aos":
+        from .state_noise import REFUSAL
+
+        raise NotImplementedError(REFUSAL + f"obs_layout={obs_layout!r} was asked for")
     observation = None
     if chain or observed_states is not None or flatten_observation:
         if obs_layout != "aos":
@@ -641,13 +682,19 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         n_envs=n_envs,
         device=device,
         dtype=dtype,
-        constraints=d["constraints"] if constraints is None else constraints,
-        auto_reset=auto_reset,
+        # (a StateNoiseProcessor: constraints, auto-reset and reward move behind the noise -- the physics has none of them)
+        constraints=() if state_noise is not None else (d["constraints"] if constraints is None else constraints),
+        auto_reset=False if state_noise is not None else auto_reset,
         obs_layout=obs_layout,
         **kwargs,
     )
+    if state_noise is not None:
+        limit_mask, squared_mask = system._constraint_masks(tuple(d["constraints"] if constraints is None else constraints))
+        state_noise = dict(state_noise, limit_mask=limit_mask, squared_mask=squared_mask,
+                           auto_reset=(n_envs > 1 and bool(limit_mask or squared_mask)) if auto_reset is None else bool(auto_reset))
     if reference_generator is None and reward_function is None:
-        return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)), flux_action=flux_action)
+        return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)), flux_action=flux_action,
+                                       state_noise=state_noise)
     from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator
 
     modules = default_env_modules(env_id)
@@ -665,4 +712,5 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     if not (reward_function is None or isinstance(reward_function, dict) or (isinstance(reward_function, str) and reward_function == "default")):
         raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
     return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,
-                                           _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation, flux_action=flux_action)
+                                           _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation, flux_action=flux_action,
+                                           state_noise=state_noise)

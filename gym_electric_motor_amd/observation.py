@@ -243,21 +243,33 @@ class ObservationStage:
 
 class ObservationPipeline:
     """Everything between a physical system's raw state rows and the state an env hands out, for BOTH env shells, and the one place
-    where the order of the launches after the physics lives:
+    where the order of the launches around the physics lives:
 
-        the flux observer on the raw rows -> `rows` [.., n_base + 2]      (when the chain holds a FluxObserver)
+        the masked reset of the envs the last NOISY row terminated, IN FRONT of the physics    (with a StateNoiseProcessor: `noise`)
+        the noise on the raw rows, done and reward on the noisy row -> `noisy` [N, n_base]    (with a StateNoiseProcessor)
+        the flux observer on the raw (noisy) rows -> `rows` [.., n_base + 2]      (when the chain holds a FluxObserver)
         the column program on those rows, reading the references when the observation is flat -> `state`   (unless it is the identity)
 
     `observation`: None (no stage: `state` is the system's own buffer and nothing is launched) or dict(chain=, observed_states=,
     flatten=); `n_ref`: the reference columns a flat observation carries; `flux_action`: None | 'SCIM' | 'DFIM', the flux-oriented dq
     action processor.  Owns the stage, the observer, `rows`, the dq processor's `abc` scratch, the `state` buffer and the raw and
-    extended scratch trajectories of the K-step rollouts; every refusal of a combination is raised here."""
+    extended scratch trajectories of the K-step rollouts; every refusal of a combination is raised here.
+    `noise`: None or the StateNoiseProcessor's spec (state_noise.py) with the constraint masks and the auto-reset the user asked for -- the
+    system itself then has neither; `reward_config`: the reward the noise stage evaluates on the noisy row (the complete env's).  The
+    system's own `done` buffer carries the NOISY done mask: the physics clears it, the noise stage behind it writes it, and the reset in
+    front of the next physics reads it."""
 
-    def __init__(self, physical_system, observation=None, n_ref=0, flux_action=None, defer_create=False):
+    def __init__(self, physical_system, observation=None, n_ref=0, flux_action=None, defer_create=False, noise=None, reward_config=None):
         ps = self.physical_system = physical_system
-        self.stage = self.flux = self.flux_action = self.raw_scratch = self.ext_scratch = None
+        self.stage = self.flux = self.flux_action = self.raw_scratch = self.ext_scratch = self.noise = None
         self.flux_only = self.has_program = False
         self.action_space = ps.action_space
+        if noise is not None:
+            from .state_noise import REFUSAL, StateNoiseStage
+
+            if getattr(ps, "_obs_layout", "aos") != "aos":
+                raise NotImplementedError(REFUSAL + "obs_layout='soa' was asked for")
+            self.noise = StateNoiseStage(ps, noise, reward_config)
         if observation is None:
             if flux_action:
                 raise ValueError("the flux-oriented dq action processor needs a FluxObserver")
@@ -267,6 +279,8 @@ class ObservationPipeline:
             stage = self.stage = ObservationStage(ps, observation.get("chain", ()), observation.get("observed_states"), observation.get("flatten", False),
                                                   n_ref=n_ref, flux_action=flux_action)
             self.flux, self.flux_action = stage.flux, flux_action
+            if self.flux is not None and self.noise is not None:
+                self.flux.auto_reset = self.noise.auto_reset  # (the system itself runs without auto-reset: the observer follows the env's)
             self.flux_only = self.flux is not None and stage.is_identity  # (the extended row IS the observation: no column program to run)
             self.has_program = not self.flux_only
             if flux_action:
@@ -280,6 +294,10 @@ class ObservationPipeline:
 
         new = lambda *shape: torch.zeros(shape, dtype=ps._tdtype, device=ps._tdev)  # noqa: E731
         self.rows = self.state = ps._obs
+        if self.noise is not None:
+            self.noise.create(ps.n_envs, ps._device, ps._dtype_name)
+            self.noisy = self.rows = self.state = new(ps.n_envs, self.noise.n_in)
+            self._reset_done = torch.zeros(ps.n_envs, dtype=torch.uint8, device=ps._tdev)  # (a reset row is noised, never checked: core.py:312)
         if self.flux is not None:
             self.flux.set_reset_observation(ps.reset_observation)
             self.flux.create(ps.n_envs, ps._device, ps._dtype_name)
@@ -291,6 +309,10 @@ class ObservationPipeline:
             self.state = new(ps.n_envs, self.stage.n_out)
 
     def refuse_rollout(self):
+        if self.noise is not None:
+            from .state_noise import ROLLOUT_REFUSAL as NOISE_ROLLOUT_REFUSAL
+
+            raise NotImplementedError(NOISE_ROLLOUT_REFUSAL)
         if self.flux_action:
             from .flux_observer import ROLLOUT_REFUSAL
 
@@ -312,14 +334,36 @@ class ObservationPipeline:
         shape = tuple(self.physical_system._obs.shape)
         return self._scratch("raw_scratch", shape if last_only else (K,) + shape)
 
-    # ------------------------------------------------------------------ the launches after the physics
-    def bind_after_step(self, refs=None, stream=None, generators=None):
-        """-> zero-argument launch() of what follows a step's physics, or None when there is nothing to run: the observer on the system's
-        fresh rows and done mask, then `generators` (the complete env's reference step: a flat observation carries what it writes into
-        `refs` [N, n_ref]), then the column program into `state`."""
+    # ------------------------------------------------------------------ the launches around the physics
+    def bind_before_step(self, stream=None):
+        """-> zero-argument launch() of what precedes a step's physics, or None: with a StateNoiseProcessor (and auto-reset) the masked
+        `gemx_reset` of the envs whose last noisy row terminated -- one asynchronous launch, no observation written, no host state."""
+        if self.noise is None or not self.noise.auto_reset:
+            return None
+        import torch
+
         ps = self.physical_system
-        observer = self.flux.bind_step(ps._obs, ps._done, self.rows, stream) if self.flux is not None else None
-        return _lib.sequence(observer, generators, self.stage.bind_apply(self.rows, refs, self.state, stream) if self.has_program else None)
+        stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
+        args = (C.c_void_p(ps._done_ptr), None, C.c_void_p(stream.cuda_stream))
+        return _lib.bound_call(ps._L.gemx_reset, ps, args, (ps._done, stream))
+
+    def before_step(self):
+        """`bind_before_step` on the current stream, run once."""
+        launch = self.bind_before_step()
+        if launch is not None:
+            launch()
+
+    def bind_after_step(self, refs=None, stream=None, generators=None, reward=None):
+        """-> zero-argument launch() of what follows a step's physics, or None when there is nothing to run: the noise stage on the system's
+        fresh rows (noisy rows, the done mask and -- `reward` [N] given -- the reward against `refs` as they stand, i.e. as the previous
+        observation showed them), the observer on the (noisy) rows and the done mask, then `generators` (the complete env's reference
+        step: a flat observation carries what it writes into `refs` [N, n_ref]), then the column program into `state`."""
+        ps = self.physical_system
+        noise, src = None, ps._obs
+        if self.noise is not None:
+            noise, src = self.noise.bind_step(ps._obs, refs, self.noisy, ps._done, reward, stream), self.noisy
+        observer = self.flux.bind_step(src, ps._done, self.rows, stream) if self.flux is not None else None
+        return _lib.sequence(noise, observer, generators, self.stage.bind_apply(self.rows, refs, self.state, stream) if self.has_program else None)
 
     def after_step(self, refs=None):
         """`bind_after_step` on the current stream, run once -> `state`."""
@@ -354,11 +398,17 @@ class ObservationPipeline:
 
     def reset(self, refs=None):
         """After the system's reset: the observer's, the extended reset rows -- the system's, then [0, 0] (flux_observer.py:80-83) --
-        and the column program -> `state`."""
+        and the column program -> `state`.  With a StateNoiseProcessor the reset rows are noised first (state_noise_processor.py:70-74: one
+        stream position), and no env is left waiting for a restart."""
+        src = self.physical_system._obs
+        if self.noise is not None:
+            self.physical_system._done.zero_()
+            self.noise.step(src, None, self.noisy, self._reset_done)
+            src = self.noisy
         if self.flux is not None:
             self.flux.reset()
             nb = self.flux.n_in
-            self.rows[:, :nb].copy_(self.physical_system._obs)
+            self.rows[:, :nb].copy_(src)
             self.rows[:, nb:].zero_()
         if self.has_program:
             self.stage.apply(self.rows, refs, out=self.state)
@@ -379,6 +429,8 @@ class ObservationPipeline:
         return self.flux.bind_actions(dq, self.abc, stream)
 
     def close(self):
+        if self.noise is not None:
+            self.noise.close()
         if self.stage is not None:
             self.stage.close()
         if self.flux is not None:

@@ -24,8 +24,15 @@ As in the reference, wrappers are applied innermost first: `(DeadTimeProcessor(2
 delays the abc action by two steps and lets the dq processor advance its angle by 0.5 + 2 steps (lines 83-86); an observation-side
 processor sees the state names of everything listed before it.  The two sides do not interact, so they may be listed in any order.
 The flux-oriented processor reads the observer's angle: it must be listed after a `FluxObserver` and after any `DeadTimeProcessor`.
-Outside the accelerated path: `StateNoiseProcessor` (the reference checks constraints and computes the reward on the NOISY state,
-core.py:344-350, and those are fused into the stepping kernels).
+
+STATE NOISE, a stage of its own directly behind `simulate()` (state_noise.py, csrc/gemx_statenoise.hip): the reference checks the
+constraints and computes the reward on the NOISY state (core.py:344-350), so with this wrapper the physics runs without constraints,
+auto-reset and fused reward, ONE launch adds the noise and decides `done` and the reward on the noisy row, and the env restarts the
+terminated envs with a masked reset in front of the next step.  At most one, on states of the base system, listed before every
+observation-side processor and `FluxObserver` (which then read the noisy row); the fused K-step rollouts refuse it.
+
+    StateNoiseProcessor(states[, random_dist][, random_kwargs])   physical_system_wrappers/state_noise_processor.py:4-92
+                                                                  ('normal', 'uniform', 'laplace')
 """
 
 
@@ -135,9 +142,39 @@ class CosSinProcessor:
         return self._angle
 
 
-STATE_NOISE_REFUSAL = ("StateNoiseProcessor is not on the accelerated path: the reference checks the constraints and computes the reward on the NOISY "
-                       "state (core.py:344-350), and the done mask, the auto-reset and the reward are fused into the stepping kernels, which a pass "
-                       "over their output cannot reproduce")
+class StateNoiseProcessor:
+    """Adds random noise to the named states (state_noise_processor.py:31-92; the reference's keywords and defaults): `random_dist` is
+    'normal', 'uniform' or 'laplace', `random_kwargs` numpy's keywords of that distribution -- scalars, or sequences of one value per
+    state, as numpy broadcasts them over size=(random_length, len(states)).  `random_length` is accepted and unused: it only batches
+    numpy's draws.  Constraints, reward and `terminated` are evaluated on the noisy state, as in the reference's env shell."""
+
+    def __init__(self, states, random_dist="normal", random_kwargs=(), random_length=1000, physical_system=None):
+        self._random_kwargs = dict(random_kwargs)
+        self._random_length = int(random_length)
+        self._states = states
+        self._random_dist = random_dist
+
+    @property
+    def random_kwargs(self):
+        return self._random_kwargs
+
+    @random_kwargs.setter
+    def random_kwargs(self, value):
+        self._random_kwargs = dict(value)
+
+
+def _state_noise_spec(w):
+    """dict(states=, dist=, kwargs=) of a StateNoiseProcessor (this module's holder or the reference's instance, read by its attributes);
+    NotImplementedError for an object whose parameters cannot be read and for a distribution the device does not draw."""
+    from .state_noise import DISTRIBUTIONS, REFUSAL
+
+    try:
+        states, dist, kwargs = w._states, w._random_dist, dict(w._random_kwargs)
+    except (AttributeError, TypeError, ValueError):
+        raise NotImplementedError(REFUSAL + f"the parameters of this {type(w).__name__} cannot be read (_states, _random_dist, _random_kwargs)") from None
+    if dist not in DISTRIBUTIONS:
+        raise NotImplementedError(REFUSAL + f"random_dist {dist!r} is not drawn on the device")
+    return dict(states=states if isinstance(states, str) else tuple(states), dist=dist, kwargs=kwargs)
 
 
 def _observation_spec(w, names):
@@ -172,14 +209,18 @@ def fold_wrappers(wrappers, observation_chain=None):
     Accepts this module's holders and the reference's own instances (by class name).  The observation-side processors
     (CurrentSumProcessor, CosSinProcessor, FluxObserver), in any position, are appended to the list `observation_chain` as specs for
     `observation.ObservationStage`, innermost first; without such a list they are refused like any other wrapper the kernels' action stage
-    cannot hold."""
+    cannot hold.  A StateNoiseProcessor comes back as `state_noise=dict(states=, dist=, kwargs=)` -- not a BatchedSCMLSystem argument
+    either: make() hands it to the env."""
+    from .state_noise import REFUSAL as NOISE_REFUSAL
+
     delay, frame, seen_dq, reset_row = 0, None, False, None  # frame None: leave it to the system's control_space
-    seen_flux, flux_action = False, None
+    seen_flux, flux_action, noise, seen_obs = False, None, None, False
     for w in wrappers:
         names = {c.__name__ for c in type(w).__mro__}
         spec = _observation_spec(w, names)
         flux_kind = _flux_action_kind(w, names)
         if spec is not None and observation_chain is not None:
+            seen_obs = True
             if spec[0] == "flux":
                 if seen_flux:
                     raise ValueError("one FluxObserver per system")
@@ -192,7 +233,11 @@ def fold_wrappers(wrappers, observation_chain=None):
                 raise ValueError("one dq action processor per system")
             flux_action, seen_dq = flux_kind, True
         elif "StateNoiseProcessor" in names:
-            raise NotImplementedError(STATE_NOISE_REFUSAL)
+            if noise is not None:
+                raise NotImplementedError(NOISE_REFUSAL + "a second StateNoiseProcessor was listed")
+            if seen_obs:  # (an inner observation-side processor would read the clean row, and its columns could be noised)
+                raise NotImplementedError(NOISE_REFUSAL + "this one is listed behind an observation-side processor (noise on appended columns)")
+            noise = _state_noise_spec(w)
         elif "DeadTimeProcessor" in names:
             if seen_dq:
                 raise ValueError("DeadTimeProcessor must be wrapped INSIDE the DqToAbcActionProcessor (listed before it), as the "
@@ -216,4 +261,6 @@ def fold_wrappers(wrappers, observation_chain=None):
         out["flux_action"] = flux_action  # (not a BatchedSCMLSystem argument: make() takes it out and hands it to the env)
     if reset_row is not None and any(reset_row):
         out["action_delay_reset"] = reset_row
+    if noise is not None:
+        out["state_noise"] = noise
     return out

@@ -536,6 +536,50 @@ int gemx_fluxobs_actions(gemx_fluxobs *h, const void *dq_dev, void *abc_out_dev,
 int gemx_fluxobs_get_state(gemx_fluxobs *h, double *out_dev, void *stream);
 int gemx_fluxobs_set_state(gemx_fluxobs *h, const double *in_dev, void *stream);
 
+/* Device-side STATE NOISE (new struct and entry points only, ABI number unchanged): the reference's StateNoiseProcessor
+ * (physical_system_wrappers/state_noise_processor.py:62-92) and what its env shell then evaluates on the NOISY state (core.py:344-350) --
+ * the constraint monitor and the reward -- as one stage behind a stepping kernel that runs WITHOUT constraints, auto-reset and reward.
+ * The caller feeds done_out back as the mask of gemx_reset before its next gemx_step.
+ *   gemx_noise_step: ONE launch.  state_in_dev [N][n_in] R -> state_out_dev [N][n_in] R = the row plus, on column index[j], the draw of
+ *     (env, slot j, position), evaluated in double and rounded to R before the add; every other column keeps its bits.  state_in_dev ==
+ *     state_out_dev is allowed (any other overlap is not).  done_out_dev [N] uint8 = the constraints of limit_mask / squared_mask (as in
+ *     gemx_config) on the noisy row, with the expressions and the term order of the stepping kernels.  reward_out_dev [N] R (may be NULL;
+ *     needs has_reward) = the reward description evaluated on the noisy row against refs_dev [N][n_ref] R with the arithmetic of
+ *     gemx_reward_rows, violation_reward where done.  Then the position advances by one.
+ *   gemx_noise_draws: out_dev [K][N][n_noisy] R = the draws of positions step0 .. step0 + K - 1, as gemx_noise_step adds them; the
+ *     position does not move (cf. gemx_synthetic_actions).
+ *   gemx_noise_get_position (synchronises `stream`) / gemx_noise_set_position: the stream position, for a checkpoint.
+ * Distributions, per slot: NORMAL(param0 = loc, param1 = scale) by Box-Muller, UNIFORM(param0 = low, param1 = high) and
+ * LAPLACE(param0 = loc, param1 = scale) by the inverse distribution function, from counter-based Philox4x32-10 words: the draw is a pure
+ * function of (seed, env_base + env, position, slot) -- shards by env_base draw what the whole job draws; parity with numpy's streams is
+ * distributional.  The position lives in device memory: a call allocates nothing, never synchronises and can be captured in a HIP graph
+ * whose replays advance the stream.  The tensors need the alignment of R only.
+ * GEMX_ERR_ARG at create: a null pointer, struct_size, n_in outside [1, GEMX_MAX_OUT], n_noisy outside [0, n_in], an index outside
+ * [0, n_in) or listed twice, an unknown distribution, a negative scale or high < low, a mask bit >= n_in, has_reward not 0 | 1, and what
+ * gemx_set_reward refuses of the reward description. */
+enum { GEMX_NOISE_NORMAL = 0, GEMX_NOISE_UNIFORM = 1, GEMX_NOISE_LAPLACE = 2 };
+typedef struct gemx_noise_config {
+    int32_t struct_size;         /* = sizeof(gemx_noise_config) */
+    int32_t n_in;                /* columns of a state row: 1..GEMX_MAX_OUT */
+    int32_t n_noisy;             /* noisy columns (slots): 0..n_in */
+    int32_t has_reward;          /* 1: `reward` below is evaluated on the noisy row; 0: no reward */
+    int32_t index[GEMX_MAX_OUT]; /* column of slot j */
+    int32_t dist[GEMX_MAX_OUT];  /* GEMX_NOISE_* of slot j */
+    double param0[GEMX_MAX_OUT], param1[GEMX_MAX_OUT]; /* loc, scale | low, high */
+    uint64_t seed;
+    int64_t env_base;            /* global index of env 0 (see gemx_config.env_base) */
+    uint32_t limit_mask, squared_mask; /* the constraints, as in gemx_config, evaluated on the noisy row */
+    gemx_reward_config reward;
+} gemx_noise_config;
+typedef struct gemx_noise gemx_noise;
+int gemx_noise_create(const gemx_noise_config *cfg, int64_t n_envs, int dtype, int device, gemx_noise **out);
+int gemx_noise_destroy(gemx_noise *h);
+int gemx_noise_step(gemx_noise *h, const void *state_in_dev, const void *refs_dev, void *state_out_dev, uint8_t *done_out_dev,
+                    void *reward_out_dev, void *stream);
+int gemx_noise_draws(gemx_noise *h, uint64_t step0, int32_t K, void *out_dev, void *stream);
+int gemx_noise_get_position(gemx_noise *h, uint64_t *position_host, void *stream);
+int gemx_noise_set_position(gemx_noise *h, uint64_t position, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
