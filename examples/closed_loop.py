@@ -6,6 +6,7 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
     python examples/closed_loop.py --complete [--bind | --graph 64]                     # the same loop through the complete env
     python examples/closed_loop.py --complete --graph 64 --reference step               # ... on step (sinusoidal, ...) profiles
     python examples/closed_loop.py --complete --rollout 500                             # open loop: (state, reference, reward, done) datasets
+    python examples/closed_loop.py --complete --graph 64 --time-limit 500               # episodes of 500 steps, counted on the device
 
 Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
 step per control step.  `--complete`: `ga.make(..., reference_generator="default")` does the wiring -- two launches per control step (physics +
@@ -13,6 +14,8 @@ reward, then the fused generator step), `--bind` with everything resolved once (
 `--complete --rollout K`: no policy in the loop -- random actions generated on the device, K control steps per `rollout_complete_synthetic`
 call (physics rollout, generator rollout in the shell's order, reward pass: three launches per K steps), i.e. the dataset a closed loop
 of K `step()`s on the same actions would have produced, bit for bit.
+`--complete --time-limit M`: `make(..., max_episode_steps=M, episode_statistics=True)` -- an env is truncated after M steps and restarts in
+front of its next step; the mean return and length of the finished episodes come from the device counters (`env.episode_statistics()`).
 
 The same loop with the reference package is `env.step(policy(obs))` on ONE env per Python call (reference: core.py:329-372).
 """
@@ -41,7 +44,11 @@ def main():
     ap.add_argument("--flat", action="store_true", help="--complete: the device-side observation stage hands the policy ONE flat tensor "
                                                         "(i_sd, i_sq, cos(epsilon), sin(epsilon), reference i_sd, reference i_sq)")
     ap.add_argument("--rollout", type=int, default=0, metavar="K", help="--complete: open-loop datasets, K control steps per rollout_complete_synthetic call")
+    ap.add_argument("--time-limit", type=int, default=0, metavar="M", help="--complete: episodes of at most M steps (max_episode_steps) and the device-side "
+                                                                            "episode statistics")
     args = ap.parse_args()
+    if args.time_limit and (not args.complete or args.rollout):
+        ap.error("--time-limit needs --complete (and no --rollout: a fused K-step launch cannot restart a truncated env)")
     if args.rollout and (not args.complete or args.bind or args.graph):
         ap.error("--rollout needs --complete (and neither --bind nor --graph)")
     if args.reference != "wiener" and not args.complete:
@@ -100,6 +107,8 @@ def complete(args):
     if args.flat:  # cos / sin instead of the angle, the four columns the policy reads, state and references in one tensor
         wrappers += (ga.CosSinProcessor(remove_angle=True),)
         obs_kw = dict(observed_states=["i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"], flatten_observation=True)
+    if args.time_limit:
+        obs_kw.update(max_episode_steps=args.time_limit, episode_statistics=True)
     env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw)
     ps = env.physical_system
     if args.rollout:
@@ -155,7 +164,21 @@ def complete(args):
     print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
           f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
     assert torch.isfinite(ret).all()
+    episode_report(env)
     env.close()
+
+
+def episode_report(env):
+    """--time-limit: the finished episodes, from the device counters."""
+    if env.episodes is None:
+        return
+    stats = env.episode_statistics()
+    finished = stats["n_finished"] > 0
+    if not bool(finished.any()):
+        print("episodes: none finished yet")
+        return
+    print(f"episodes (limit {env.episodes.max_steps}): {int(stats['n_finished'].sum())} finished; last finished per env: mean return "
+          f"{float(stats['last_ret'][finished].mean()):.2f}, mean length {float(stats['last_length'][finished].double().mean()):.1f}")
 
 
 def rollout_loop(args, env):
@@ -229,6 +252,7 @@ def flat_loop(args, env):
     print(f"complete env ({mode}, {args.reference} references): {n} envs x {steps} closed-loop steps in {dt:.3f} s = {n * steps / dt / 1e6:.1f} M env-steps/s "
           f"({dt / steps * 1e6:.1f} us/step); mean return {float(ret.mean()):.2f}")
     assert torch.isfinite(ret).all()
+    episode_report(env)
     env.close()
 
 

@@ -168,6 +168,14 @@ class GemxNoiseConfig(C.Structure):
     ]
 
 
+class GemxEpisodeConfig(C.Structure):
+    """Mirror of `gemx_episode_config` (include/gemx.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("max_steps", C.c_int32), ("auto_reset_in_kernel", C.c_int32), ("has_reward", C.c_int32)]
+
+
+EPISODE_STATE_BYTES = 28  # GEMX_EPISODE_STATE_BYTES
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
@@ -180,6 +188,7 @@ EXPORTS = (
     "gemx_fluxobs_create", "gemx_fluxobs_destroy", "gemx_fluxobs_reset", "gemx_fluxobs_step", "gemx_fluxobs_rows", "gemx_fluxobs_actions",
     "gemx_fluxobs_get_state", "gemx_fluxobs_set_state",
     "gemx_noise_create", "gemx_noise_destroy", "gemx_noise_step", "gemx_noise_draws", "gemx_noise_get_position", "gemx_noise_set_position",
+    "gemx_episode_create", "gemx_episode_destroy", "gemx_episode_step", "gemx_episode_rows", "gemx_episode_get_state", "gemx_episode_set_state",
 )
 
 
@@ -254,6 +263,12 @@ def load():
     L.gemx_noise_draws.argtypes = [vp, C.c_uint64, i32, vp, vp]
     L.gemx_noise_get_position.argtypes = [vp, C.POINTER(C.c_uint64), vp]
     L.gemx_noise_set_position.argtypes = [vp, C.c_uint64, vp]
+    L.gemx_episode_create.argtypes = [C.POINTER(GemxEpisodeConfig), i64, C.c_int, C.c_int, vp, C.POINTER(vp)]
+    L.gemx_episode_destroy.argtypes = [vp]
+    L.gemx_episode_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.gemx_episode_rows.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
+    L.gemx_episode_get_state.argtypes = [vp, vp, vp]
+    L.gemx_episode_set_state.argtypes = [vp, vp, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

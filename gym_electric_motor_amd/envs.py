@@ -64,6 +64,20 @@ launch cannot restart an env on a done mask it has not seen.
     env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator="default",
                   physical_system_wrappers=(ga.StateNoiseProcessor(["i_sd", "i_sq"], "normal", dict(scale=0.01)),))
 
+Episode time limit and episode statistics (episodes.py, csrc/gemx_episode.hip): `max_episode_steps=M` is gymnasium's TimeLimit on the device,
+`episode_statistics=True` its RecordEpisodeStatistics -- ONE launch more per step, directly behind the launch that writes reward and
+`terminated` and before the generators.  With a time limit `step()` hands out `truncated` [N] (bool) in the fourth slot; the observation
+of a truncating step is the final state, and the truncated envs restart in front of the next step's physics (one more launch: the masked
+reset), their generators and flux observer with them.  A step that terminates and reaches the limit at once counts as terminated.
+`env.episode_statistics()` -> dict(length, ret, last_length, last_ret, n_finished): [N] device tensors, views of the stage's state; the
+return accumulates in float64.  The K-step rollouts run the statistics as one pass over their stored rows (`episode_statistics=True`:
+a fifth result, dict(ended, finished_return, finished_length) [K, N]); with a time limit they raise: a K-step launch cannot restart an
+env on a mask it has not seen.  The physics-only env counts lengths (it has no reward of its own: `ret` stays 0).
+
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=4096, reference_generator="default", max_episode_steps=1000, episode_statistics=True)
+    obs, reward, terminated, truncated, _ = env.step(actions)
+    stats = env.episode_statistics()                    # stats["last_ret"][stats["n_finished"] > 0].mean()
+
 Outside the accelerated path: reward weights or constraints on appended columns (`i_sum`,
 `cos(...)`, `psi_abs`, `psi_angle`) and visualisation; an instance of the reference's own `SwitchedReferenceGenerator` is refused (pass the holder of that
 name).  For a full single-env GEM environment pass a `BatchedSCMLSystem(n_envs=1)` as
@@ -249,8 +263,10 @@ def default_ode_solver(env_id, tau=None, load=None):
 class BatchedElectricMotorEnv:
     """Vector-env style shell around a batched physical system (physics + done mask only)."""
 
-    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None, state_noise=None, _reward_config=None):
-        """flux_action: None | 'SCIM' | 'DFIM' -- the flux-oriented dq action processor (needs a FluxObserver in the observation chain).
+    def __init__(self, physical_system, observation=None, _n_ref=0, _defer_create=False, flux_action=None, state_noise=None, _reward_config=None,
+                 episodes=None, _episode_reward=False):
+        """episodes: None | dict(max_steps=, statistics=) -- the episode stage (`make(max_episode_steps=, episode_statistics=)`).
+        flux_action: None | 'SCIM' | 'DFIM' -- the flux-oriented dq action processor (needs a FluxObserver in the observation chain).
         state_noise: None | the StateNoiseProcessor's spec with the constraint masks and the auto-reset asked for (`make` builds it; the
         system itself then has no constraints and no auto-reset): `terminated` and the returned state are the noisy ones.
         observation: None, or dict(chain=, observed_states=, flatten=) for a device-side `ObservationStage` behind the system: `reset()`,
@@ -261,21 +277,34 @@ class BatchedElectricMotorEnv:
         self.physical_system = physical_system
         self.n_envs = physical_system.n_envs
         pipe = self.pipeline = ObservationPipeline(physical_system, observation, _n_ref, flux_action, _defer_create, noise=state_noise,
-                                                   reward_config=_reward_config)
+                                                   reward_config=_reward_config, episode=episodes, episode_reward=_episode_reward)
+        self.episodes = pipe.episode
         self.observation_stage, self.flux, self.flux_action, self._flux_only = pipe.stage, pipe.flux, pipe.flux_action, pipe.flux_only
         self.state_noise = pipe.noise
         self.action_space = pipe.action_space
         self.state_space = physical_system.state_space if pipe.stage is None else pipe.stage.observation_space
         self.state_names = list(physical_system.state_names if pipe.stage is None else pipe.stage.observation_names)
 
+    truncated = property(lambda self: self.pipeline.truncated, doc="[N] bool: the envs the last step truncated (False without a time limit)")
+
+    def episode_statistics(self):
+        """-> dict(length, ret, last_length, last_ret, n_finished): [N] device tensors, views of the episode stage's state -- the running
+        episode's steps and return (float64), the totals of the episode that ended last, the number of finished episodes."""
+        if self.episodes is None or not self.episodes.statistics:
+            raise ValueError("this env keeps no episode statistics: build it with make(..., episode_statistics=True)")
+        return self.episodes.fields()
+
     def get_checkpoint(self):
         """`physical_system.get_checkpoint()`, plus the flux observer's per-env state (`flux_observer`: float64 [4, N]) when the env has one,
-        plus, with a StateNoiseProcessor, `state_noise`: the stream position and the done mask whose envs restart in front of the next step."""
+        plus, with a StateNoiseProcessor, `state_noise`: the stream position and the done mask whose envs restart in front of the next step,
+        plus, with an episode stage, `episodes`: its state blob and the mask of the reset in front of the next step."""
         ck = self.physical_system.get_checkpoint()
         if self.flux is not None:
             ck["flux_observer"] = self.flux.get_state()
         if self.state_noise is not None:
             ck["state_noise"] = dict(position=self.state_noise.get_position(), done=self.physical_system._done.clone())
+        if self.episodes is not None:
+            ck["episodes"] = dict(state=self.episodes.get_state(), reset_mask=self.episodes.reset_mask.clone())
         return ck
 
     def set_checkpoint(self, ckpt):
@@ -286,6 +315,9 @@ class BatchedElectricMotorEnv:
         if self.state_noise is not None:
             self.state_noise.set_position(ckpt["state_noise"]["position"])
             self.physical_system._done.copy_(ckpt["state_noise"]["done"])
+        if self.episodes is not None:
+            self.episodes.set_state(ckpt["episodes"]["state"])
+            self.episodes.reset_mask.copy_(ckpt["episodes"]["reset_mask"])
 
     @property
     def unwrapped(self):
@@ -310,7 +342,7 @@ class BatchedElectricMotorEnv:
         return self._shown(raw), {}
 
     def step(self, actions, references=None):
-        """-> (obs [N, S_out], reward, terminated [N] uint8, truncated=False, {}).  reward: [N] device tensor when a reward function is
+        """-> (obs [N, S_out], reward, terminated [N] uint8, truncated, {}); truncated: False, or with a time limit [N] bool.  reward: [N] device tensor when a reward function is
         installed (`physical_system.set_reward`) and `references [N, n_ref]` are passed, else None.  With auto_reset (default for
         n_envs > 1) an env that terminated restarts from the reset state on its next step; the state it shows
         right after that restart is `physical_system.reset_observation`."""
@@ -321,39 +353,50 @@ class BatchedElectricMotorEnv:
         if self.flux_action:  # launch 1 of 4: the dq actions rotated into the frame the last observation left
             pipe.bind_actions(pipe.dq_to_device(actions))()
             actions = pipe.abc
-        pipe.before_step()  # (a StateNoiseProcessor: the envs the last noisy row terminated restart)
+        pipe.before_step()  # (a StateNoiseProcessor: the envs the last noisy row terminated restart; a time limit: the truncated ones)
         obs = ps.simulate(actions, references=references) if references is not None else ps.simulate(actions)
         pipe.after_step()
-        return self._shown(obs), (ps.reward if references is not None else None), ps.done, False, {}
+        return self._shown(obs), (ps.reward if references is not None else None), ps.done, pipe.truncated, {}
 
     def _rollout(self, physics, K, obs_out, kw):
         """A physics rollout into the pipeline's raw rows, then its launches: ONE pass over the stored rows writes the processed
         `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
         pipe = self.pipeline
         pipe.refuse_rollout()
+        want = kw.pop("episode_statistics", None)
+        if pipe.episode is None and want:
+            pipe.bind_episode_rows(None, outputs=want)  # (raises: the env has no stage)
         res = physics(obs_out=pipe.raw_rows(K, obs_out, kw.get("last_only", False)), **kw)
-        return (pipe.after_rollout(res[0], res[1], None, obs_out),) + tuple(res[1:])
+        episodes, stats = pipe.bind_episode_rows(res[1], outputs=want)  # (the physics-only env: lengths, no reward)
+        if episodes is not None:
+            episodes()
+        return (pipe.after_rollout(res[0], res[1], None, obs_out),) + tuple(res[1:]) + ((stats,) if want else ())
 
     def rollout(self, actions, obs_out=None, **kw):
         """PhysicalSystem.rollout; with an observation stage the raw trajectory goes into a scratch tensor and ONE `apply` writes the
-        processed `[K, N, n_post]` trajectory (into `obs_out`, when given)."""
+        processed `[K, N, n_post]` trajectory (into `obs_out`, when given).  episode_statistics=True (an env with the episode stage): one
+        more result, dict(ended, finished_return, finished_length) [K, N] in the pipeline's scratch."""
         return self._rollout(lambda **k: self.physical_system.rollout(actions, **k), len(actions), obs_out, kw)
 
     def rollout_synthetic(self, K, obs_out=None, **kw):
         """K fused steps on random actions generated on the device (PhysicalSystem.rollout_synthetic)."""
         return self._rollout(lambda **k: self.physical_system.rollout_synthetic(K, **k), K, obs_out, kw)
 
-    def bind_rollout(self, actions, obs_out, done_out, stream=None):
+    def bind_rollout(self, actions, obs_out, done_out, stream=None, episode_statistics=None):
         """-> zero-argument launch(): the pre-bound `gemx_rollout` call for fixed tensors (PhysicalSystem.bind_rollout); with an
-        observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus the pipeline's launches."""
+        observation stage `obs_out` is the processed `[K, N, n_post]` tensor and a launch is the rollout plus the pipeline's launches.
+        episode_statistics: dict(ended=, finished_return=, finished_length=) of [K, N] tensors the episode stage's pass writes."""
         ps, pipe = self.physical_system, self.pipeline
         pipe.refuse_rollout()
-        if pipe.stage is None:
+        if pipe.stage is None and pipe.episode is None and not episode_statistics:
             return ps.bind_rollout(actions, obs_out, done_out, stream=stream)
+        if episode_statistics is True:
+            raise ValueError("bind_rollout: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
         raw = pipe.raw_rows(int(actions.shape[0]), obs_out)
-        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), pipe.bind_after_rollout(raw, done_out, None, obs_out, stream),
-                                 result=(obs_out, done_out))
+        episodes, stats = pipe.bind_episode_rows(done_out, outputs=episode_statistics, stream=stream)
+        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), episodes, pipe.bind_after_rollout(raw, done_out, None, obs_out, stream),
+                                 result=(obs_out, done_out) + ((stats,) if stats else ()))
 
     def close(self):
         self.pipeline.close()
@@ -372,7 +415,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
     _REWARD_KEYS = ("reward_weights", "gamma", "reward_power", "bias", "violation_reward", "normed_reward_weights")
 
     def __init__(self, physical_system, reference_generator, reward_function=None, default_modules=None, _defer_create=False, observation=None,
-                 flux_action=None, state_noise=None):
+                 flux_action=None, state_noise=None, episodes=None):
         ps = physical_system
         d = default_modules or dict(reference_states=(), reward=dict())
         if observation is None and getattr(ps, "_obs_layout", "aos") != "aos":
@@ -406,7 +449,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         self.reference_space = Box(lo, hi, dtype=float)
         # (after the generator: a flat observation carries its n_ref columns)
         super().__init__(ps, observation, _n_ref=len(self.reference_names), _defer_create=_defer_create, flux_action=flux_action, state_noise=state_noise,
-                         _reward_config=self.reward_config if state_noise is not None else None)
+                         _reward_config=self.reward_config if state_noise is not None else None, episodes=episodes, _episode_reward=True)
         flat = self.observation_stage is not None and self.observation_stage.flatten
         self.observation_space = (self.state_space, self.reference_space)  # gymnasium.spaces.Tuple((state box, reference box)), core.py:278
         if flat:  # FlattenObservation of that Tuple: one box, state then reference
@@ -433,7 +476,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
     def _launchers(self, a, stream):
         """-> zero-argument step() on the action tensor `a` with everything resolved, returning the observation: the dq -> abc actions
         (flux-oriented action processor only), physics + fused reward reading the generator's buffer, then the pipeline's launches
-        around the generator step on the fresh done mask, which writes that same buffer."""
+        around the generator step on the fresh done mask (with an episode stage: on `ended`), which writes that same buffer."""
         import ctypes as C
 
         ps, pipe = self.physical_system, self.pipeline
@@ -453,13 +496,14 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 check(rc)
             ps._k += 1
 
-        after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(ps._done, stream=stream),
-                                     reward=self._reward[0] if noisy else None)
+        after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(pipe.restart_mask, stream=stream),
+                                     reward=self._reward[0] if noisy else None, returns=self._reward[0])
         return bps._lib.sequence(to_abc, pipe.bind_before_step(stream), physics, after, result=self._obs)
 
     def step(self, actions, references=None):
-        """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated=False, {}).  Two kernel launches; three with
-        an observation stage, whose processed state (or flat `[N, n_post + n_ref]` observation) replaces the raw one."""
+        """-> ((state [N, S_out], ref [N, n_ref]), reward [N], terminated [N] uint8, truncated, {}); truncated: False, or with a time limit
+        [N] bool.  Two kernel launches; three with an observation stage, whose processed state (or flat `[N, n_post + n_ref]` observation)
+        replaces the raw one."""
         if references is not None:
             raise TypeError("the complete env generates its references: step(actions)")
         ps = self.physical_system
@@ -468,7 +512,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         key = (a.data_ptr(), stream.cuda_stream)
         if self._bound is None or self._bound[0] != key:  # (a loop that reuses its action tensor and stream resolves the launches once)
             self._bound = (key, self._launchers(a, stream))
-        return self._bound[1](), self._reward[0], ps._done, False, {}
+        return self._bound[1](), self._reward[0], ps._done, self.pipeline.truncated, {}
 
     def bind_step(self, action_buffer, stream=None):
         """A zero-argument `step()` for a closed loop that reuses ONE action tensor: -> `(step, (state, ref), reward, done)`; `step()`
@@ -529,10 +573,10 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 check(t, name, dtype, shape)
         return K
 
-    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False):
+    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False, episodes=None):
         """-> the launchers that follow the physics of a complete K-step rollout, in order, on fixed tensors: the generators in the shell's
-        order on the done mask; the reward of row k against the references shown before step k; the pipeline's launches over the stored
-        rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
+        order on the done mask; the reward of row k against the references shown before step k; `episodes` (the episode stage's pass over
+        the done and reward rows, directly behind the launch that completes them); the pipeline's launches over the stored rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
         rollouts continue from it)."""
         torch = bps._torch()
         ps, gen = self.physical_system, self.reference_generator
@@ -550,7 +594,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 with _on(stream):
                     shown.copy_(last)
 
-        return generators, reward, self.pipeline.bind_after_rollout(raw, done_out, refs_out, state_out, stream), show
+        return generators, reward, episodes, self.pipeline.bind_after_rollout(raw, done_out, refs_out, state_out, stream), show
 
     def bind_reward_rows(self, rows, refs_rows, done, reward_out, stream=None):
         """-> zero-argument launch() of the reward pass (`gemx_reward_rows`) on fixed tensors: the base system's rows [K, N, S] of a
@@ -565,17 +609,21 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 C.c_void_p(done.data_ptr()), int(rows.shape[0]), C.c_void_p(reward_out.data_ptr()), C.c_void_p(stream.cuda_stream))
         return bps._lib.bound_call(ps._L.gemx_reward_rows, ps, args, (rows, refs_rows, done, reward_out, stream))
 
-    def _rollout_complete(self, K, physics, outs):
+    def _rollout_complete(self, K, physics, outs, episode_statistics=None):
         """The eager entry points: allocate what was not given, run `physics(raw, done_out)` and then the tail, once."""
         torch = bps._torch()
         ps = self.physical_system
+        if self.pipeline.episode is None and episode_statistics:
+            self.pipeline.bind_episode_rows(None, outputs=episode_statistics)  # (raises: the env has no stage)
         outs = tuple(torch.empty(shape, dtype=torch.uint8 if i == 3 else ps._tdtype, device=ps._tdev) if t is None else t
                      for i, (t, shape) in enumerate(zip(outs, self._complete_shapes(K))))
         raw = self.pipeline.raw_rows(K, outs[0])
+        episodes, stats = self.pipeline.bind_episode_rows(outs[3], outs[2], episode_statistics)
         physics(raw, outs[3])
-        return bps._lib.sequence(*self._tail(K, raw, *outs, torch.cuda.current_stream(ps._tdev), eager=True), result=outs)()
+        result = outs + ((stats,) if episode_statistics else ())
+        return bps._lib.sequence(*self._tail(K, raw, *outs, torch.cuda.current_stream(ps._tdev), eager=True, episodes=episodes), result=result)()
 
-    def rollout_complete(self, actions, state_out=None, refs_out=None, reward_out=None, done_out=None):
+    def rollout_complete(self, actions, state_out=None, refs_out=None, reward_out=None, done_out=None, episode_statistics=None):
         """K complete control steps in THREE launches (four with an observation stage) instead of K x (two or three):
         -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], done [K, N]) -- exactly what K calls of `step(actions[k])` return,
         stacked, bit for bit.  The physics rollout writes the states and the done mask; the generators replay the shell's order on that
@@ -583,27 +631,33 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         observation stage `state` is the processed trajectory; with `flatten_observation=True` it is the flat `[K, N, n_post + n_ref]`
         tensor, and `refs` is still returned.  Afterwards `reference_generator.references` holds row K-1: `step()` and further rollouts
         continue the same sequence.  (`physical_system.done` / `.reward` and the internal state buffer keep what the last `step()` wrote,
-        as after `rollout()`.)  actions: [K, N, A] / [K, N], as `rollout` takes them."""
+        as after `rollout()`.)  actions: [K, N, A] / [K, N], as `rollout` takes them.
+        episode_statistics (an env built with `episode_statistics=True`; its counters follow every rollout either way): True -> a fifth
+        result dict(ended [K, N] uint8, finished_return [K, N] float64, finished_length [K, N] int32) -- an episode's totals at the row where
+        it ended, 0 elsewhere -- in the pipeline's scratch (the next rollout overwrites it), or a dict of the caller's tensors."""
         if not hasattr(actions, "shape") or len(actions.shape) < 1:
             raise ValueError("rollout_complete needs actions [K, N, A] / [K, N]")
         K = self._check_complete("rollout_complete", actions.shape[0], None, state_out, refs_out, reward_out, done_out)
         ps = self.physical_system
         a = ps._actions_to_device(actions, (K, ps._n_envs))
-        return self._rollout_complete(K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), (state_out, refs_out, reward_out, done_out))
+        return self._rollout_complete(K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), (state_out, refs_out, reward_out, done_out),
+                                      episode_statistics)
 
-    def rollout_complete_synthetic(self, K, seed=0, step0=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
+    def rollout_complete_synthetic(self, K, seed=0, step0=None, state_out=None, refs_out=None, reward_out=None, done_out=None, episode_statistics=None):
         """`rollout_complete` on the device-side action source (`physical_system.rollout_synthetic(K, seed, step0)`): no action tensor is
         read.  Equal, bit for bit, to `rollout_complete(physical_system.synthetic_actions(K, seed, step0))`."""
         K = self._check_complete("rollout_complete_synthetic", K, None, state_out, refs_out, reward_out, done_out)
         ps = self.physical_system
         return self._rollout_complete(K, lambda raw, done: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done),
-                                      (state_out, refs_out, reward_out, done_out))
+                                      (state_out, refs_out, reward_out, done_out), episode_statistics)
 
-    def bind_rollout_complete(self, actions, state_out, refs_out, reward_out, done_out, stream=None):
+    def bind_rollout_complete(self, actions, state_out, refs_out, reward_out, done_out, stream=None, episode_statistics=None):
         """-> zero-argument launch() of `rollout_complete` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
         done_out)`.  Everything -- handles, pointers, the stream -- is resolved here, once: a call allocates nothing and never
         synchronises, and every launch goes to ONE stream, so it can be captured with `torch.cuda.graph` (a linear graph) and replayed;
-        replays advance the physics and the generators.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
+        replays advance the physics and the generators.  A ReplayReferenceGenerator is refused: its row index lives on the host.
+        episode_statistics: dict(ended=, finished_return=, finished_length=) of [K, N] tensors the episode stage's pass writes (a bound
+        launch allocates nothing: `True` is refused); `launch()` then returns that dict as a fifth result."""
         if not hasattr(actions, "shape") or len(actions.shape) < 1:
             raise ValueError("bind_rollout_complete needs a device tensor of actions [K, N, A] / [K, N]")
         outs = (state_out, refs_out, reward_out, done_out)
@@ -616,7 +670,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps = self.physical_system
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
         raw = self.pipeline.raw_rows(K, state_out)
-        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), *self._tail(K, raw, *outs, stream), result=outs)
+        if episode_statistics is True:
+            raise ValueError("bind_rollout_complete: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
+        episodes, stats = self.pipeline.bind_episode_rows(done_out, reward_out, episode_statistics, stream)
+        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), *self._tail(K, raw, *outs, stream, episodes=episodes),
+                                 result=outs + ((stats,) if stats else ()))
 
     def close(self):
         self.reference_generator.close()
@@ -625,7 +683,8 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
 def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, load=None, ode_solver=None, tau=None,
          constraints=None, dtype="float32", auto_reset=None, obs_layout="aos", physical_system_wrappers=(), reference_generator=None,
-         reward_function=None, state_filter=None, observed_states=None, flatten_observation=False, **kwargs):
+         reward_function=None, state_filter=None, observed_states=None, flatten_observation=False, max_episode_steps=None, episode_statistics=False,
+         **kwargs):
     """Build a batched env.  Component arguments follow the reference's env-arg convention (instance | dict | None).
     physical_system_wrappers: reference-style tuple (innermost first) of DeadTimeProcessor / DqToAbcActionProcessor holders
     (or the reference's own instances), which are folded into the kernel's action stage, and of CurrentSumProcessor / CosSinProcessor
@@ -639,8 +698,15 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     generator instances are read the same way, its SwitchedReferenceGenerator excepted) | ReplayReferenceGenerator;
     reward_function: None | 'default' | dict of `set_reward` keywords.  Naming either one selects the complete env
     (CompleteBatchedElectricMotorEnv), the other then takes the env id's default (`default_env_modules`); `seed` keys the default
-    generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env."""
+    generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env.
+    max_episode_steps: None | int >= 1 -- gymnasium's TimeLimit on the device: `step()` returns `truncated` [N], truncated envs restart in
+    front of the next step; episode_statistics: `env.episode_statistics()` hands out per-env episode length and return counters
+    (episodes.py).  Both off: nothing is built and nothing more is launched."""
+    from .episodes import check_max_episode_steps
     from .physical_system_wrappers import fold_wrappers
+
+    max_episode_steps = check_max_episode_steps(max_episode_steps)
+    episodes = dict(max_steps=max_episode_steps, statistics=bool(episode_statistics)) if max_episode_steps is not None or episode_statistics else None
 
     if state_filter is not None:
         raise NotImplementedError("state_filter is spelled observed_states=[names] on the accelerated path (a device-side column selection, "
@@ -694,7 +760,7 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
                            auto_reset=(n_envs > 1 and bool(limit_mask or squared_mask)) if auto_reset is None else bool(auto_reset))
     if reference_generator is None and reward_function is None:
         return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)), flux_action=flux_action,
-                                       state_noise=state_noise)
+                                       state_noise=state_noise, episodes=episodes)
     from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator
 
     modules = default_env_modules(env_id)
@@ -713,4 +779,4 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         raise ValueError("reward_function: 'default' or a dict of set_reward keywords")
     return CompleteBatchedElectricMotorEnv(system, reference_generator, reward_function, default_modules=modules,
                                            _defer_create=bool(kwargs.get("_defer_create", False)), observation=observation, flux_action=flux_action,
-                                           state_noise=state_noise)
+                                           state_noise=state_noise, episodes=episodes)

@@ -245,8 +245,10 @@ class ObservationPipeline:
     """Everything between a physical system's raw state rows and the state an env hands out, for BOTH env shells, and the one place
     where the order of the launches around the physics lives:
 
-        the masked reset of the envs the last NOISY row terminated, IN FRONT of the physics    (with a StateNoiseProcessor: `noise`)
+        the masked reset of the envs the last NOISY row terminated, IN FRONT of the physics    (with a StateNoiseProcessor: `noise`;
+                                                             with a time limit: of the envs in the episode stage's `reset_mask`)
         the noise on the raw rows, done and reward on the noisy row -> `noisy` [N, n_base]    (with a StateNoiseProcessor)
+        the episode stage on that step's done byte and reward -> truncated, ended, reset_mask  (with a time limit / episode statistics)
         the flux observer on the raw (noisy) rows -> `rows` [.., n_base + 2]      (when the chain holds a FluxObserver)
         the column program on those rows, reading the references when the observation is flat -> `state`   (unless it is the identity)
 
@@ -257,11 +259,20 @@ class ObservationPipeline:
     `noise`: None or the StateNoiseProcessor's spec (state_noise.py) with the constraint masks and the auto-reset the user asked for -- the
     system itself then has neither; `reward_config`: the reward the noise stage evaluates on the noisy row (the complete env's).  The
     system's own `done` buffer carries the NOISY done mask: the physics clears it, the noise stage behind it writes it, and the reset in
-    front of the next physics reads it."""
+    front of the next physics reads it.
+    `episode`: None or dict(max_steps=, statistics=) -- the episode stage (episodes.py) directly behind the launch that produces reward and
+    done; `episode_reward`: whether it reads a reward (the complete env's).  With the stage, `ended` = done | truncated replaces `done` as the
+    byte the generators restart on and the observer resets on (`restart_mask`), and with a time limit `reset_mask` is the mask of the reset
+    in front of the next physics: a truncated env is `env.reset()` in the reference."""
 
-    def __init__(self, physical_system, observation=None, n_ref=0, flux_action=None, defer_create=False, noise=None, reward_config=None):
+    AFTER_STEP = ("noise", "episode", "observer", "generators", "program")  # THE order of the launches behind a step's physics
+
+    def __init__(self, physical_system, observation=None, n_ref=0, flux_action=None, defer_create=False, noise=None, reward_config=None, episode=None,
+                 episode_reward=False):
         ps = self.physical_system = physical_system
-        self.stage = self.flux = self.flux_action = self.raw_scratch = self.ext_scratch = self.noise = None
+        self.stage = self.flux = self.flux_action = self.raw_scratch = self.ext_scratch = self.noise = self.episode = None
+        self.ended_scratch = self.finished_return_scratch = self.finished_length_scratch = None
+        self.truncated = False  # (what `step()` hands out in the fourth slot; with a time limit: the bool view of the stage's bytes)
         self.flux_only = self.has_program = False
         self.action_space = ps.action_space
         if noise is not None:
@@ -288,6 +299,14 @@ class ObservationPipeline:
                     raise NotImplementedError("random initial states together with the flux-oriented dq action processor are not on the accelerated path: "
                                               "the frame of the first action after a reset comes from the reset observation, which would not be a constant")
                 self.action_space = Box(-1, 1, shape=(self.flux.n_action,), dtype=np.float64)
+        if episode is not None:
+            from .episodes import EpisodeStage
+
+            # (under a StateNoiseProcessor the system is built without auto-reset: the stepping kernel restarts nothing)
+            in_kernel = bool(getattr(ps, "_auto_reset", False)) and self.noise is None
+            self.episode = EpisodeStage(episode.get("max_steps"), episode.get("statistics", False), in_kernel, has_reward=episode_reward)
+            if self.flux is not None and self.episode.max_steps:
+                self.flux.auto_reset = True  # (every env in `ended` restarts, by the kernel or by the masked reset: the observer follows)
         if defer_create:
             return
         import torch
@@ -307,8 +326,33 @@ class ObservationPipeline:
         if self.has_program:
             self.stage.create(ps._device, ps._dtype_name)
             self.state = new(ps.n_envs, self.stage.n_out)
+        if self.episode is not None:
+            self.episode.create(ps.n_envs, ps._device, ps._dtype_name)
+            if self.episode.max_steps:
+                self.truncated = self.episode.truncated.view(torch.bool)
+
+    @property
+    def restart_mask(self):
+        """[N] uint8: the envs that restart after this step -- `ended` with an episode stage, else the system's `done`."""
+        return self.physical_system._done if self.episode is None else self.episode.ended
+
+    def _reset_source(self):
+        """Whose mask the reset in front of the physics reads: None (no such launch), 'episode' or 'noise'."""
+        if self.episode is not None and self.episode.max_steps:
+            return "episode"
+        return "noise" if self.noise is not None and self.noise.auto_reset else None
+
+    def launch_order(self, generators=False):
+        """The names of a step's launches, in order, as `bind_before_step` / `bind_after_step` resolve them (needs no device)."""
+        present = dict(noise=self.noise is not None, episode=self.episode is not None, observer=self.flux is not None, generators=bool(generators),
+                       program=self.has_program)
+        return (["actions"] if self.flux_action else []) + (["reset"] if self._reset_source() else []) + ["physics"] + [n for n in self.AFTER_STEP if present[n]]
 
     def refuse_rollout(self):
+        if self.episode is not None and self.episode.max_steps:
+            from .episodes import ROLLOUT_REFUSAL as EPISODE_ROLLOUT_REFUSAL
+
+            raise NotImplementedError(EPISODE_ROLLOUT_REFUSAL)
         if self.noise is not None:
             from .state_noise import ROLLOUT_REFUSAL as NOISE_ROLLOUT_REFUSAL
 
@@ -318,12 +362,12 @@ class ObservationPipeline:
 
             raise NotImplementedError(ROLLOUT_REFUSAL)
 
-    def _scratch(self, name, shape):
+    def _scratch(self, name, shape, dtype=None):
         ps, buf = self.physical_system, getattr(self, name)
         if buf is None or tuple(buf.shape) != shape:
             import torch
 
-            buf = torch.empty(shape, dtype=ps._tdtype, device=ps._tdev)
+            buf = torch.empty(shape, dtype=dtype or ps._tdtype, device=ps._tdev)
             setattr(self, name, buf)
         return buf
 
@@ -337,15 +381,19 @@ class ObservationPipeline:
     # ------------------------------------------------------------------ the launches around the physics
     def bind_before_step(self, stream=None):
         """-> zero-argument launch() of what precedes a step's physics, or None: with a StateNoiseProcessor (and auto-reset) the masked
-        `gemx_reset` of the envs whose last noisy row terminated -- one asynchronous launch, no observation written, no host state."""
-        if self.noise is None or not self.noise.auto_reset:
+        `gemx_reset` of the envs whose last noisy row terminated -- one asynchronous launch, no observation written, no host state.  With
+        a time limit the mask is the episode stage's `reset_mask` instead (the truncated envs; behind a StateNoiseProcessor or with
+        auto_reset=False every ended env): still one launch."""
+        source = self._reset_source()
+        if source is None:
             return None
         import torch
 
         ps = self.physical_system
+        mask = self.episode.reset_mask if source == "episode" else ps._done
         stream = stream if stream is not None else torch.cuda.current_stream(ps._tdev)
-        args = (C.c_void_p(ps._done_ptr), None, C.c_void_p(stream.cuda_stream))
-        return _lib.bound_call(ps._L.gemx_reset, ps, args, (ps._done, stream))
+        args = (C.c_void_p(mask.data_ptr()), None, C.c_void_p(stream.cuda_stream))
+        return _lib.bound_call(ps._L.gemx_reset, ps, args, (mask, stream))
 
     def before_step(self):
         """`bind_before_step` on the current stream, run once."""
@@ -353,17 +401,23 @@ class ObservationPipeline:
         if launch is not None:
             launch()
 
-    def bind_after_step(self, refs=None, stream=None, generators=None, reward=None):
-        """-> zero-argument launch() of what follows a step's physics, or None when there is nothing to run: the noise stage on the system's
-        fresh rows (noisy rows, the done mask and -- `reward` [N] given -- the reward against `refs` as they stand, i.e. as the previous
-        observation showed them), the observer on the (noisy) rows and the done mask, then `generators` (the complete env's reference
-        step: a flat observation carries what it writes into `refs` [N, n_ref]), then the column program into `state`."""
+    def bind_after_step(self, refs=None, stream=None, generators=None, reward=None, returns=None):
+        """-> zero-argument launch() of what follows a step's physics, or None when there is nothing to run, in the order AFTER_STEP: the
+        noise stage on the system's fresh rows (noisy rows, the done mask and -- `reward` [N] given -- the reward against `refs` as they
+        stand, i.e. as the previous observation showed them), the episode stage on the done mask and `returns` (the [N] reward of this step,
+        whichever launch wrote it), the observer on the (noisy) rows and `restart_mask`, then `generators` (the complete env's reference
+        step, bound on `restart_mask`: a flat observation carries what it writes into `refs` [N, n_ref]), then the column program into `state`."""
         ps = self.physical_system
-        noise, src = None, ps._obs
+        bound, src = dict(generators=generators), ps._obs
         if self.noise is not None:
-            noise, src = self.noise.bind_step(ps._obs, refs, self.noisy, ps._done, reward, stream), self.noisy
-        observer = self.flux.bind_step(src, ps._done, self.rows, stream) if self.flux is not None else None
-        return _lib.sequence(noise, observer, generators, self.stage.bind_apply(self.rows, refs, self.state, stream) if self.has_program else None)
+            bound["noise"], src = self.noise.bind_step(ps._obs, refs, self.noisy, ps._done, reward, stream), self.noisy
+        if self.episode is not None:
+            bound["episode"] = self.episode.bind_step(ps._done, returns if self.episode.has_reward else None, stream=stream)
+        if self.flux is not None:
+            bound["observer"] = self.flux.bind_step(src, self.restart_mask, self.rows, stream)
+        if self.has_program:
+            bound["program"] = self.stage.bind_apply(self.rows, refs, self.state, stream)
+        return _lib.sequence(*(bound.get(name) for name in self.AFTER_STEP))
 
     def after_step(self, refs=None):
         """`bind_after_step` on the current stream, run once -> `state`."""
@@ -391,6 +445,34 @@ class ObservationPipeline:
             observer = self.flux.bind_rows(raw, done, src, stream)
         return _lib.sequence(observer, self.stage.bind_apply(src, refs, out, stream) if self.has_program else None, result=out)
 
+    def bind_episode_rows(self, done, reward=None, outputs=None, stream=None):
+        """-> (launch | None, outputs | None): the episode stage's pass over the stored `done` [K, N] and `reward` [K, N] rows of a K-step
+        rollout.  With a stage the pass always runs (the counters follow the rollout).  `outputs`: None / False (nothing handed out: `ended`
+        goes to scratch), True (ended, finished_return, finished_length in the pipeline's scratch, overwritten by the next rollout) or a
+        dict of the caller's tensors under those names (`ended` at least): what a bound launch takes, since it allocates nothing."""
+        if self.episode is None:
+            if outputs:
+                raise ValueError("episode_statistics= outputs need an env built with make(..., episode_statistics=True)")
+            return None, None
+        import torch
+
+        if done.dim() != 2:
+            raise NotImplementedError("last_only rollouts cannot carry the episode stage: its counters need every row")
+        shape = tuple(done.shape)
+        if isinstance(outputs, dict):
+            unknown = sorted(set(outputs) - {"ended", "finished_return", "finished_length"})
+            if unknown or outputs.get("ended") is None:
+                raise ValueError(f"episode_statistics: a dict of tensors under 'ended' (needed), 'finished_return', 'finished_length'; got {sorted(outputs)}")
+            outs = {k: v for k, v in outputs.items() if v is not None}
+        else:
+            outs = dict(ended=self._scratch("ended_scratch", shape, torch.uint8))
+            if outputs:
+                outs.update(finished_return=self._scratch("finished_return_scratch", shape, torch.float64),
+                            finished_length=self._scratch("finished_length_scratch", shape, torch.int32))
+        launch = self.episode.bind_rows(done, reward if self.episode.has_reward else None, outs["ended"], outs.get("finished_return"),
+                                        outs.get("finished_length"), stream)
+        return launch, (outs if outputs else None)
+
     def after_rollout(self, raw, done, refs=None, out=None):
         """`bind_after_rollout` on the current stream, run once -> the processed trajectory."""
         launch = self.bind_after_rollout(raw, done, refs, out)
@@ -401,6 +483,8 @@ class ObservationPipeline:
         and the column program -> `state`.  With a StateNoiseProcessor the reset rows are noised first (state_noise_processor.py:70-74: one
         stream position), and no env is left waiting for a restart."""
         src = self.physical_system._obs
+        if self.episode is not None:
+            self.episode.restart()
         if self.noise is not None:
             self.physical_system._done.zero_()
             self.noise.step(src, None, self.noisy, self._reset_done)
@@ -431,6 +515,8 @@ class ObservationPipeline:
     def close(self):
         if self.noise is not None:
             self.noise.close()
+        if self.episode is not None:
+            self.episode.close()
         if self.stage is not None:
             self.stage.close()
         if self.flux is not None:

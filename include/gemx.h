@@ -38,7 +38,8 @@ extern "C" {
                             * 8: gemx_refgen_step (new entry point: one fused generator step per launch); the generators' step index moved from the host
                             *    into device memory (gemx_refgen_rollout: same bits);
                             * 9: gemx_refgen_kinds_config / gemx_refgen_create_kinds / gemx_refgen_get_params (new struct and entry points only: a kind per
-                            *    generator column -- Wiener, Laplace, sinusoidal, step, triangular, sawtooth, constant; gemx_refgen_config handles: same bits) */
+                            *    generator column -- Wiener, Laplace, sinusoidal, step, triangular, sawtooth, constant; gemx_refgen_config handles: same bits);
+                            *    + gemx_episode_config / gemx_episode_* (new struct and entry points only: episode time limit and statistics) */
 #define GEMX_MAX_ODE 8  /* ODE state length incl. omega and the angle      */
 #define GEMX_MAX_OUT 24 /* system-state (observation) length               */
 #define GEMX_MODEL_ROWS 5
@@ -579,6 +580,46 @@ int gemx_noise_step(gemx_noise *h, const void *state_in_dev, const void *refs_de
 int gemx_noise_draws(gemx_noise *h, uint64_t step0, int32_t K, void *out_dev, void *stream);
 int gemx_noise_get_position(gemx_noise *h, uint64_t *position_host, void *stream);
 int gemx_noise_set_position(gemx_noise *h, uint64_t position, void *stream);
+
+/* Device-side EPISODE TIME LIMIT and EPISODE STATISTICS (new struct and entry points only, ABI number unchanged): gymnasium's TimeLimit and
+ * RecordEpisodeStatistics around an env, as one stage behind the launch that wrote a step's done byte and reward.  Per env the handle keeps
+ * length (i32), ret (f64: the return accumulates in double whatever R is), last_length, last_ret (the totals of the episode that ended
+ * last) and n_finished (u32).  One step of one env:
+ *     length += 1, ret += (double)reward
+ *     truncated = max_steps > 0 && length >= max_steps && !done      (terminating AND reaching the limit in one step: terminated)
+ *     ended = done | truncated;  where ended: last_length = length, last_ret = ret, n_finished += 1, length = 0, ret = 0
+ *   gemx_episode_step: ONE launch, one lane per env.  done_dev [N] uint8, reward_dev [N] R (given exactly when has_reward) ->
+ *     truncated_out_dev, ended_out_dev [N] uint8 and reset_mask_out_dev [N] uint8 (may be NULL) = truncated when auto_reset_in_kernel (the
+ *     stepping kernel restarts terminated envs itself) and ended when not: the mask of the gemx_reset in front of the caller's next
+ *     gemx_step.  Every lane reads its inputs before it writes: done_dev and reset_mask_out_dev MAY BE THE SAME BUFFER (no other overlap).
+ *   gemx_episode_rows: the same arithmetic over stored rows done_dev [K][N], reward_dev [K][N] in one pass (a lane scans its env's K rows in
+ *     order): afterwards the handle holds what K calls of gemx_episode_step leave, bit for bit.  ended_out_dev [K][N] uint8;
+ *     finished_return_out_dev [K][N] double and finished_length_out_dev [K][N] int32 (each may be NULL): the episode's totals at the row
+ *     where it ended, 0 elsewhere.  The outputs must not overlap the inputs.
+ *   gemx_episode_get_state / gemx_episode_set_state (both synchronise `stream`): all five fields as ONE device blob of
+ *     GEMX_EPISODE_STATE_BYTES * N bytes, 8-byte aligned: ret [N] double, last_ret [N] double, length [N] int32, last_length [N] int32,
+ *     n_finished [N] uint32, in that order.
+ * state_dev at create: NULL (the handle allocates the blob, zeroed) or the caller's own zeroed blob of that layout, which it keeps alive as
+ * long as the handle: the handle then works IN that memory (the Python holder hands out views of it, nothing is copied).
+ * A step or rows call allocates nothing, keeps no host state, issues no memset and never synchronises: it can be captured in a HIP graph.
+ * GEMX_ERR_ARG: a null pointer, struct_size, max_steps < 0, a flag not 0 | 1, n_envs < 1, K < 1, a misaligned tensor, reward_dev not
+ * matching has_reward. */
+#define GEMX_EPISODE_STATE_BYTES 28
+typedef struct gemx_episode_config {
+    int32_t struct_size;          /* = sizeof(gemx_episode_config) */
+    int32_t max_steps;            /* the time limit in control steps; 0: none (statistics only) */
+    int32_t auto_reset_in_kernel; /* 1: the stepping kernel restarts terminated envs itself -> reset_mask = truncated; 0: reset_mask = ended */
+    int32_t has_reward;           /* 1: the calls read a reward; 0: ret stays 0 */
+} gemx_episode_config;
+typedef struct gemx_episode gemx_episode;
+int gemx_episode_create(const gemx_episode_config *cfg, int64_t n_envs, int dtype, int device, void *state_dev, gemx_episode **out);
+int gemx_episode_destroy(gemx_episode *h);
+int gemx_episode_step(gemx_episode *h, const uint8_t *done_dev, const void *reward_dev, uint8_t *truncated_out_dev, uint8_t *ended_out_dev,
+                      uint8_t *reset_mask_out_dev, void *stream);
+int gemx_episode_rows(gemx_episode *h, const uint8_t *done_dev, const void *reward_dev, int32_t K, uint8_t *ended_out_dev,
+                      double *finished_return_out_dev, int32_t *finished_length_out_dev, void *stream);
+int gemx_episode_get_state(gemx_episode *h, void *out_dev, void *stream);
+int gemx_episode_set_state(gemx_episode *h, const void *in_dev, void *stream);
 
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
