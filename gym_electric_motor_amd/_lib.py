@@ -120,6 +120,18 @@ class GemxRefgenSwitchedConfig(C.Structure):
     ]
 
 
+REFGEN_BLOB_HEADER_BYTES = 64  # GEMX_REFGEN_BLOB_HEADER_BYTES
+# bytes per (column, env) lane of the arrays a generator handle owns, in the blob's order (include/gemx.h, gemx_refgen_get_blob):
+# every handle | + a gemx_refgen_create_kinds handle | + a handle with a switched column
+REFGEN_LANE_BYTES = dict(all=(8, 8, 4, 4, 4, 8), kinds=(4, 48), switched=(4, 4, 4, 4))
+
+
+def refgen_state_bytes(n_envs, n_ref, kinds=False, switched=False):
+    """`gemx_refgen_state_bytes` restated: the header, then one section per array, each padded to a multiple of 8 bytes."""
+    rows = REFGEN_LANE_BYTES["all"] + (REFGEN_LANE_BYTES["kinds"] if kinds or switched else ()) + (REFGEN_LANE_BYTES["switched"] if switched else ())
+    return REFGEN_BLOB_HEADER_BYTES + sum((int(n_envs) * int(n_ref) * b + 7) // 8 * 8 for b in rows)
+
+
 OBS_MAX_POST = 32
 OBS_COPY, OBS_SUM, OBS_COSPI, OBS_SINPI = range(4)  # GEMX_OBS_*
 
@@ -185,6 +197,7 @@ EXPORTS = (
     "gemx_obsproc_create", "gemx_obsproc_apply", "gemx_obsproc_destroy",
     "gemx_refgen_rollout_shell", "gemx_reward_rows",
     "gemx_refgen_create_switched", "gemx_refgen_get_switch_state",
+    "gemx_refgen_state_bytes", "gemx_refgen_get_blob", "gemx_refgen_set_blob",
     "gemx_fluxobs_create", "gemx_fluxobs_destroy", "gemx_fluxobs_reset", "gemx_fluxobs_step", "gemx_fluxobs_rows", "gemx_fluxobs_actions",
     "gemx_fluxobs_get_state", "gemx_fluxobs_set_state",
     "gemx_noise_create", "gemx_noise_destroy", "gemx_noise_step", "gemx_noise_draws", "gemx_noise_get_position", "gemx_noise_set_position",
@@ -239,6 +252,10 @@ def load():
     L.gemx_refgen_get_params.argtypes = [vp, vp, vp, vp]
     L.gemx_refgen_create_switched.argtypes = [C.POINTER(GemxRefgenSwitchedConfig), i64, C.c_int, C.c_int, C.POINTER(vp)]
     L.gemx_refgen_get_switch_state.argtypes = [vp, vp, vp]
+    L.gemx_refgen_state_bytes.argtypes = [vp]
+    L.gemx_refgen_state_bytes.restype = i64
+    L.gemx_refgen_get_blob.argtypes = [vp, vp, vp]
+    L.gemx_refgen_set_blob.argtypes = [vp, vp, vp]
     L.gemx_refgen_destroy.argtypes = [vp]
     L.gemx_refgen_reset.argtypes = [vp, vp, vp]
     L.gemx_refgen_rollout.argtypes = [vp, vp, i32, vp, vp]

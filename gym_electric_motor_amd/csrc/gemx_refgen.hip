@@ -28,6 +28,18 @@
 // launch what they launched before.
 #include "gemx_support.hpp"
 
+// the head of a checkpoint blob (gemx_refgen_get_blob): who may take the arrays behind it.  64 bytes; kept in the handle, so that the
+// asynchronous copy into a blob reads memory that outlives the call
+struct RefgenBlobHeader {
+    uint32_t magic, owners;  // owners: the OWN_* bits of the arrays that follow (plain / kinds / switched handle)
+    int64_t n_envs;
+    int32_t n_ref, reserved;
+    int64_t env_base, bytes;     // bytes: of the whole blob, gemx_refgen_state_bytes
+    int32_t column[GEMX_MAX_REF];  // per column: its kind | the number of its alternatives << 8 (a plain handle: Wiener columns)
+    int64_t pad;
+};
+static_assert(sizeof(RefgenBlobHeader) == GEMX_REFGEN_BLOB_HEADER_BYTES, "the blob header is 64 bytes");
+
 struct gemx_refgen {
     gemx_refgen_config cfg;
     int64_t n;
@@ -51,6 +63,7 @@ struct gemx_refgen {
     int32_t *alt = nullptr, *sk = nullptr, *slen = nullptr;
     uint32_t *n_super = nullptr;
     void *sdev = nullptr;
+    RefgenBlobHeader blob_head;  // written by every gemx_refgen_get_blob, read by its copy
 };
 
 namespace {
@@ -871,6 +884,89 @@ int gemx_refgen_get_switch_state(gemx_refgen *r, int32_t *alt_sk_slen_nsuper_out
     hipStream_t st = (hipStream_t)stream;
     const void *src[4] = {r->alt, r->sk, r->slen, r->n_super};
     for (int i = 0; i < 4; ++i) GEMX_HIP_TRY(hipMemcpyAsync(alt_sk_slen_nsuper_out_dev + i * m, src[i], m * 4, hipMemcpyDeviceToDevice, st));
+    return GEMX_OK;
+}
+
+// ---- checkpoint blob (include/gemx.h): the header, then EVERY array of refgen_lane_arrays the handle owns, in the table's order, each
+// section padded to 8 bytes.  The three functions walk the table: an array added to it is carried without a change here.
+static int refgen_owners(const gemx_refgen *r) { return OWN_ALL | (r->has_kinds ? OWN_KINDS : 0) | (r->switched ? OWN_SWITCHED : 0); }
+static size_t refgen_section_bytes(const gemx_refgen *r, const LaneArrayRow &a) { return ((size_t)r->n * r->cfg.n_ref * a.bytes + 7) & ~(size_t)7; }
+static RefgenBlobHeader refgen_blob_header(gemx_refgen *r) {
+    RefgenBlobHeader h;
+    memset(&h, 0, sizeof(h));
+    h.magic = 0x47525847u;  // "GXRG"
+    h.owners = (uint32_t)refgen_owners(r);
+    h.n_envs = r->n; h.n_ref = r->cfg.n_ref; h.env_base = r->cfg.env_base;
+    h.bytes = gemx_refgen_state_bytes(r);
+    for (int g = 0; g < r->cfg.n_ref; ++g) {
+        h.column[g] = r->has_kinds ? r->kcfg.kind[g] : GEMX_REF_WIENER;
+        if (r->switched) h.column[g] |= ((const RefgenSwitchedDev *)r->sdev)->n_alt[g] << 8;
+    }
+    return h;
+}
+
+int64_t gemx_refgen_state_bytes(gemx_refgen *r) {
+    if (!r) return 0;
+    size_t total = sizeof(RefgenBlobHeader);
+    const int owners = refgen_owners(r);
+    refgen_lane_arrays(r, [&](const LaneArrayRow &a) {
+        if (a.owner & owners) total += refgen_section_bytes(r, a);
+    });
+    return (int64_t)total;
+}
+
+int gemx_refgen_get_blob(gemx_refgen *r, void *out_dev, void *stream) {
+    if (!r || !out_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    gemx::DeviceGuard guard(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    // (equal states give equal blobs: the sections' padding is zeroed)
+    GEMX_HIP_TRY(hipMemsetAsync(out_dev, 0, (size_t)gemx_refgen_state_bytes(r), st));
+    r->blob_head = refgen_blob_header(r);  // (the same words on every call: a copy still in flight reads what this writes)
+    GEMX_HIP_TRY(hipMemcpyAsync(out_dev, &r->blob_head, sizeof(RefgenBlobHeader), hipMemcpyHostToDevice, st));
+    const int owners = refgen_owners(r);
+    const size_t m = (size_t)r->n * r->cfg.n_ref;
+    size_t at = sizeof(RefgenBlobHeader);
+    hipError_t err = hipSuccess;
+    refgen_lane_arrays(r, [&](const LaneArrayRow &a) {
+        if (!(a.owner & owners)) return;
+        if (err == hipSuccess) err = hipMemcpyAsync((char *)out_dev + at, *a.p, m * a.bytes, hipMemcpyDeviceToDevice, st);
+        at += refgen_section_bytes(r, a);
+    });
+    GEMX_HIP_TRY(err);
+    return GEMX_OK;
+}
+
+int gemx_refgen_set_blob(gemx_refgen *r, const void *in_dev, void *stream) {
+    if (!r || !in_dev) return gemx::fail(GEMX_ERR_ARG, "null argument");
+    gemx::DeviceGuard guard(r->device);
+    hipStream_t st = (hipStream_t)stream;
+    // the header alone comes to the host first (synchronises `stream`); nothing is enqueued before it has been checked
+    RefgenBlobHeader got;
+    GEMX_HIP_TRY(hipMemcpyAsync(&got, in_dev, sizeof(got), hipMemcpyDeviceToHost, st));
+    GEMX_HIP_TRY(hipStreamSynchronize(st));
+    const RefgenBlobHeader want = refgen_blob_header(r);
+    if (got.magic != want.magic) return gemx::fail(GEMX_ERR_ARG, "not a reference generator blob (magic %08x)", got.magic);
+    if (got.n_envs != want.n_envs) return gemx::fail(GEMX_ERR_ARG, "the reference generator blob is for n_envs = %lld, this handle has %lld", (long long)got.n_envs, (long long)want.n_envs);
+    if (got.n_ref != want.n_ref) return gemx::fail(GEMX_ERR_ARG, "the reference generator blob has %d reference columns, this handle has %d", got.n_ref, want.n_ref);
+    if (got.owners != want.owners)
+        return gemx::fail(GEMX_ERR_ARG, "the reference generator blob is of another generator kind (arrays %u: 1 Wiener, 3 kinds, 7 switched; this handle: %u)", got.owners, want.owners);
+    for (int g = 0; g < want.n_ref; ++g)
+        if (got.column[g] != want.column[g])
+            return gemx::fail(GEMX_ERR_ARG, "the reference generator blob's column %d is of another generator kind (%d with %d alternatives; this handle: %d with %d)", g,
+                              got.column[g] & 255, got.column[g] >> 8, want.column[g] & 255, want.column[g] >> 8);
+    if (got.env_base != want.env_base)
+        return gemx::fail(GEMX_ERR_ARG, "the reference generator blob belongs to the shard at env_base = %lld, this handle's is %lld", (long long)got.env_base, (long long)want.env_base);
+    if (got.bytes != want.bytes) return gemx::fail(GEMX_ERR_ARG, "the reference generator blob has %lld bytes, this handle's has %lld", (long long)got.bytes, (long long)want.bytes);
+    const int owners = refgen_owners(r);
+    const size_t m = (size_t)r->n * r->cfg.n_ref;
+    size_t at = sizeof(RefgenBlobHeader);
+    hipError_t err = hipSuccess;
+    refgen_lane_arrays(r, [&](const LaneArrayRow &a) {
+        if (!(a.owner & owners)) return;
+        if (err == hipSuccess) err = hipMemcpyAsync(*a.p, (const char *)in_dev + at, m * a.bytes, hipMemcpyDeviceToDevice, st);
+        at += refgen_section_bytes(r, a);
+    });
+    GEMX_HIP_TRY(err);
     return GEMX_OK;
 }
 

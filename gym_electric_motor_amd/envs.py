@@ -307,8 +307,20 @@ class BatchedElectricMotorEnv:
             ck["episodes"] = dict(state=self.episodes.get_state(), reset_mask=self.episodes.reset_mask.clone())
         return ck
 
+    def _checkpoint_keys(self):
+        """The entries `set_checkpoint` reads beside the physical system's, by the stages this env has."""
+        return [k for k, part in (("flux_observer", self.flux), ("state_noise", self.state_noise), ("episodes", self.episodes)) if part is not None]
+
+    def _check_checkpoint(self, ckpt):
+        """What is checked before anything is restored: every entry this env reads is there."""
+        missing = [k for k in ["state", "switch_state", "aux", "k"] + self._checkpoint_keys() if k not in ckpt]
+        if missing:
+            raise ValueError(f"the checkpoint lacks {missing}: it was taken from an env without these stages, or is not a get_checkpoint() result")
+
     def set_checkpoint(self, ckpt):
-        """Restore `get_checkpoint()` of an env of the same configuration: the next `step()` continues bit for bit."""
+        """Restore `get_checkpoint()` of an env of the same configuration: the next `step()` continues bit for bit.  An entry this env needs
+        and the checkpoint lacks raises before anything is restored."""
+        self._check_checkpoint(ckpt)
         self.physical_system.set_checkpoint(ckpt)
         if self.flux is not None:
             self.flux.set_state(ckpt["flux_observer"])
@@ -462,6 +474,30 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         ps._reward_buf = self._reward  # (`physical_system.reward` shows the same buffer)
         self._refs = gen.references
         self._obs = self.pipeline.state if flat else (self.pipeline.state, self._refs)
+
+    def get_checkpoint(self):
+        """The physics-only env's checkpoint plus `reference_generator`: the generators' whole device state -- one opaque blob: values,
+        sub-episode and super-episode counters, the indices of their random streams, the waveform parameters -- and the references shown
+        last, which the reward of the next step reads (`reference_generator.get_state()`; a ReplayReferenceGenerator: its host row index)."""
+        ck = super().get_checkpoint()
+        ck["reference_generator"] = self.reference_generator.get_state()
+        return ck
+
+    def set_checkpoint(self, ckpt):
+        """Restore `get_checkpoint()` of a complete env of the same configuration (n_envs, shard, generator kinds and columns, stages): the
+        next `step()`, `rollout_complete()` or replay of a captured `bind_step` continues the run bit for bit -- state, references, reward,
+        terminated, truncated, statistics.  Everything is copied INTO the buffers the env owns, so launchers bound before the restore stay
+        valid.  Checked before anything is enqueued: a checkpoint without the `reference_generator` entry (a physics-only env's), of
+        another n_envs, generator kind, column count or shard, or with a truncated blob raises ValueError and leaves the env as it was."""
+        self._check_checkpoint(ckpt)
+        if "reference_generator" not in ckpt:
+            raise ValueError("the checkpoint has no 'reference_generator' entry: it was taken from a physics-only env (or by a version that did not "
+                             "carry the generators); a complete env cannot continue from it")
+        gen = self.reference_generator
+        gen.check_state(ckpt["reference_generator"])
+        self.physical_system.check_checkpoint(ckpt)
+        gen.set_state(ckpt["reference_generator"])  # (the blob's header is checked here, before its first copy is enqueued)
+        super().set_checkpoint(ckpt)
 
     def reset(self, seed=None, options=None):
         """All envs to the initial state, all generators restarted and advanced once (core.py:312-313, 485-505).

@@ -987,14 +987,22 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         _lib.check(self._L.gemx_get_aux_state(self._handle, C.c_void_p(aux.data_ptr()), self._stream()))
         return {"state": self.get_state(), "switch_state": self.get_switch_state(), "aux": aux, "k": int(self._k)}
 
-    def set_checkpoint(self, ckpt):
-        """Restore `get_checkpoint()` of a system of the SAME configuration (n_envs, dtype, converter, supply, wrappers, initialisers;
-        checked by the library): the next simulate() / rollout() continues bit for bit."""
+    def check_checkpoint(self, ckpt):
+        """The size checks of `set_checkpoint`, which restore nothing -> the aux blob on this system's device."""
         torch = _torch()
         aux = torch.as_tensor(ckpt["aux"]).to(device=self._tdev, dtype=torch.uint8).contiguous()
         if aux.numel() != int(self._L.gemx_aux_state_bytes(self._handle)):
             raise ValueError(f"checkpoint aux blob has {aux.numel()} bytes, this system needs {int(self._L.gemx_aux_state_bytes(self._handle))}: "
                              "it was taken from a system of another configuration")
+        if torch.as_tensor(ckpt["state"]).numel() != self._n_ode * self._n_envs:
+            raise ValueError(f"checkpoint state has shape {tuple(torch.as_tensor(ckpt['state']).shape)}, this system's is {(self._n_ode, self._n_envs)}: "
+                             "it was taken from a system of another n_envs or motor")
+        return aux
+
+    def set_checkpoint(self, ckpt):
+        """Restore `get_checkpoint()` of a system of the SAME configuration (n_envs, dtype, converter, supply, wrappers, initialisers;
+        checked by the library): the next simulate() / rollout() continues bit for bit."""
+        aux = self.check_checkpoint(ckpt)
         self.set_state(ckpt["state"])
         self.set_switch_state(ckpt["switch_state"])
         _lib.check(self._L.gemx_set_aux_state(self._handle, C.c_void_p(aux.data_ptr()), self._stream()))

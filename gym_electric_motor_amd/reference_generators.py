@@ -180,6 +180,48 @@ class _DeviceGenerators:
         d = done if done.dim() == 1 else done.any(dim=0)
         self.reset(mask=d.to(torch.uint8))
 
+    # ------------------------------------------------------------------ checkpoint
+    def state_bytes(self):
+        """Bytes of the handle's checkpoint blob (`gemx_refgen_state_bytes`)."""
+        return int(self._L.gemx_refgen_state_bytes(self._handle))
+
+    def get_state(self):
+        """-> dict(blob, references) of new device tensors, for a checkpoint: the handle's whole per-(column, env) state as one opaque uint8
+        blob (`gemx_refgen_get_blob`: values, sigmas, sub-episode counters, the stream indices, the waveform parameters, the super-episode
+        state) and a clone of `references` -- the values shown last, which the reward of the next step reads."""
+        import torch
+
+        blob = torch.empty(self.state_bytes(), dtype=torch.uint8, device=self._tdev)
+        _lib.check(self._L.gemx_refgen_get_blob(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
+        return dict(blob=blob, references=self._refs.clone())
+
+    def check_state(self, state):
+        """What can be checked of `get_state()`'s dict without touching the device -> (blob, references), on this generator's device.
+        ValueError names the mismatch."""
+        import torch
+
+        if not isinstance(state, dict) or "blob" not in state or "references" not in state:
+            raise ValueError("a reference generator's checkpoint is the dict(blob=, references=) of its get_state()")
+        blob, refs = state["blob"], state["references"]
+        if not (torch.is_tensor(blob) and blob.dtype == torch.uint8 and blob.dim() == 1):
+            raise ValueError("reference generator checkpoint: blob must be a one-dimensional uint8 tensor")
+        if blob.numel() != self.state_bytes():
+            raise ValueError(f"reference generator checkpoint: the blob has {blob.numel()} bytes, this generator's has {self.state_bytes()}: it is "
+                             "truncated, or was taken from a generator of another configuration (n_envs, columns, kinds)")
+        if not (torch.is_tensor(refs) and tuple(refs.shape) == tuple(self._refs.shape) and refs.dtype == self._tdtype):
+            raise ValueError(f"reference generator checkpoint: references must be a {self._tdtype} tensor of shape {tuple(self._refs.shape)}, not "
+                             f"{getattr(refs, 'dtype', type(refs).__name__)} {tuple(getattr(refs, 'shape', ()))}")
+        return blob.to(self._tdev).contiguous(), refs.to(self._tdev)
+
+    def set_state(self, state):
+        """Restore `get_state()` of a generator of the same configuration: `step`, `rollout` and `rollout_shell` continue bit for bit.
+        Checked before anything is enqueued (sizes and types here, the blob's header -- n_envs, columns, kinds, shard -- by
+        `gemx_refgen_set_blob`, which synchronises the stream for it); ValueError names the mismatch and the generator is untouched.
+        The references are copied INTO the buffer this generator owns: bound launchers and captured graphs keep pointing at it."""
+        blob, refs = self.check_state(state)
+        _lib.check(self._L.gemx_refgen_set_blob(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
+        self._refs.copy_(refs)
+
     def close(self):
         if self._handle is not None:
             self._L.gemx_refgen_destroy(self._handle)
@@ -635,6 +677,29 @@ class ReplayReferenceGenerator:
     def bind_rollout_shell(self, done, out, stream=None):
         raise RuntimeError("a ReplayReferenceGenerator cannot be captured in a graph: its row index lives on the host, so a bound rollout "
                            "would replay the rows of its first launch")
+
+    def get_state(self):
+        """-> dict(row, references), for a checkpoint: the host row index and a clone of the references shown last."""
+        return dict(row=int(self._k), references=self._refs.clone())
+
+    def check_state(self, state):
+        """`get_state()`'s dict, checked without touching the device -> (row, references); ValueError names the mismatch."""
+        import torch
+
+        if not isinstance(state, dict) or "row" not in state or "references" not in state:
+            raise ValueError("a ReplayReferenceGenerator's checkpoint is the dict(row=, references=) of its get_state()")
+        row, refs = state["row"], state["references"]
+        if isinstance(row, bool) or not isinstance(row, (int, np.integer)) or not 0 <= int(row) <= int(self._rows.shape[0]):
+            raise ValueError(f"ReplayReferenceGenerator checkpoint: row must be an index into the profile's {int(self._rows.shape[0])} rows, not {row!r}")
+        if not (torch.is_tensor(refs) and tuple(refs.shape) == tuple(self._refs.shape) and refs.dtype == self._refs.dtype):
+            raise ValueError(f"ReplayReferenceGenerator checkpoint: references must be a {self._refs.dtype} tensor of shape {tuple(self._refs.shape)}")
+        return int(row), refs
+
+    def set_state(self, state):
+        """Restore `get_state()`: the next `step` shows the row the checkpointed generator would have shown."""
+        row, refs = self.check_state(state)
+        self._k = row
+        self._refs.copy_(refs)
 
     def close(self):
         pass

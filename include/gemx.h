@@ -446,6 +446,26 @@ int gemx_refgen_create_switched(const gemx_refgen_switched_config *cfg, int64_t 
  * gemx_refgen_get_params reports the kind of the lane's CURRENT alternative (index and length of a CONST one: -1). */
 int gemx_refgen_get_switch_state(gemx_refgen *r, int32_t *alt_sk_slen_nsuper_out_dev, void *stream);
 
+/* Checkpoint of a handle's whole device state (new entry points only, ABI number unchanged): one opaque blob of
+ * gemx_refgen_state_bytes(r) bytes in device memory -- a header of GEMX_REFGEN_BLOB_HEADER_BYTES, then EVERY per-(column, env) array the
+ * handle owns, in this order, each a section of n_envs * n_ref * (bytes per lane) bytes padded to a multiple of 8:
+ *   every handle:                          value 8, sigma 8, left 4, n_sub 4, n_reset 4, t 8
+ *   + gemx_refgen_create_kinds handles:    len 4, par 48
+ *   + handles with a switched column:      alt 4, sk 4, slen 4, n_super 4
+ * (value, sigma, steps left, sub-episodes and resets drawn so far, index of the step draws; sub-episode length, the six waveform
+ * parameters; alternative, super-episode step counter and length, super-episodes drawn so far.)  The header names n_envs, n_ref, which of
+ * the three groups follow, the columns' kinds and env_base.  A handle of the same configuration that takes the blob continues the
+ * streams bit for bit; the references shown last are the caller's tensor and travel beside it.
+ *   gemx_refgen_get_blob: asynchronous copies on `stream`; equal states give equal blobs.
+ *   gemx_refgen_set_blob: copies the header alone to the host (synchronises `stream`) and checks it BEFORE anything is enqueued:
+ *     GEMX_ERR_ARG, with the mismatch named in gemx_last_error, for a blob of another n_envs, n_ref, handle or column kind, or shard
+ *     (env_base), and the handle is untouched; then asynchronous copies on `stream`.  The caller guarantees the blob's size.
+ * For the same build and the same configuration, as the blob of gemx_get_aux_state is. */
+#define GEMX_REFGEN_BLOB_HEADER_BYTES 64
+int64_t gemx_refgen_state_bytes(gemx_refgen *r);
+int gemx_refgen_get_blob(gemx_refgen *r, void *out_dev, void *stream);
+int gemx_refgen_set_blob(gemx_refgen *r, const void *in_dev, void *stream);
+
 /* Device-side OBSERVATION STAGE: the observation-side physical-system wrappers of the reference (CurrentSumProcessor,
  * physical_system_wrappers/current_sum_processor.py:40-57; CosSinProcessor, cos_sin_processor.py:52-66), the env shell's state_filter
  * (core.py:273-276, 317, 366) and the flat (state || reference) vector FlattenObservation makes of the shell's Tuple, in ONE pass over the

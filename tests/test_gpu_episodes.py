@@ -294,14 +294,22 @@ def test_graph_replay(dtype):
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_checkpoint(dtype):
-    """get_checkpoint() after step 4 into a fresh env: steps 5-7 and the counters are those of the uninterrupted run.  (Constant references:
-    the env's checkpoint does not carry the generators' random state.)"""
+    """get_checkpoint() after step 4 into a fresh env: steps 5-7 and the counters are those of the uninterrupted run -- with constant
+    references, and with the env id's default Wiener references, whose streams the checkpoint carries
+    (tests/test_gpu_checkpoint_complete.py: every generator kind)."""
+    import gym_electric_motor_amd as ga
+
+    _checkpoint(dtype, lambda: [ga.ConstReferenceGenerator("i_sd", 0.1), ga.ConstReferenceGenerator("i_sq", -0.2)])
+    _checkpoint(dtype, lambda: "default")
+
+
+def _checkpoint(dtype, generator):
     import torch
 
     import gym_electric_motor_amd as ga
 
-    mk = lambda: ga.make("Cont-CC-PMSM-v0", n_envs=N_ENV, dtype=dtype, max_episode_steps=M_ENV, episode_statistics=True,  # noqa: E731
-                         reference_generator=[ga.ConstReferenceGenerator("i_sd", 0.1), ga.ConstReferenceGenerator("i_sq", -0.2)])
+    mk = lambda: ga.make("Cont-CC-PMSM-v0", n_envs=N_ENV, dtype=dtype, max_episode_steps=M_ENV, episode_statistics=True, seed=23,  # noqa: E731
+                         reference_generator=generator())
     first, second = mk(), mk()
     a = _actions(first, N_ENV, seed=17)
     _run(first, a, steps=4)
@@ -326,6 +334,8 @@ def test_checkpoint(dtype):
         for name in FIELDS:
             assert torch.equal(_bits(env.episode_statistics()[name]), _bits(stats7[name])), name
     assert float(stats7["last_ret"].abs().sum()) > 0
+    if generator() == "default":  # the comparison saw references that move: the walk's steps, and the restarts after steps 3 and 6
+        assert not torch.equal(got[0][1], got[1][1]) and not torch.equal(got[-1][1], got[-2][1])
     for e in (first, second, third):
         e.close()
 

@@ -411,6 +411,40 @@ def test_checkpoint_continues_bit_for_bit():
     other.close()
 
 
+def test_complete_env_checkpoint_continues_bit_for_bit():
+    """The twin of the test above with the env id's Wiener generators and the reward: the checkpoint carries them beside the observer."""
+    import torch
+
+    import gym_electric_motor_amd as ga
+
+    n = 65
+    mk = lambda: ga.make("Cont-CC-SCIM-v0", n_envs=n, reference_generator="default", seed=6,  # noqa: E731
+                         physical_system_wrappers=(ga.FluxObserver(), ga.FluxOrientedDqToAbcActionProcessor("SCIM")))
+    a = torch.as_tensor(np.random.default_rng(4).uniform(-1, 1, (30, n, 2)), dtype=torch.float32, device="cuda")
+    env = mk()
+    env.reset()
+    for k in range(15):
+        env.step(a[k])
+    ck = env.get_checkpoint()
+    assert tuple(ck["flux_observer"].shape) == (4, n) and set(ck["reference_generator"]) == {"blob", "references"}
+    want = []
+    for k in range(15, 30):
+        (s, r), w, dn, _, _ = env.step(a[k])
+        want.append((s.clone(), r.clone(), w.clone(), dn.clone()))
+    other = mk()
+    other.reset()
+    for k in range(3):  # (nothing of the other env is at its create-time zero)
+        other.step(a[29 - k])
+    other.set_checkpoint(ck)
+    for k, row in zip(range(15, 30), want):
+        (s, r), w, dn, _, _ = other.step(a[k])
+        for name, x, y in zip(("state", "refs", "reward", "terminated"), (s, r, w, dn), row):
+            assert torch.equal(x, y), (name, k)
+    assert not torch.equal(want[0][1], want[-1][1]) and not torch.equal(want[0][2], want[-1][2])  # (references and rewards move)
+    env.close()
+    other.close()
+
+
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
 def test_stage_composition_over_the_extended_row(dtype):
     """CosSinProcessor('psi_angle') + observed_states + flatten over the SCIM's 16-column extended row against the host program.  (The

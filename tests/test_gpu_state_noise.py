@@ -262,6 +262,26 @@ def test_graph_replay_and_checkpoint(dtype):
         assert torch.equal(s2, s) and torch.equal(second.physical_system.done, d), k
     assert sum(int(d.sum()) for _, d in tail) > 0
     first.close(), second.close()
+    # the complete env's checkpoint carries the Wiener generators and the references the noisy reward reads, too
+    first, second = (ga.make("Cont-CC-PMSM-v0", reference_generator="default", **kw) for _ in range(2))
+    first.reset()
+    for _ in range(7):
+        first.step(a)
+    ck = first.get_checkpoint()
+    assert ck["state_noise"]["position"] == 8 and set(ck["reference_generator"]) == {"blob", "references"}
+    tail = []
+    for _ in range(9):
+        (s, r), w, d, _, _ = first.step(a)
+        tail.append((s.clone(), r.clone(), w.clone(), d.clone()))
+    second.reset()
+    second.step(-a)  # (nothing of the second env is at its create-time zero)
+    second.set_checkpoint(ck)
+    for k, want in enumerate(tail):
+        (s, r), w, d, _, _ = second.step(a)
+        for name, x, y in zip(("state", "refs", "reward", "terminated"), (s, r, w, d), want):
+            assert torch.equal(x, y), (name, k)
+    assert sum(int(t[3].sum()) for t in tail) > 0 and not torch.equal(tail[0][1], tail[-1][1])
+    first.close(), second.close()
 
 
 @pytest.mark.parametrize("dtype", ["float32", "float64"])
