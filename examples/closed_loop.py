@@ -5,6 +5,7 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
     python examples/closed_loop.py [--envs 16384] [--steps 2000]                        # generator and reward wired by hand
     python examples/closed_loop.py --complete [--bind | --graph 64]                     # the same loop through the complete env
     python examples/closed_loop.py --complete --graph 64 --reference step               # ... on step (sinusoidal, ...) profiles
+    python examples/closed_loop.py --complete --graph 64 --reference profile            # ... on a given two-column cycle, periodic, per env
     python examples/closed_loop.py --complete --rollout 500                             # open loop: (state, reference, reward, done) datasets
     python examples/closed_loop.py --complete --graph 64 --time-limit 500               # episodes of 500 steps, counted on the device
 
@@ -29,7 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 # --reference KIND -> the holder class of the reference's generator of that kind ('wiener': the env id's default generators)
 REFERENCES = dict(wiener=None, sinusoidal="SinusoidalReferenceGenerator", step="StepReferenceGenerator", triangular="TriangularReferenceGenerator",
-                  sawtooth="SawtoothReferenceGenerator", laplace="LaplaceProcessReferenceGenerator", constant="ConstReferenceGenerator")
+                  sawtooth="SawtoothReferenceGenerator", laplace="LaplaceProcessReferenceGenerator", constant="ConstReferenceGenerator",
+                  profile="ProfileReferenceGenerator")
 
 
 def main():
@@ -99,7 +101,13 @@ def complete(args):
 
     n = args.envs
     generator = "default"  # default generators (i_sd, i_sq) and reward weights (0.5, 0.5) of the env id
-    if args.reference != "wiener":  # one holder per referenced state; the columns of one device handle
+    if args.reference == "profile":  # a given trajectory: a synthetic two-column cycle of 500 rows sampled at 2 tau, repeated (end="wrap")
+        import numpy as np
+
+        t = np.arange(500) / 500.0
+        cycle = np.stack([-0.2 + 0.1 * np.sin(2 * np.pi * t), 0.3 * np.sign(np.sin(6 * np.pi * t))], axis=1)  # columns: i_sd, i_sq
+        generator = ga.ProfileReferenceGenerator(cycle, reference_states=("i_sd", "i_sq"), profile_tau=2e-4, end="wrap", start="random", seed=1)
+    elif args.reference != "wiener":  # one holder per referenced state; the columns of one device handle
         holder = getattr(ga, REFERENCES[args.reference])
         kw = dict() if args.reference in ("laplace", "constant") else dict(frequency_range=(5, 50), amplitude_range=(0.1, 0.4))
         generator = [holder(reference_state=s, **kw) for s in ("i_sd", "i_sq")]

@@ -31,6 +31,7 @@ from .components import (  # noqa: F401
 )
 from .envs import BatchedElectricMotorEnv, CompleteBatchedElectricMotorEnv, default_components, default_env_modules, default_ode_solver, default_physical_system_wrappers, make  # noqa: F401
 from .reference_generators import BatchedWienerProcessReferenceGenerator, ReplayReferenceGenerator  # noqa: F401
+from .reference_generators import ProfileReferenceGenerator, ProfileReferences  # noqa: F401
 from .reference_generators import (  # noqa: F401
     BatchedMultipleReferenceGenerator, ConstReferenceGenerator, LaplaceProcessReferenceGenerator, SawtoothReferenceGenerator,
     SinusoidalReferenceGenerator, StepReferenceGenerator, SwitchedReferenceGenerator, TriangularReferenceGenerator, WienerProcessReferenceGenerator,

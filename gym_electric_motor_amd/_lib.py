@@ -188,6 +188,27 @@ class GemxEpisodeConfig(C.Structure):
 
 EPISODE_STATE_BYTES = 28  # GEMX_EPISODE_STATE_BYTES
 
+PROFILE_INTERP_HOLD, PROFILE_INTERP_LINEAR = 0, 1  # GEMX_PROFILE_INTERP_*
+PROFILE_END_HOLD, PROFILE_END_WRAP = 0, 1  # GEMX_PROFILE_END_*
+PROFILE_START_ZERO, PROFILE_START_RANDOM = 0, 1  # GEMX_PROFILE_START_*
+REFPROFILE_BLOB_HEADER_BYTES = 64  # GEMX_REFPROFILE_BLOB_HEADER_BYTES
+
+
+class GemxRefprofileConfig(C.Structure):
+    """Mirror of `gemx_refprofile_config` (include/gemx.h)."""
+
+    _fields_ = [
+        ("struct_size", C.c_int32), ("n_ref", C.c_int32), ("n_rows", C.c_int32), ("per_env", C.c_int32),
+        ("interpolation", C.c_int32), ("end", C.c_int32), ("start", C.c_int32), ("reserved", C.c_int32),
+        ("seed", C.c_uint64), ("env_base", C.c_int64), ("tau", C.c_double), ("profile_tau", C.c_double),
+    ]
+
+
+def refprofile_state_bytes(n_envs):
+    """`gemx_refprofile_state_bytes` restated: the header, then k, s, e as int32 [3][N]."""
+    return REFPROFILE_BLOB_HEADER_BYTES + 12 * int(n_envs)
+
+
 EXPORTS = (
     "gemx_abi_version", "gemx_sizeof_config", "gemx_last_error", "gemx_device_count", "gemx_create", "gemx_destroy",
     "gemx_n_envs", "gemx_n_ode", "gemx_n_out", "gemx_n_action", "gemx_action_itemsize", "gemx_n_switch_bytes", "gemx_reset_observation", "gemx_set_reward", "gemx_rollout_reward", "gemx_refgen_create", "gemx_refgen_destroy", "gemx_refgen_reset",
@@ -202,6 +223,8 @@ EXPORTS = (
     "gemx_fluxobs_get_state", "gemx_fluxobs_set_state",
     "gemx_noise_create", "gemx_noise_destroy", "gemx_noise_step", "gemx_noise_draws", "gemx_noise_get_position", "gemx_noise_set_position",
     "gemx_episode_create", "gemx_episode_destroy", "gemx_episode_step", "gemx_episode_rows", "gemx_episode_get_state", "gemx_episode_set_state",
+    "gemx_refprofile_create", "gemx_refprofile_destroy", "gemx_refprofile_reset", "gemx_refprofile_step", "gemx_refprofile_rollout",
+    "gemx_refprofile_rollout_shell", "gemx_refprofile_get_state", "gemx_refprofile_state_bytes", "gemx_refprofile_get_blob", "gemx_refprofile_set_blob",
 )
 
 
@@ -286,6 +309,17 @@ def load():
     L.gemx_episode_rows.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp]
     L.gemx_episode_get_state.argtypes = [vp, vp, vp]
     L.gemx_episode_set_state.argtypes = [vp, vp, vp]
+    L.gemx_refprofile_create.argtypes = [C.POINTER(GemxRefprofileConfig), vp, i64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.gemx_refprofile_destroy.argtypes = [vp]
+    L.gemx_refprofile_reset.argtypes = [vp, vp, vp]
+    L.gemx_refprofile_step.argtypes = [vp, vp, vp, vp]
+    L.gemx_refprofile_rollout.argtypes = [vp, vp, i32, vp, vp]
+    L.gemx_refprofile_rollout_shell.argtypes = [vp, vp, i32, vp, vp]
+    L.gemx_refprofile_get_state.argtypes = [vp, vp, vp]
+    L.gemx_refprofile_state_bytes.argtypes = [vp]
+    L.gemx_refprofile_state_bytes.restype = i64
+    L.gemx_refprofile_get_blob.argtypes = [vp, vp, vp]
+    L.gemx_refprofile_set_blob.argtypes = [vp, vp, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

@@ -153,6 +153,11 @@ def make_sharded(env_id, n_envs_total, rank, world, device, **kwargs):
 
     lo, hi = shard_range(n_envs_total, rank, world)
     kwargs.setdefault("env_base", lo)
+    from .reference_generators import as_profile_holder
+
+    holder = as_profile_holder(kwargs.get("reference_generator"))
+    if holder is not None:  # a per-env table [T, n_envs_total, n_ref] is cut to this shard's envs; the start rows are keyed by env_base
+        kwargs["reference_generator"] = holder.shard(lo, hi, n_envs_total)
     env = make(env_id, n_envs=hi - lo, device=device, **kwargs)
     env.shard = (lo, hi)
     env.n_envs_total = n_envs_total

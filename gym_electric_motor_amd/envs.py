@@ -90,7 +90,7 @@ import numpy as np
 from .spaces import Box
 from . import components as comp
 from . import physical_systems as bps
-from .reference_generators import ReplayReferenceGenerator
+from .reference_generators import ProfileReferences, ReplayReferenceGenerator
 
 _ID = re.compile(r"^(Finite|Cont)-(CC|TC|SC)-(PermExDc|SeriesDc|ShuntDc|ExtExDc|PMSM|SynRM|SCIM|EESM|DFIM)-v0$")
 
@@ -437,8 +437,8 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         if unknown:
             raise TypeError(f"reward_function: unknown keywords {unknown}; known: {list(self._REWARD_KEYS)}")
         gen = reference_generator
-        if isinstance(gen, ReplayReferenceGenerator):  # its columns are the env id's referenced states unless it names its own
-            gen.set_modules(ps, _defer_create=_defer_create, default_states=d["reference_states"])
+        if isinstance(gen, ReplayReferenceGenerator) or (isinstance(gen, ProfileReferences) and not gen.is_set):
+            gen.set_modules(ps, _defer_create=_defer_create, default_states=d["reference_states"])  # its columns are the env id's referenced states unless it names its own
         elif not gen.is_set:  # (a generator the caller has already announced to this system is taken as it is)
             gen.set_modules(ps, _defer_create=_defer_create)
         if gen.n_envs != ps.n_envs:
@@ -731,7 +731,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     flatten_observation: the complete env hands out ONE tensor [N, n_post + n_ref], the processed state followed by the references.
     reference_generator: None | 'default' | BatchedWienerProcessReferenceGenerator | BatchedMultipleReferenceGenerator | a holder such as
     StepReferenceGenerator(...) or SwitchedReferenceGenerator([...]), or a list of holders (one per referenced state; the reference's own
-    generator instances are read the same way, its SwitchedReferenceGenerator excepted) | ReplayReferenceGenerator;
+    generator instances are read the same way, its SwitchedReferenceGenerator excepted) | ProfileReferenceGenerator(profiles, ...) (given
+    trajectories per env, on the device) | ReplayReferenceGenerator;
     reward_function: None | 'default' | dict of `set_reward` keywords.  Naming either one selects the complete env
     (CompleteBatchedElectricMotorEnv), the other then takes the env id's default (`default_env_modules`); `seed` keys the default
     generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env.
@@ -797,7 +798,8 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     if reference_generator is None and reward_function is None:
         return BatchedElectricMotorEnv(system, observation=observation, _defer_create=bool(kwargs.get("_defer_create", False)), flux_action=flux_action,
                                        state_noise=state_noise, episodes=episodes)
-    from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator
+    from .reference_generators import (BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, SWITCHED_REFUSAL, _DeviceGenerators, _SubGenerator,
+                                       as_profile_holder)
 
     modules = default_env_modules(env_id)
     if reference_generator is None or (isinstance(reference_generator, str) and reference_generator == "default"):
@@ -805,9 +807,11 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
                                                                      **modules["generator"])
     elif isinstance(reference_generator, (str, type)):
         raise ValueError("reference_generator: 'default', a BatchedWienerProcessReferenceGenerator, a BatchedMultipleReferenceGenerator, generator "
-                         "holders (e.g. StepReferenceGenerator(...), or a list of them) or a ReplayReferenceGenerator instance")
+                         "holders (e.g. StepReferenceGenerator(...), or a list of them), a ProfileReferenceGenerator or a ReplayReferenceGenerator instance")
     elif type(reference_generator).__name__ == "SwitchedReferenceGenerator" and not isinstance(reference_generator, _SubGenerator):
         raise NotImplementedError(SWITCHED_REFUSAL)  # (the reference's own instance; the holder of the same name goes on below)
+    elif as_profile_holder(reference_generator) is not None:  # given trajectories on the device (a list that mixes them with other kinds is refused)
+        reference_generator = ProfileReferences(reference_generator, seed=kwargs.get("seed", 0))
     elif not isinstance(reference_generator, (_DeviceGenerators, ReplayReferenceGenerator)):
         # holders, a list of them, or the reference's own instances: one handle, columns in state order
         reference_generator = BatchedMultipleReferenceGenerator(reference_generator, seed=kwargs.get("seed", 0))

@@ -57,6 +57,9 @@ class _DeviceGenerators:
     reference_names = property(lambda self: self._ordered)
     n_envs = property(lambda self: self._n_envs)
     is_set = property(lambda self: hasattr(self, "_cfg"), doc="set_modules has run")
+    # the entry points behind the surface below (a generator on a handle of another kind names its own: ProfileReferences)
+    _ABI = dict(reset="gemx_refgen_reset", step="gemx_refgen_step", rollout="gemx_refgen_rollout", rollout_shell="gemx_refgen_rollout_shell",
+                state_bytes="gemx_refgen_state_bytes", get_blob="gemx_refgen_get_blob", set_blob="gemx_refgen_set_blob", destroy="gemx_refgen_destroy")
 
     def _create(self, ps, create, cfg):
         import torch
@@ -85,7 +88,7 @@ class _DeviceGenerators:
         import torch
 
         m = None if mask is None else torch.as_tensor(mask).to(device=self._tdev, dtype=torch.uint8).contiguous()
-        _lib.check(self._L.gemx_refgen_reset(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None, self._stream()))
+        _lib.check(getattr(self._L, self._ABI["reset"])(self._handle, C.c_void_p(m.data_ptr()) if m is not None else None, self._stream()))
 
     def rollout(self, K, done=None, out=None):
         """References of the next K control steps, [K, N, n_ref].  done [K, N] (optional): terminations of those steps known in
@@ -95,7 +98,7 @@ class _DeviceGenerators:
         if out is None:
             out = torch.empty((int(K), self._n_envs, int(self._cfg.n_ref)), dtype=self._tdtype, device=self._tdev)
         d = None if done is None else done.to(device=self._tdev, dtype=torch.uint8).contiguous()
-        _lib.check(self._L.gemx_refgen_rollout(self._handle, C.c_void_p(d.data_ptr()) if d is not None else None, int(K),
+        _lib.check(getattr(self._L, self._ABI["rollout"])(self._handle, C.c_void_p(d.data_ptr()) if d is not None else None, int(K),
                                                C.c_void_p(out.data_ptr()), self._stream()))
         return out
 
@@ -139,7 +142,7 @@ class _DeviceGenerators:
             out = torch.empty((K, self._n_envs, int(self._cfg.n_ref)), dtype=self._tdtype, device=self._tdev)
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
         args = (C.c_void_p(done.data_ptr()) if done is not None else None, K, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        return _lib.bound_call(self._L.gemx_refgen_rollout_shell, self, args, (done, out, stream), out)
+        return _lib.bound_call(getattr(self._L, self._ABI["rollout_shell"]), self, args, (done, out, stream), out)
 
     def step(self, done=None, out=None):
         """One env-shell step in ONE launch (gemx_refgen_step): the generators of the envs with done[env] != 0 restart, then every
@@ -171,7 +174,7 @@ class _DeviceGenerators:
 
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
         args = (C.c_void_p(done.data_ptr()) if done is not None else None, C.c_void_p(out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        return _lib.bound_call(self._L.gemx_refgen_step, self, args, (done, out, stream), out)
+        return _lib.bound_call(getattr(self._L, self._ABI["step"]), self, args, (done, out, stream), out)
 
     def apply_done(self, done):
         """After a rollout: envs with any termination in `done` ([K, N] or [N]) restart their generators (closed-loop use)."""
@@ -183,7 +186,7 @@ class _DeviceGenerators:
     # ------------------------------------------------------------------ checkpoint
     def state_bytes(self):
         """Bytes of the handle's checkpoint blob (`gemx_refgen_state_bytes`)."""
-        return int(self._L.gemx_refgen_state_bytes(self._handle))
+        return int(getattr(self._L, self._ABI["state_bytes"])(self._handle))
 
     def get_state(self):
         """-> dict(blob, references) of new device tensors, for a checkpoint: the handle's whole per-(column, env) state as one opaque uint8
@@ -192,7 +195,7 @@ class _DeviceGenerators:
         import torch
 
         blob = torch.empty(self.state_bytes(), dtype=torch.uint8, device=self._tdev)
-        _lib.check(self._L.gemx_refgen_get_blob(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
+        _lib.check(getattr(self._L, self._ABI["get_blob"])(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
         return dict(blob=blob, references=self._refs.clone())
 
     def check_state(self, state):
@@ -219,12 +222,12 @@ class _DeviceGenerators:
         `gemx_refgen_set_blob`, which synchronises the stream for it); ValueError names the mismatch and the generator is untouched.
         The references are copied INTO the buffer this generator owns: bound launchers and captured graphs keep pointing at it."""
         blob, refs = self.check_state(state)
-        _lib.check(self._L.gemx_refgen_set_blob(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
+        _lib.check(getattr(self._L, self._ABI["set_blob"])(self._handle, C.c_void_p(blob.data_ptr()), self._stream()))
         self._refs.copy_(refs)
 
     def close(self):
         if self._handle is not None:
-            self._L.gemx_refgen_destroy(self._handle)
+            getattr(self._L, self._ABI["destroy"])(self._handle)
             self._handle = None
 
     def __del__(self):
@@ -458,6 +461,8 @@ def as_sub_generators(generator):
         return [h for g in generator for h in as_sub_generators(g)]
     if isinstance(generator, _SubGenerator):
         return [generator]
+    if isinstance(generator, ProfileReferenceGenerator):
+        raise ValueError("sub_generators: " + PROFILE_MIXED_REFUSAL)
     name = type(generator).__name__
     if name == "SwitchedReferenceGenerator":
         raise NotImplementedError(SWITCHED_REFUSAL)
@@ -703,3 +708,149 @@ class ReplayReferenceGenerator:
 
     def close(self):
         pass
+
+
+PROFILE_MIXED_REFUSAL = ("a ProfileReferenceGenerator serves all referenced columns of its env: it cannot be mixed with other generator holders in "
+                         "one list (give the other states' set points as further columns of the profile)")
+_PROFILE_CHOICES = dict(interpolation=dict(hold=_lib.PROFILE_INTERP_HOLD, linear=_lib.PROFILE_INTERP_LINEAR),
+                        end=dict(hold=_lib.PROFILE_END_HOLD, wrap=_lib.PROFILE_END_WRAP),
+                        start=dict(zero=_lib.PROFILE_START_ZERO, random=_lib.PROFILE_START_RANDOM))
+
+
+class ProfileReferenceGenerator:
+    """Given reference trajectories -- drive cycles, recorded set-point profiles, a benchmark suite of steps -- on the device, per env:
+    the holder `ga.make(env_id, reference_generator=ProfileReferenceGenerator(profiles, ...))` takes wherever it takes the other device
+    generators.  Unlike a ReplayReferenceGenerator the position lives in device memory: an env that terminates (or is truncated)
+    restarts its profile, a step is one kernel launch that can be captured in a HIP graph, `rollout_complete` replays the resets, and
+    the position travels in the checkpoint.
+
+    profiles: [T, n_ref] (every env follows the same profile) or [T, N, n_ref] (one per env), normalised units, numpy or torch.
+    reference_states: the state each column refers to (default: the env id's referenced states); the env shows the columns in the state
+    order of the physical system.  profile_tau: sampling time of the rows (None: the system's tau, one row per control step);
+    interpolation 'linear' | 'hold' between rows when it differs.  end: 'hold' (stay on the last row) | 'wrap' (periodic).  start:
+    'zero' | 'random' -- a start row per (env, episode), uniform in [0, T - 1], a function of (seed, global env index, episode number).
+    An env at step k of its episode, started at row s, stands at position s + k * tau / profile_tau (csrc/gemx_refprofile.hip)."""
+
+    def __init__(self, profiles, reference_states=None, profile_tau=None, interpolation="linear", end="hold", start="zero", seed=None):
+        if np.ndim(profiles) not in (2, 3):
+            raise ValueError(f"profiles must be [T, n_ref] or [T, N, n_ref], not {np.ndim(profiles)}-dimensional")
+        shape = tuple(int(x) for x in np.shape(profiles))
+        if shape[0] < 1:
+            raise ValueError("profiles: T, the number of rows, must be >= 1")
+        if not 1 <= shape[-1] <= _lib.MAX_REF:
+            raise ValueError(f"profiles carry {shape[-1]} columns: 1..{_lib.MAX_REF} referenced states (_lib.MAX_REF)")
+        for what, value in (("interpolation", interpolation), ("end", end), ("start", start)):
+            if not isinstance(value, str) or value not in _PROFILE_CHOICES[what]:
+                raise ValueError(f"{what}: one of {sorted(_PROFILE_CHOICES[what])}, not {value!r}")
+        if profile_tau is not None and not (np.ndim(profile_tau) == 0 and np.isfinite(float(profile_tau)) and float(profile_tau) > 0):
+            raise ValueError(f"profile_tau: a positive sampling time or None (the system's tau), not {profile_tau!r}")
+        self.profiles = profiles
+        self.reference_states = None if reference_states is None else tuple(s.lower() for s in ([reference_states] if isinstance(reference_states, str) else reference_states))
+        if self.reference_states is not None and len(set(self.reference_states)) != len(self.reference_states):
+            raise ValueError(f"reference_states names a state twice: {list(self.reference_states)}")
+        if self.reference_states is not None and len(self.reference_states) != shape[-1]:
+            raise ValueError(f"profiles carry {shape[-1]} columns for the {len(self.reference_states)} reference_states {list(self.reference_states)}")
+        self.profile_tau = None if profile_tau is None else float(profile_tau)
+        self.interpolation, self.end, self.start = interpolation, end, start
+        self.seed = None if seed is None else int(seed)
+        self.shape = shape
+
+    per_env = property(lambda self: len(self.shape) == 3, doc="one profile per env ([T, N, n_ref])")
+
+    def shard(self, lo, hi, n_total):
+        """-> the holder of envs [lo, hi) of a job of n_total: a per-env table is sliced to the shard, a shared one is kept."""
+        if not self.per_env:
+            return self
+        if self.shape[1] != int(n_total):
+            raise ValueError(f"profiles are for {self.shape[1]} envs, the job has n_envs_total = {int(n_total)}")
+        return ProfileReferenceGenerator(self.profiles[:, int(lo):int(hi)], self.reference_states, self.profile_tau, self.interpolation, self.end, self.start, self.seed)
+
+    def __repr__(self):
+        return (f"ProfileReferenceGenerator(profiles{list(self.shape)}, reference_states={self.reference_states!r}, profile_tau={self.profile_tau!r}, "
+                f"interpolation={self.interpolation!r}, end={self.end!r}, start={self.start!r}, seed={self.seed!r})")
+
+
+def as_profile_holder(generator):
+    """-> the ProfileReferenceGenerator holder `generator` is (alone, or as a list of one), else None.  A list that mixes one with other
+    holders is refused: ValueError."""
+    if isinstance(generator, ProfileReferenceGenerator):
+        return generator
+    if isinstance(generator, (list, tuple)) and any(isinstance(g, ProfileReferenceGenerator) for g in generator):
+        if len(generator) != 1:
+            raise ValueError("reference_generator: " + PROFILE_MIXED_REFUSAL)
+        return generator[0]
+    return None
+
+
+class ProfileReferences(_DeviceGenerators):
+    """The device generator behind a ProfileReferenceGenerator holder (gemx_refprofile_*): the surface and the calling contract of the
+    other device generators -- `reset(mask)`, `step(done)` (restart first, then show and advance), `rollout` (restarts after row k),
+    `rollout_shell` (before it: K x step), `bind_step` / `bind_rollout_shell` (graph-capturable), `get_state` / `set_state`.  The table is
+    this object's tensor, in the state order of the physical system; the handle borrows it."""
+
+    _ABI = dict(reset="gemx_refprofile_reset", step="gemx_refprofile_step", rollout="gemx_refprofile_rollout", rollout_shell="gemx_refprofile_rollout_shell",
+                state_bytes="gemx_refprofile_state_bytes", get_blob="gemx_refprofile_get_blob", set_blob="gemx_refprofile_set_blob", destroy="gemx_refprofile_destroy")
+
+    def __init__(self, holder, seed=0, env_base=None):
+        holder = as_profile_holder(holder)
+        if holder is None:
+            raise TypeError("ProfileReferences is built from a ProfileReferenceGenerator holder")
+        self.holder = holder
+        self._seed = int(holder.seed if holder.seed is not None else seed) & (2**64 - 1)
+        self._env_base = None if env_base is None else int(env_base)
+        self._handle = None
+        self._refs = None
+
+    def set_modules(self, physical_system, _defer_create=False, default_states=None):
+        ps, h = physical_system, self.holder
+        states = h.reference_states if h.reference_states is not None else tuple(default_states or ())
+        n_ref = h.shape[-1]
+        if len(states) != n_ref:
+            raise ValueError(f"profiles carry {n_ref} columns for the {len(states)} referenced states {list(states)}")
+        missing = [s for s in states if s not in ps.state_positions]
+        if missing:
+            raise ValueError(f"reference_states {missing} are not states of the physical system {list(ps.state_names)}")
+        if h.per_env and h.shape[1] != ps.n_envs:
+            raise ValueError(f"profiles are for N = {h.shape[1]} envs, the system has {ps.n_envs}")
+        self._order = sorted(range(n_ref), key=lambda j: ps.state_positions[states[j]])  # the caller's columns -> state order
+        self._ordered = tuple(states[j] for j in self._order)
+        self._n_envs = ps.n_envs
+        cfg = _lib.GemxRefprofileConfig()
+        cfg.struct_size = C.sizeof(cfg)
+        cfg.n_ref, cfg.n_rows, cfg.per_env = n_ref, h.shape[0], int(h.per_env)
+        cfg.tau = float(ps.tau)
+        cfg.profile_tau = h.profile_tau if h.profile_tau is not None else float(ps.tau)
+        # (rows sampled at tau itself are shown as they are: w == 0 at every step, and nothing is interpolated)
+        cfg.interpolation = _lib.PROFILE_INTERP_HOLD if cfg.profile_tau == cfg.tau else _PROFILE_CHOICES["interpolation"][h.interpolation]
+        cfg.end, cfg.start = _PROFILE_CHOICES["end"][h.end], _PROFILE_CHOICES["start"][h.start]
+        cfg.seed = self._seed
+        cfg.env_base = self._env_base if self._env_base is not None else int(getattr(ps, "env_base", 0))
+        self._cfg = cfg
+        idx = [ps.state_positions[n] for n in self._ordered]
+        self._space = (np.asarray(ps.state_space.low, dtype=float)[idx], np.asarray(ps.state_space.high, dtype=float)[idx])
+        if _defer_create:
+            return self
+        import torch
+
+        self._L = _lib.load()
+        self._tdev, self._tdtype = ps._tdev, ps._tdtype
+        self._table = torch.as_tensor(h.profiles).to(device=self._tdev, dtype=self._tdtype)[..., self._order].contiguous()
+        handle = C.c_void_p()
+        _lib.check(self._L.gemx_refprofile_create(C.byref(cfg), C.c_void_p(self._table.data_ptr()), self._n_envs, ps.device,
+                                                  _lib.F64 if self._tdtype == torch.float64 else _lib.F32, C.byref(handle)))
+        self._handle = handle
+        self._refs = torch.zeros((self._n_envs, n_ref), dtype=self._tdtype, device=self._tdev)
+        return self
+
+    ratio = property(lambda self: self._cfg.tau / self._cfg.profile_tau, doc="rows per control step: tau / profile_tau")
+    reference_space = property(lambda self: self._space, doc="(low, high) arrays [n_ref]: the state space's bounds of the referenced states")
+    table = property(lambda self: self._table, doc="the device table the handle reads, columns in state order")
+
+    def state(self):
+        """dict(k, s, e) of int32 [N] tensors, for tests / inspection: steps shown since the episode began, its start row, episodes begun."""
+        import torch
+
+        out = torch.empty((3, self._n_envs), dtype=torch.int32, device=self._tdev)
+        _lib.check(self._L.gemx_refprofile_get_state(self._handle, C.c_void_p(out.data_ptr()), self._stream()))
+        torch.cuda.current_stream(self._tdev).synchronize()
+        return dict(k=out[0], s=out[1], e=out[2])

@@ -641,6 +641,65 @@ int gemx_episode_rows(gemx_episode *h, const uint8_t *done_dev, const void *rewa
 int gemx_episode_get_state(gemx_episode *h, void *out_dev, void *stream);
 int gemx_episode_set_state(gemx_episode *h, const void *in_dev, void *stream);
 
+/* Device-side PROFILE REFERENCES (new struct and entry points only, ABI number unchanged): given reference trajectories -- drive cycles,
+ * recorded set-point profiles -- shown per env from a table in device memory, as a stage with a handle of its own.  The table is R
+ * [n_rows][n_ref] shared by all envs (per_env = 0) or [n_rows][N][n_ref], one profile per env (per_env = 1), in normalised units; it is
+ * BORROWED: the handle keeps the device pointer and the caller keeps the memory alive and unchanged as long as the handle.  Per env the
+ * handle keeps k (int32: steps shown since the episode began), s (int32: the episode's start row) and e (uint32: episodes begun so far).
+ *   position   p = s + k * (tau / profile_tau), evaluated in double from the integers every time (a product rounded once, then a sum
+ *              rounded once): never accumulated, step 10 000 carries no drift
+ *   rows       i = floor(p), w = p - i;  END_HOLD: p >= n_rows - 1 shows row n_rows - 1;  END_WRAP: rows modulo n_rows, the partner of
+ *              row n_rows - 1 is row 0
+ *   value      INTERP_HOLD, or w == 0: the table entry of row i, the same bits;  INTERP_LINEAR: fma((R)w, b - a, a) in R, a and b the
+ *              entries of row i and of its partner
+ *   restart    k = 0, e += 1, and with START_RANDOM s = min(int(u * n_rows), n_rows - 1), u the first word of the Philox4x32-10 block
+ *              keyed by (seed, env_base + env, e): a function of the global env index and the episode number alone, so shards by env_base
+ *              show what the whole job shows.  START_ZERO: s = 0.  A fresh handle has k = s = e = 0.
+ *   gemx_refprofile_reset: restarts the envs with mask_dev[env] != 0 (NULL: all).
+ *   gemx_refprofile_step: ONE launch, the contract of gemx_refgen_step: envs with done_dev[env] != 0 (NULL: none) restart FIRST, then
+ *     refs_dev [N][n_ref] R receives the values at p(k) and k advances.
+ *   gemx_refprofile_rollout / _rollout_shell: K rows refs_out_dev [K][N][n_ref] with done_dev [K][N] (or NULL) in one launch, a lane
+ *     walking its env's rows in order; _rollout restarts AFTER row k (gemx_refgen_rollout's order), _rollout_shell BEFORE it: one call ==
+ *     K x gemx_refprofile_step(done[k]), row for row and bit for bit (one __device__ row function serves all three).
+ *   gemx_refprofile_get_state: int32 [3][N] = k, s, e (one device-to-device copy).
+ *   gemx_refprofile_state_bytes / _get_blob / _set_blob: the checkpoint, a header of GEMX_REFPROFILE_BLOB_HEADER_BYTES and the 12 N
+ *     bytes of state; _set_blob copies the header alone to the host (synchronises `stream`) and checks it BEFORE anything is enqueued:
+ *     GEMX_ERR_ARG, the mismatch named in gemx_last_error, for a blob of another n_envs, n_ref, n_rows, table layout or shard
+ *     (env_base); the handle is then untouched.  The table itself is configuration and does not travel.
+ * Reset, step and the rollouts are one kernel launch each: no host state, no allocation, no synchronisation -- a captured call replays
+ * and advances the counters.  refs tensors need the alignment of R only.
+ * GEMX_ERR_ARG at create: a null pointer, struct_size, n_ref outside [1, GEMX_MAX_REF], n_rows < 1, a flag outside its enum, tau or
+ * profile_tau not positive and finite, tau / profile_tau above 2^20, n_envs < 1, a misaligned table. */
+enum { GEMX_PROFILE_INTERP_HOLD = 0, GEMX_PROFILE_INTERP_LINEAR = 1 };
+enum { GEMX_PROFILE_END_HOLD = 0, GEMX_PROFILE_END_WRAP = 1 };
+enum { GEMX_PROFILE_START_ZERO = 0, GEMX_PROFILE_START_RANDOM = 1 };
+#define GEMX_REFPROFILE_BLOB_HEADER_BYTES 64
+typedef struct gemx_refprofile_config {
+    int32_t struct_size;   /* = sizeof(gemx_refprofile_config) */
+    int32_t n_ref;         /* 1..GEMX_MAX_REF columns */
+    int32_t n_rows;        /* T: rows of a profile, >= 1 */
+    int32_t per_env;       /* 0: table [n_rows][n_ref], shared; 1: table [n_rows][N][n_ref] */
+    int32_t interpolation; /* GEMX_PROFILE_INTERP_* */
+    int32_t end;           /* GEMX_PROFILE_END_* */
+    int32_t start;         /* GEMX_PROFILE_START_* */
+    int32_t reserved;
+    uint64_t seed;         /* START_RANDOM */
+    int64_t env_base;      /* global index of env 0 (see gemx_config.env_base) */
+    double tau;            /* control period of the physical system */
+    double profile_tau;    /* sampling time of the table's rows */
+} gemx_refprofile_config;
+typedef struct gemx_refprofile gemx_refprofile;
+int gemx_refprofile_create(const gemx_refprofile_config *cfg, const void *table_dev, int64_t n_envs, int device, int dtype, gemx_refprofile **out);
+int gemx_refprofile_destroy(gemx_refprofile *h);
+int gemx_refprofile_reset(gemx_refprofile *h, const uint8_t *mask_dev, void *stream);
+int gemx_refprofile_step(gemx_refprofile *h, const uint8_t *done_dev, void *refs_dev, void *stream);
+int gemx_refprofile_rollout(gemx_refprofile *h, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
+int gemx_refprofile_rollout_shell(gemx_refprofile *h, const uint8_t *done_dev, int32_t K, void *refs_out_dev, void *stream);
+int gemx_refprofile_get_state(gemx_refprofile *h, int32_t *k_s_e_out_dev, void *stream);
+int64_t gemx_refprofile_state_bytes(gemx_refprofile *h);
+int gemx_refprofile_get_blob(gemx_refprofile *h, void *out_dev, void *stream);
+int gemx_refprofile_set_blob(gemx_refprofile *h, const void *in_dev, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
