@@ -7,6 +7,7 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
     python examples/closed_loop.py --complete --graph 64 --reference step               # ... on step (sinusoidal, ...) profiles
     python examples/closed_loop.py --complete --graph 64 --reference profile            # ... on a given two-column cycle, periodic, per env
     python examples/closed_loop.py --complete --rollout 500                             # open loop: (state, reference, reward, done) datasets
+    python examples/closed_loop.py --complete --rollout 500 --gae                       # ... and GAE advantages of each dataset, one launch
     python examples/closed_loop.py --complete --graph 64 --time-limit 500               # episodes of 500 steps, counted on the device
 
 Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
@@ -15,6 +16,8 @@ reward, then the fused generator step), `--bind` with everything resolved once (
 `--complete --rollout K`: no policy in the loop -- random actions generated on the device, K control steps per `rollout_complete_synthetic`
 call (physics rollout, generator rollout in the shell's order, reward pass: three launches per K steps), i.e. the dataset a closed loop
 of K `step()`s on the same actions would have produced, bit for bit.
+`--complete --rollout K --gae`: a value head beside the policy (the negative tracking error, scaled to the horizon of the discount) and
+`ga.bind_advantages` on each dataset's reward and done rows: advantages and returns [K, N] in one more launch per K steps.
 `--complete --time-limit M`: `make(..., max_episode_steps=M, episode_statistics=True)` -- an env is truncated after M steps and restarts in
 front of its next step; the mean return and length of the finished episodes come from the device counters (`env.episode_statistics()`).
 
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--flat", action="store_true", help="--complete: the device-side observation stage hands the policy ONE flat tensor "
                                                         "(i_sd, i_sq, cos(epsilon), sin(epsilon), reference i_sd, reference i_sq)")
     ap.add_argument("--rollout", type=int, default=0, metavar="K", help="--complete: open-loop datasets, K control steps per rollout_complete_synthetic call")
+    ap.add_argument("--gae", action="store_true", help="--complete --rollout K: GAE(0.99, 0.95) advantages of every dataset (ga.bind_advantages, one launch)")
     ap.add_argument("--time-limit", type=int, default=0, metavar="M", help="--complete: episodes of at most M steps (max_episode_steps) and the device-side "
                                                                             "episode statistics")
     args = ap.parse_args()
@@ -53,6 +57,8 @@ def main():
         ap.error("--time-limit needs --complete (and no --rollout: a fused K-step launch cannot restart a truncated env)")
     if args.rollout and (not args.complete or args.bind or args.graph):
         ap.error("--rollout needs --complete (and neither --bind nor --graph)")
+    if args.gae and not args.rollout:
+        ap.error("--gae needs --complete --rollout K")
     if args.reference != "wiener" and not args.complete:
         ap.error("--reference needs --complete")
     if args.flat and not args.complete:
@@ -199,14 +205,30 @@ def rollout_loop(args, env):
     state, refs, reward = (torch.empty(s, device="cuda") for s in shapes[:3])
     done = torch.empty(shapes[3], dtype=torch.uint8, device="cuda")
     ret = torch.zeros(n, device="cuda")
+    gae = None
+    if args.gae:  # the value head: minus the tracking error of the referenced currents over the discount's horizon; everything bound once
+        import gym_electric_motor_amd as ga
+
+        gamma, lam = 0.99, 0.95
+        cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
+        value, advantage, returns = (torch.empty_like(reward) for _ in range(3))
+        gae = ga.bind_advantages(reward, value, done, gamma=gamma, lam=lam, advantage_out=advantage, return_out=returns)
+
+        def value_head():
+            torch.sum((state[..., cols] - refs).abs(), dim=-1, out=value).mul_(-0.5 / (1.0 - gamma))
+
     env.reset()
     env.rollout_complete_synthetic(K, seed=1, state_out=state, refs_out=refs, reward_out=reward, done_out=done)  # (untimed: first launches)
+    if gae:
+        value_head(), gae()
     reps = max(1, args.steps // K)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(reps):
         env.rollout_complete_synthetic(K, seed=1, state_out=state, refs_out=refs, reward_out=reward, done_out=done)
         ret.add_(reward.sum(dim=0))
+        if gae:
+            value_head(), gae()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     steps = reps * K
@@ -214,6 +236,10 @@ def rollout_loop(args, env):
           f"{n * steps / dt / 1e6:.1f} M env-steps/s ({dt / steps * 1e6:.2f} us/step); state {tuple(state.shape)}, refs {tuple(refs.shape)}; "
           f"{int(done.sum())} terminations in the last chunk; mean return {float(ret.mean()):.2f}; kernel: {ps.last_launch().split(' grid')[0]}")
     assert torch.isfinite(ret).all()
+    if gae:
+        assert torch.isfinite(advantage).all() and torch.isfinite(returns).all()
+        print(f"GAE(gamma {gamma}, lambda {lam}) of every dataset, one launch per {K} steps (in the time above): advantage {tuple(advantage.shape)} mean "
+              f"{float(advantage.mean()):+.4f} std {float(advantage.std()):.4f}; returns mean {float(returns.mean()):+.3f}; value head mean {float(value.mean()):+.3f}")
     env.close()
 
 

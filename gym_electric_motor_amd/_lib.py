@@ -204,6 +204,12 @@ class GemxRefprofileConfig(C.Structure):
     ]
 
 
+class GemxReturnsConfig(C.Structure):
+    """Mirror of `gemx_returns_config` (include/gemx.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("gamma", C.c_double), ("lam", C.c_double), ("flags", C.c_int32)]
+
+
 def refprofile_state_bytes(n_envs):
     """`gemx_refprofile_state_bytes` restated: the header, then k, s, e as int32 [3][N]."""
     return REFPROFILE_BLOB_HEADER_BYTES + 12 * int(n_envs)
@@ -225,6 +231,7 @@ EXPORTS = (
     "gemx_episode_create", "gemx_episode_destroy", "gemx_episode_step", "gemx_episode_rows", "gemx_episode_get_state", "gemx_episode_set_state",
     "gemx_refprofile_create", "gemx_refprofile_destroy", "gemx_refprofile_reset", "gemx_refprofile_step", "gemx_refprofile_rollout",
     "gemx_refprofile_rollout_shell", "gemx_refprofile_get_state", "gemx_refprofile_state_bytes", "gemx_refprofile_get_blob", "gemx_refprofile_set_blob",
+    "gemx_returns_rows",
 )
 
 
@@ -320,6 +327,7 @@ def load():
     L.gemx_refprofile_state_bytes.restype = i64
     L.gemx_refprofile_get_blob.argtypes = [vp, vp, vp]
     L.gemx_refprofile_set_blob.argtypes = [vp, vp, vp]
+    L.gemx_returns_rows.argtypes = [C.POINTER(GemxReturnsConfig), i64, i32, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

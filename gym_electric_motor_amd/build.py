@@ -6,7 +6,7 @@ Sources (gym_electric_motor_amd/csrc):
                                         libgemx_u<S>_<C>_<F>.so, which gemx_create loads with dlopen (round 6: a handle maps the C ABI and
                                         the one unit it runs, not all 38)
     gemx_capi.hip                       C ABI (include/gemx.h), validation, small kernels, unit loader  } libgemx.so
-    gemx_support.hpp                    row tile in LDS and entry-point checks of the seven support units below (SUPPORT) }
+    gemx_support.hpp                    row tile in LDS and entry-point checks of the eight support units below (SUPPORT) }
     gemx_refgen.hip                     device-side reference generators: Wiener, the other kinds, switched (gemx_refgen_*) }
     gemx_obsproc.hip                    device-side observation stage (gemx_obsproc_*)                  }
     gemx_fluxobs.hip                    device-side FluxObserver and flux-oriented dq actions (gemx_fluxobs_*) }
@@ -14,7 +14,8 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_statenoise.hip                 device-side StateNoiseProcessor: noise, done and reward on the noisy row (gemx_noise_*) }
     gemx_episode.hip                    device-side episode time limit and episode statistics (gemx_episode_*) }
     gemx_refprofile.hip                 device-side profile references: drive cycles per env (gemx_refprofile_*) }
-The 38 units (19 system/converter pairs x fp32, fp64) and the eight objects of libgemx.so are compiled in parallel.
+    gemx_returns.hip                    discounted returns and GAE(lambda) over stored rollout rows (gemx_returns_rows) }
+The 38 units (19 system/converter pairs x fp32, fp64) and the nine objects of libgemx.so are compiled in parallel.
 """
 import concurrent.futures as cf
 import glob
@@ -30,7 +31,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc", "gemx_obsproc.hip", ["gemx_support.hpp"], 0.1),
            ("fluxobs", "gemx_fluxobs.hip", ["gemx_support.hpp"], 0.1), ("rewardpass", "gemx_rewardpass.hip", ["gemx_support.hpp"], 0.1),
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
-           ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05)]
+           ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05)]
 SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")

@@ -1,5 +1,5 @@
 // gemx_support.hpp -- what the small units of libgemx.so behind the stepping kernels share (gemx_obsproc.hip, gemx_rewardpass.hip,
-// gemx_fluxobs.hip, gemx_refgen.hip, gemx_statenoise.hip, gemx_episode.hip, gemx_refprofile.hip; nothing else includes it): the row tile in LDS and the checks of their entry points.
+// gemx_fluxobs.hip, gemx_refgen.hip, gemx_statenoise.hip, gemx_episode.hip, gemx_refprofile.hip, gemx_returns.hip; nothing else includes it): the row tile in LDS and the checks of their entry points.
 //
 // Row tile: rows of L dwords, contiguous in global memory, sit in LDS at an ODD dword stride so that lane r reads row r without bank
 // conflicts.  Global memory is moved in 16-byte units, consecutive lanes consecutive units; a unit straddles rows whenever L is no

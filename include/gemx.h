@@ -39,7 +39,8 @@ extern "C" {
                             *    into device memory (gemx_refgen_rollout: same bits);
                             * 9: gemx_refgen_kinds_config / gemx_refgen_create_kinds / gemx_refgen_get_params (new struct and entry points only: a kind per
                             *    generator column -- Wiener, Laplace, sinusoidal, step, triangular, sawtooth, constant; gemx_refgen_config handles: same bits);
-                            *    + gemx_episode_config / gemx_episode_* (new struct and entry points only: episode time limit and statistics) */
+                            *    + gemx_episode_config / gemx_episode_* (new struct and entry points only: episode time limit and statistics)
+                            *    + gemx_returns_config / gemx_returns_rows (new struct and entry point only: discounted returns and GAE over stored rows) */
 #define GEMX_MAX_ODE 8  /* ODE state length incl. omega and the angle      */
 #define GEMX_MAX_OUT 24 /* system-state (observation) length               */
 #define GEMX_MODEL_ROWS 5
@@ -699,6 +700,41 @@ int gemx_refprofile_get_state(gemx_refprofile *h, int32_t *k_s_e_out_dev, void *
 int64_t gemx_refprofile_state_bytes(gemx_refprofile *h);
 int gemx_refprofile_get_blob(gemx_refprofile *h, void *out_dev, void *stream);
 int gemx_refprofile_set_blob(gemx_refprofile *h, const void *in_dev, void *stream);
+
+/* Device-side DISCOUNTED RETURNS and GENERALISED ADVANTAGE ESTIMATES, GAE(lambda), over the stored rows of a rollout (new struct and
+ * entry point only, ABI number unchanged): the reverse scan over K per env that every learner runs on reward [K][N], done [K][N] and a
+ * critic's value [K][N], as ONE launch.  No per-env state survives a call: there is no handle.  Per env, for k = K-1 ... 0, with one
+ * double accumulator A and everything converted to double first:
+ *     term = terminated[k] != 0;  end = ended[k] != 0 (ended_dev NULL: end = term);  trunc = end && !term
+ *     v      = value[k]
+ *     v_next = k == K-1 ? last_value : value[k+1]                          (last_value_dev NULL: 0)
+ *     if (end)  v_next = trunc && final_value ? final_value[k] : 0         (final_value_dev is read at rows with end && !term ONLY)
+ *     t1 = gamma * v_next;  delta = (reward[k] + t1) - v
+ *     t2 = gamma * lam;     t3 = t2 * A;   A = end ? delta : delta + t3
+ *     advantage[k] = (R)A;  return[k] = (R)(A + v)
+ *   A starts as carry_in (carry_in_dev NULL: 0); carry_out_dev (may be NULL) receives it after row 0.  A long trajectory can be scanned
+ *   in pieces, the later rows first: rows [k0, K) and then rows [0, k0) with carry_out -> carry_in and last_value = value[k0] are one
+ *   scan, bit for bit.  A TRUNCATED ROW WITHOUT final_value_dev IS TREATED AS TERMINATED.  Every product and sum above is rounded on its
+ *   own, in double, with no FMA across them: a float64 host restatement of these operations gives the same bits, and an fp32 output is
+ *   that double rounded to nearest.
+ *   value_dev NULL: the plain discounted return-to-go, the same rows with v = 0 and v_next = 0 everywhere and lam taken as 1 (cfg->lam
+ *   is ignored); A starts as carry_in if given, else as (double)last_value if given, else as 0 -- giving both is GEMX_ERR_ARG;
+ *   return_out_dev is the only output and final_value_dev must be NULL.  return[k] = reward[k] + gamma * return[k+1], cut at `end`.
+ *   reward_dev, value_dev, final_value_dev, advantage_out_dev, return_out_dev: [K][N] R, contiguous; last_value_dev [N] R;
+ *   terminated_dev (the env's done), ended_dev (terminated | truncated: what gemx_episode_* hands out) [K][N] uint8;
+ *   carry_in_dev, carry_out_dev [N] double.  The outputs must not overlap the inputs or each other.
+ * One kernel launch on `stream`: no allocation, no host state, no memset, no synchronisation -- the call can be captured in a HIP graph.
+ * GEMX_ERR_ARG: cfg NULL, struct_size, flags != 0, gamma or (with value_dev) lam outside [0, 1], reward_dev or terminated_dev NULL, no
+ * output, the value_dev-NULL restrictions above, K < 1, n_envs < 1, a misaligned tensor, an unknown dtype or device. */
+typedef struct gemx_returns_config {
+    int32_t struct_size; /* = sizeof(gemx_returns_config) */
+    double gamma;        /* discount, [0, 1] */
+    double lam;          /* GAE lambda, [0, 1]; ignored (taken as 1) without value_dev */
+    int32_t flags;       /* reserved: 0 */
+} gemx_returns_config;
+int gemx_returns_rows(const gemx_returns_config *cfg, int64_t n_envs, int32_t K, int dtype, int device, const void *reward_dev, const void *value_dev,
+                      const void *last_value_dev, const uint8_t *terminated_dev, const uint8_t *ended_dev, const void *final_value_dev,
+                      const double *carry_in_dev, double *carry_out_dev, void *advantage_out_dev, void *return_out_dev, void *stream);
 
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
