@@ -52,7 +52,11 @@ def main():
     ap.add_argument("--gae", action="store_true", help="--complete --rollout K: GAE(0.99, 0.95) advantages of every dataset (ga.bind_advantages, one launch)")
     ap.add_argument("--time-limit", type=int, default=0, metavar="M", help="--complete: episodes of at most M steps (max_episode_steps) and the device-side "
                                                                             "episode statistics")
+    ap.add_argument("--env-parameters", type=float, default=0.0, metavar="SPREAD", dest="env_parameters",
+                    help="domain randomisation: every env gets its own r_s, l_d, l_q and J_load, uniform within +-SPREAD (relative) of the motor's, from a seeded numpy Generator")
     args = ap.parse_args()
+    if args.env_parameters and args.rollout:
+        ap.error("--env-parameters: the synthetic-action rollouts are not available with per-env parameters")
     if args.time_limit and (not args.complete or args.rollout):
         ap.error("--time-limit needs --complete (and no --rollout: a fused K-step launch cannot restart a truncated env)")
     if args.rollout and (not args.complete or args.bind or args.graph):
@@ -71,7 +75,8 @@ def main():
 
     n = args.envs
     # Cont-CC-PMSM-v0 with (u_d, u_q) actions: the reference's DqToAbcActionProcessor folded into the kernel
-    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),))
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=(ga.DqToAbcActionProcessor.make("PMSM"),),
+                  **env_parameter_kw(args, ga))
     ps = env.physical_system
     gen = ga.BatchedWienerProcessReferenceGenerator(reference_states=("i_sd", "i_sq"), seed=1).set_modules(ps)
     ps.set_reward(reward_weights=dict(i_sd=0.5, i_sq=0.5), referenced_states=gen.reference_names)
@@ -100,6 +105,19 @@ def main():
     gen.close()
 
 
+def env_parameter_kw(args, ga):
+    """make() keywords of --env-parameters SPREAD: +-SPREAD relative uniform spread on the resistances, inductances and J_load."""
+    if not args.env_parameters:
+        return dict()
+    import numpy as np
+
+    rng = np.random.default_rng(7)
+    own = ga.make("Cont-CC-PMSM-v0", n_envs=1, _defer_create=True).physical_system  # (host side only: the env's own motor and load)
+    mp, j_load = own.electrical_motor.motor_parameter, float(own.mechanical_load._j_load)  # (the ConstantSpeedLoad's J_load is 0: the speed is held)
+    spread = lambda v: v * rng.uniform(1.0 - args.env_parameters, 1.0 + args.env_parameters, args.envs)  # noqa: E731
+    return dict(env_parameters=ga.EnvParameters(motor={k: spread(mp[k]) for k in ("r_s", "l_d", "l_q")}, load={"j_load": spread(j_load)}))
+
+
 def complete(args):
     import torch
 
@@ -123,7 +141,8 @@ def complete(args):
         obs_kw = dict(observed_states=["i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"], flatten_observation=True)
     if args.time_limit:
         obs_kw.update(max_episode_steps=args.time_limit, episode_statistics=True)
-    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw)
+    env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw,
+                  **env_parameter_kw(args, ga))
     ps = env.physical_system
     if args.rollout:
         return rollout_loop(args, env)

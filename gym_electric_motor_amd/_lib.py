@@ -232,6 +232,7 @@ EXPORTS = (
     "gemx_refprofile_create", "gemx_refprofile_destroy", "gemx_refprofile_reset", "gemx_refprofile_step", "gemx_refprofile_rollout",
     "gemx_refprofile_rollout_shell", "gemx_refprofile_get_state", "gemx_refprofile_state_bytes", "gemx_refprofile_get_blob", "gemx_refprofile_set_blob",
     "gemx_returns_rows",
+    "gemx_set_env_params", "gemx_clear_env_params", "gemx_get_env_params", "gemx_env_params_fields",
 )
 
 
@@ -329,6 +330,10 @@ def load():
     L.gemx_refprofile_set_blob.argtypes = [vp, vp, vp]
     L.gemx_returns_rows.argtypes = [C.POINTER(GemxReturnsConfig), i64, i32, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.gemx_rollout_reward.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
+    L.gemx_set_env_params.argtypes = [vp, vp]
+    L.gemx_clear_env_params.argtypes = [vp]
+    L.gemx_get_env_params.argtypes = [vp, vp, vp]
+    L.gemx_env_params_fields.argtypes = [vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]
     L.gemx_get_switch_state.argtypes = [vp, vp, vp]

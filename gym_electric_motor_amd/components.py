@@ -230,6 +230,119 @@ class ScipyOdeSolver(DormandPrince5Solver):
 
 
 # ------------------------------------------------------------------------------------------------- motors
+def _matrix(rows):
+    """np.array(rows, dtype=float) whose entries may be arrays of one common shape [N] as well: -> [rows, cols], or [N, rows, cols]."""
+    shape = np.broadcast_shapes(*(np.shape(x) for row in rows for x in row))
+    return np.stack([np.stack([np.broadcast_to(np.asarray(x, dtype=float), shape) for x in row], axis=-1) for row in rows], axis=-2)
+
+
+def _scale_row(m, row, divisor):
+    """m[row] = m[row] / divisor, for [rows, cols] and [N, rows, cols] alike."""
+    m = np.array(m, dtype=float)
+    m[..., row, :] = m[..., row, :] / np.asarray(divisor, dtype=float)[..., None]
+    return m
+
+
+def _motor_kind(motor):
+    """The motor class of this package `motor` is (or is named after: the reference's own instances)."""
+    names = [c.__name__ for c in type(motor).__mro__]
+    for kind in ("DcPermanentlyExcitedMotor", "DcSeriesMotor", "DcShuntMotor", "DcExternallyExcitedMotor", "PermanentMagnetSynchronousMotor",
+                 "ExternallyExcitedSynchronousMotor", "SynchronousReluctanceMotor", "DoublyFedInductionMotor", "SquirrelCageInductionMotor"):
+        if kind in names:
+            return kind
+    raise ValueError(f"motor {type(motor).__name__} is not on the accelerated path")
+
+
+def derived_parameters(motor, mp):
+    """`mp` with the quantities a motor class derives from its parameters added (the EESM's rotor quantities referred to the stator side,
+    externally_excited_synchronous_motor.py:69-75); values may be arrays.  Returns a new dict."""
+    mp = dict(mp)
+    if _motor_kind(motor) == "ExternallyExcitedSynchronousMotor":
+        mp["r_E"] = mp["k"] ** 2 * 3 / 2 * mp["r_e"]
+        mp["l_M"] = mp["k"] * 3 / 2 * mp["l_m"]
+        mp["l_E"] = mp["k"] ** 2 * 3 / 2 * mp["l_e"]
+        mp["i_k_rs"] = 2 / 3 / mp["k"]
+        mp["sigma"] = 1 - mp["l_M"] ** 2 / (mp["l_d"] * mp["l_E"])
+    return mp
+
+
+def model_constants(motor, mp):
+    """`_model_constants` of a motor of `motor`'s class with the parameters `mp` (each class's `_update_model`, cited at its constructor).
+    The ONE derivation: the constructors call it with their own scalars, per-env parameters (env_parameters.py) with [N] arrays -- the
+    same float64 operations element for element -- and get [N, rows, cols]."""
+    kind = _motor_kind(motor)
+    if kind == "DcPermanentlyExcitedMotor":  # lines 71-75
+        return _matrix([[-mp["psi_e"], -mp["r_a"], 1.0]]) / np.asarray(mp["l_a"], dtype=float)[..., None, None]
+    if kind == "DcSeriesMotor":  # lines 68-72: features [i, omega * i, u]
+        return _matrix([[-mp["r_a"] - mp["r_e"], -mp["l_e_prime"], 1.0]]) / np.asarray(mp["l_a"] + mp["l_e"], dtype=float)[..., None, None]
+    if kind in ("DcShuntMotor", "DcExternallyExcitedMotor"):  # DcMotor._update_model, dc_motor.py:96-104: features [i_a, i_e, omega * i_e, u_a, u_e]
+        m = _matrix([[-mp["r_a"], 0, -mp["l_e_prime"], 1, 0], [0, -mp["r_e"], 0, 0, 1]])
+        return _scale_row(_scale_row(m, 0, mp["l_a"]), 1, mp["l_e"])
+    if kind == "PermanentMagnetSynchronousMotor":  # lines 107-119
+        m = _matrix([
+            [0, -mp["r_s"], 0, 1, 0, 0, mp["l_q"] * mp["p"]],
+            [-mp["psi_p"] * mp["p"], 0, -mp["r_s"], 0, 1, -mp["l_d"] * mp["p"], 0],
+            [mp["p"], 0, 0, 0, 0, 0, 0],
+        ])
+        return _scale_row(_scale_row(m, 0, mp["l_d"]), 1, mp["l_q"])
+    if kind == "SynchronousReluctanceMotor":  # lines 117-129
+        m = _matrix([
+            [0, -mp["r_s"], 0, 1, 0, 0, mp["l_q"] * mp["p"]],
+            [0, 0, -mp["r_s"], 0, 1, -mp["l_d"] * mp["p"], 0],
+            [mp["p"], 0, 0, 0, 0, 0, 0],
+        ])
+        return _scale_row(_scale_row(m, 0, mp["l_d"]), 1, mp["l_q"])
+    if kind == "ExternallyExcitedSynchronousMotor":  # lines 69-93: rotor quantities referred to the stator side (upper-case index)
+        mp = derived_parameters(motor, mp)
+        sg, ik = mp["sigma"], mp["i_k_rs"]
+        # features [omega, i_d, i_q, i_e, u_d, u_q, u_e, omega*i_d, omega*i_q, omega*i_e]
+        m = _matrix([
+            [0, -mp["r_s"] / sg, 0, mp["l_M"] * mp["r_E"] / (sg * mp["l_E"]) * ik, 1 / sg, 0, -mp["l_M"] * mp["k"] / (sg * mp["l_E"]), 0,
+             mp["l_q"] * mp["p"] / sg, 0],
+            [0, 0, -mp["r_s"], 0, 0, 1, 0, -mp["l_d"] * mp["p"], 0, -mp["p"] * mp["l_M"] * ik],
+            [0, mp["l_M"] * mp["r_s"] / (sg * mp["l_d"]), 0, -mp["r_E"] / sg * ik, -mp["l_M"] / (sg * mp["l_d"]), 0, mp["k"] / sg, 0,
+             -mp["p"] * mp["l_M"] * mp["l_q"] / (sg * mp["l_d"]), 0],
+            [mp["p"], 0, 0, 0, 0, 0, 0, 0, 0, 0],
+        ])
+        m = _scale_row(_scale_row(m, 0, mp["l_d"]), 1, mp["l_q"])
+        return _scale_row(_scale_row(m, 2, mp["l_E"]), 2, ik)
+    # the induction machines: InductionMotor._update_model, induction_motor.py:287-312
+    l_s = mp["l_m"] + mp["l_sigs"]
+    l_r = mp["l_m"] + mp["l_sigr"]
+    sigma = (l_s * l_r - mp["l_m"] ** 2) / (l_s * l_r)
+    tau_r = l_r / mp["r_r"]
+    tau_sig = sigma * l_s / (mp["r_s"] + mp["r_r"] * (mp["l_m"] ** 2) / (l_r**2))
+    k = mp["l_m"] / (sigma * l_r * l_s)
+    g = mp["l_m"] * mp["r_r"] / (sigma * l_s * l_r**2)
+    return _matrix([
+        [0, -1 / tau_sig, 0, g, 0, 0, +k * mp["p"], 1 / (sigma * l_s), 0, -k, 0],
+        [0, 0, -1 / tau_sig, 0, g, -k * mp["p"], 0, 0, 1 / (sigma * l_s), 0, -k],
+        [0, mp["l_m"] / tau_r, 0, -1 / tau_r, 0, 0, -mp["p"], 0, 0, 1, 0],
+        [0, 0, mp["l_m"] / tau_r, 0, -1 / tau_r, mp["p"], 0, 0, 0, 0, 1],
+        [mp["p"], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
+    ])
+
+
+def torque_coefficients(motor, mp):
+    """The kernels' torque coefficients (tc0, tc1[, tc2, tc3]) of a motor of `motor`'s class with the parameters `mp` (`derived_parameters`
+    applied); values may be arrays.  DFIM: + the rotor current reconstruction i_r = psi_r / l_r - l_m / l_r * i_s."""
+    kind = _motor_kind(motor)
+    if kind == "DcPermanentlyExcitedMotor":
+        return [mp["psi_e"], 0.0]
+    if kind in ("DcSeriesMotor", "DcShuntMotor", "DcExternallyExcitedMotor"):
+        return [mp["l_e_prime"], 0.0]
+    if kind == "ExternallyExcitedSynchronousMotor":
+        return [1.5 * mp["p"] * mp["l_M"] * mp["i_k_rs"], 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
+    if kind == "PermanentMagnetSynchronousMotor":
+        return [1.5 * mp["p"] * mp["psi_p"], 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
+    if kind == "SynchronousReluctanceMotor":
+        return [0.0, 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
+    if kind == "DoublyFedInductionMotor":
+        l_r = mp["l_m"] + mp["l_sigr"]
+        return [1.5 * mp["p"] * mp["l_m"] / l_r, 0.0, 1 / l_r, mp["l_m"] / l_r]
+    return [1.5 * mp["p"] * mp["l_m"] / (mp["l_m"] + mp["l_sigr"]), 0.0]
+
+
 class _ElectricMotor:
     """electric_motors/electric_motor.py:9-325 (parameter / limit / nominal bookkeeping only)."""
 
@@ -277,8 +390,7 @@ class DcPermanentlyExcitedMotor(_ElectricMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # _update_model, lines 71-75
-        self._model_constants = np.array([[-mp["psi_e"], -mp["r_a"], 1.0]]) / mp["l_a"]
+        self._model_constants = model_constants(self, mp)  # _update_model, lines 71-75
         # _update_limits, lines 95-105 + DcMotor._update_limits (dc_motor.py:153-160)
         r_a = 1 if mp["r_a"] == 0 else mp["r_a"]
         agenda = {"u": self._default_limits["u"], "i": self._limits["u"] / r_a}
@@ -311,8 +423,7 @@ class DcSeriesMotor(_ElectricMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # _update_model, lines 68-72: features [i, omega * i, u]
-        self._model_constants = np.array([[-mp["r_a"] - mp["r_e"], -mp["l_e_prime"], 1.0]]) / (mp["l_a"] + mp["l_e"])
+        self._model_constants = model_constants(self, mp)  # _update_model, lines 68-72
         # _update_limits, lines 89-99 + DcMotor._update_limits (dc_motor.py:153-160)
         r_a = 1 if mp["r_a"] == 0 else mp["r_a"]
         agenda = {"u": self._default_limits["u"], "i": self._limits["u"] / (r_a + mp["r_e"])}
@@ -344,10 +455,7 @@ class DcShuntMotor(_ElectricMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # DcMotor._update_model, dc_motor.py:96-104: features [i_a, i_e, omega * i_e, u_a, u_e]
-        self._model_constants = np.array([[-mp["r_a"], 0, -mp["l_e_prime"], 1, 0], [0, -mp["r_e"], 0, 0, 1]], dtype=float)
-        self._model_constants[0] = self._model_constants[0] / mp["l_a"]
-        self._model_constants[1] = self._model_constants[1] / mp["l_e"]
+        self._model_constants = model_constants(self, mp)  # DcMotor._update_model, dc_motor.py:96-104
         # _update_limits, dc_shunt_motor.py:137-150 + dc_motor.py:153-160
         r_a = 1 if mp["r_a"] == 0 else mp["r_a"]
         agenda = {"u": self._default_limits["u"], "i_a": self._limits.get("i", None) or self._limits["u"] / r_a,
@@ -384,10 +492,7 @@ class DcExternallyExcitedMotor(_ElectricMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # DcMotor._update_model, dc_motor.py:96-104: features [i_a, i_e, omega * i_e, u_a, u_e]
-        self._model_constants = np.array([[-mp["r_a"], 0, -mp["l_e_prime"], 1, 0], [0, -mp["r_e"], 0, 0, 1]], dtype=float)
-        self._model_constants[0] = self._model_constants[0] / mp["l_a"]
-        self._model_constants[1] = self._model_constants[1] / mp["l_e"]
+        self._model_constants = model_constants(self, mp)  # DcMotor._update_model, dc_motor.py:96-104
         # _update_limits, dc_externally_excited_motor.py:107-120 + dc_motor.py:153-160
         r_a = 1 if mp["r_a"] == 0 else mp["r_a"]
         agenda = {"u_a": self._default_limits["u"], "u_e": self._default_limits["u"],
@@ -458,15 +563,7 @@ class PermanentMagnetSynchronousMotor(_ThreePhaseMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # _update_model, lines 107-119
-        m = np.array([
-            [0, -mp["r_s"], 0, 1, 0, 0, mp["l_q"] * mp["p"]],
-            [-mp["psi_p"] * mp["p"], 0, -mp["r_s"], 0, 1, -mp["l_d"] * mp["p"], 0],
-            [mp["p"], 0, 0, 0, 0, 0, 0],
-        ], dtype=float)
-        m[0] = m[0] / mp["l_d"]
-        m[1] = m[1] / mp["l_q"]
-        self._model_constants = m
+        self._model_constants = model_constants(self, mp)  # _update_model, lines 107-119
         self._three_phase_limits()
 
     def torque(self, currents):
@@ -508,6 +605,7 @@ class ExternallyExcitedSynchronousMotor(_ThreePhaseMotor):
     IO_CURRENTS = ["i_a", "i_b", "i_c", "i_sd", "i_sq", "i_e"]
     _default_motor_parameter = {"p": 3, "l_d": 1.66e-3, "l_q": 0.35e-3, "l_m": 1.589e-3, "l_e": 1.74e-3, "j_rotor": 0.3883,
                                 "r_s": 15.55e-3, "r_e": 7.2e-3, "k": 65.21}
+    DERIVED_PARAMETERS = ("r_E", "l_M", "l_E", "i_k_rs", "sigma")  # motor_parameter entries `derived_parameters` adds
     _default_limits = dict(omega=12e3 * np.pi / 30, torque=0.0, i=150, i_e=150, epsilon=math.pi, u=320)
     _default_nominal_values = dict(omega=4.3e3 * np.pi / 30, torque=0.0, i=120, i_e=150, epsilon=math.pi, u=320)
     # dict order i_sq, i_sd, i_e, epsilon as in the reference (line 45): reset() fills the ODE slots
@@ -518,26 +616,8 @@ class ExternallyExcitedSynchronousMotor(_ThreePhaseMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # _update_model, lines 69-93: rotor quantities referred to the stator side (upper-case index)
-        mp["r_E"] = mp["k"] ** 2 * 3 / 2 * mp["r_e"]
-        mp["l_M"] = mp["k"] * 3 / 2 * mp["l_m"]
-        mp["l_E"] = mp["k"] ** 2 * 3 / 2 * mp["l_e"]
-        mp["i_k_rs"] = 2 / 3 / mp["k"]
-        mp["sigma"] = 1 - mp["l_M"] ** 2 / (mp["l_d"] * mp["l_E"])
-        sg, ik = mp["sigma"], mp["i_k_rs"]
-        # features [omega, i_d, i_q, i_e, u_d, u_q, u_e, omega*i_d, omega*i_q, omega*i_e]
-        m = np.array([
-            [0, -mp["r_s"] / sg, 0, mp["l_M"] * mp["r_E"] / (sg * mp["l_E"]) * ik, 1 / sg, 0, -mp["l_M"] * mp["k"] / (sg * mp["l_E"]), 0,
-             mp["l_q"] * mp["p"] / sg, 0],
-            [0, 0, -mp["r_s"], 0, 0, 1, 0, -mp["l_d"] * mp["p"], 0, -mp["p"] * mp["l_M"] * ik],
-            [0, mp["l_M"] * mp["r_s"] / (sg * mp["l_d"]), 0, -mp["r_E"] / sg * ik, -mp["l_M"] / (sg * mp["l_d"]), 0, mp["k"] / sg, 0,
-             -mp["p"] * mp["l_M"] * mp["l_q"] / (sg * mp["l_d"]), 0],
-            [mp["p"], 0, 0, 0, 0, 0, 0, 0, 0, 0],
-        ], dtype=float)
-        m[0] = m[0] / mp["l_d"]
-        m[1] = m[1] / mp["l_q"]
-        m[2] = m[2] / mp["l_E"] / ik
-        self._model_constants = m
+        mp.update(derived_parameters(self, mp))  # _update_model, lines 69-93: rotor quantities referred to the stator side (upper-case index)
+        self._model_constants = model_constants(self, mp)
         self._three_phase_limits()
 
     def torque(self, currents):
@@ -582,15 +662,7 @@ class SynchronousReluctanceMotor(_ThreePhaseMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # _update_model, lines 117-129
-        m = np.array([
-            [0, -mp["r_s"], 0, 1, 0, 0, mp["l_q"] * mp["p"]],
-            [0, 0, -mp["r_s"], 0, 1, -mp["l_d"] * mp["p"], 0],
-            [mp["p"], 0, 0, 0, 0, 0, 0],
-        ], dtype=float)
-        m[0] = m[0] / mp["l_d"]
-        m[1] = m[1] / mp["l_q"]
-        self._model_constants = m
+        self._model_constants = model_constants(self, mp)  # _update_model, lines 117-129
         self._three_phase_limits()
 
     def torque(self, currents):
@@ -629,21 +701,7 @@ class SquirrelCageInductionMotor(_ThreePhaseMotor):
     def __init__(self, motor_parameter=None, nominal_values=None, limit_values=None, motor_initializer=None):
         super().__init__(motor_parameter, nominal_values, limit_values, motor_initializer)
         mp = self._motor_parameter
-        # InductionMotor._update_model, induction_motor.py:287-312
-        l_s = mp["l_m"] + mp["l_sigs"]
-        l_r = mp["l_m"] + mp["l_sigr"]
-        sigma = (l_s * l_r - mp["l_m"] ** 2) / (l_s * l_r)
-        tau_r = l_r / mp["r_r"]
-        tau_sig = sigma * l_s / (mp["r_s"] + mp["r_r"] * (mp["l_m"] ** 2) / (l_r**2))
-        k = mp["l_m"] / (sigma * l_r * l_s)
-        g = mp["l_m"] * mp["r_r"] / (sigma * l_s * l_r**2)
-        self._model_constants = np.array([
-            [0, -1 / tau_sig, 0, g, 0, 0, +k * mp["p"], 1 / (sigma * l_s), 0, -k, 0],
-            [0, 0, -1 / tau_sig, 0, g, -k * mp["p"], 0, 0, 1 / (sigma * l_s), 0, -k],
-            [0, mp["l_m"] / tau_r, 0, -1 / tau_r, 0, 0, -mp["p"], 0, 0, 1, 0],
-            [0, 0, mp["l_m"] / tau_r, 0, -1 / tau_r, mp["p"], 0, 0, 0, 0, 1],
-            [mp["p"], 0, 0, 0, 0, 0, 0, 0, 0, 0, 0],
-        ], dtype=float)
+        self._model_constants = model_constants(self, mp)  # InductionMotor._update_model, induction_motor.py:287-312
         self._three_phase_limits()
 
     def _torque_limit(self):

@@ -6,12 +6,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <set>
 #include <string>
+#include <vector>
 
 #include "gemx_common.hpp"
+#include "gemx_envparams.hpp"
 
 namespace gemx {
 
@@ -218,22 +221,42 @@ static int pack_model(const gemx_config &c, double *m, double *pole) {
     return GEMX_OK;
 }
 
+// The DevParams members that depend on machine, load and supply, in double, from the quantities gemx_config carries: ONE place for
+// fill_params (a handle's own parameters) and gemx_set_env_params (a table column per env), each of which rounds to R once.
+// The order of the tail is the table's (gemx_envparams.hpp).
+struct MachineParams {
+    double m[20], tc[4], inv_j, la, lb, lc, omega_lim, lin_factor, inv_tau_decay, u_sup;
+};
+static void derive_machine_params(const double *m, int n_m, const double *torque_coef, double j_total, double load_a, double load_b, double load_c,
+                                  double tau_decay, double u_nominal, MachineParams &M) {
+    for (int i = 0; i < 20; ++i) M.m[i] = i < n_m ? m[i] : 0.0;
+    for (int i = 0; i < 4; ++i) M.tc[i] = torque_coef[i];
+    M.inv_j = j_total > 0 ? 1.0 / j_total : 0.0;
+    M.la = load_a; M.lb = load_b; M.lc = load_c;
+    // PolynomialStaticLoad.set_j_rotor, polynomial_static_load.py:62-66
+    M.omega_lim = j_total > 0 ? load_a / j_total * tau_decay : 0.0;
+    M.lin_factor = tau_decay > 0 ? j_total / tau_decay : 0.0;
+    M.inv_tau_decay = tau_decay > 0 ? 1.0 / tau_decay : 0.0;
+    M.u_sup = u_nominal;
+}
+
 template <class R> static void fill_params(const gemx_handle &h, const double *m, double pole, DevParams<R> &P) {
     const gemx_config &c = h.cfg;
     memset(&P, 0, sizeof(P));
-    for (int i = 0; i < 20; ++i) P.m[i] = (R)m[i];
-    P.tc0 = (R)c.torque_coef[0];
-    P.tc1 = (R)c.torque_coef[1];
-    P.tc2 = (R)c.torque_coef[2];
-    P.tc3 = (R)c.torque_coef[3];
+    MachineParams M;
+    derive_machine_params(m, 20, c.torque_coef, c.j_total, c.load_a, c.load_b, c.load_c, c.tau_decay, c.u_nominal, M);
+    for (int i = 0; i < 20; ++i) P.m[i] = (R)M.m[i];
+    P.tc0 = (R)M.tc[0];
+    P.tc1 = (R)M.tc[1];
+    P.tc2 = (R)M.tc[2];
+    P.tc3 = (R)M.tc[3];
     P.pole = (R)pole;
-    P.inv_j = (R)(c.j_total > 0 ? 1.0 / c.j_total : 0.0);
-    P.la = (R)c.load_a; P.lb = (R)c.load_b; P.lc = (R)c.load_c;
-    // PolynomialStaticLoad.set_j_rotor, polynomial_static_load.py:62-66
-    P.omega_lim = (R)(c.j_total > 0 ? c.load_a / c.j_total * c.tau_decay : 0.0);
-    P.lin_factor = (R)(c.tau_decay > 0 ? c.j_total / c.tau_decay : 0.0);
-    P.inv_tau_decay = (R)(c.tau_decay > 0 ? 1.0 / c.tau_decay : 0.0);
-    P.u_sup = (R)c.u_nominal;
+    P.inv_j = (R)M.inv_j;
+    P.la = (R)M.la; P.lb = (R)M.lb; P.lc = (R)M.lc;
+    P.omega_lim = (R)M.omega_lim;
+    P.lin_factor = (R)M.lin_factor;
+    P.inv_tau_decay = (R)M.inv_tau_decay;
+    P.u_sup = (R)M.u_sup;
     P.il_ratio = (R)(c.interlocking_time / c.tau);
     P.tau = (R)c.tau;
     P.t_il = (R)c.interlocking_time;
@@ -498,6 +521,19 @@ static void cov_note_launch(const gemx_handle *h, bool linmap_built) {
 }
 
 static int launch_advance(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st) {
+    if (h->envp != nullptr) {  // per-env parameters (gemx_set_env_params): the two kernels of the handle's per-env unit serve every launch
+        if (h->cur_synth) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_synthetic is not available on a handle with a parameter table (gemx_synthetic_actions + gemx_rollout)");
+        if (h->cur_half) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_half is not available on a handle with a parameter table (fp32 actions)");
+        if (!obs_every) return fail(GEMX_ERR_ARG, "per-env parameters: last-step-only launches (obs_every = 0) are not available on a handle with a parameter table");
+        if (h->ep_launch == nullptr) return fail(GEMX_ERR_ARG, "internal: the handle's per-env parameter unit is not loaded");
+        const int rc = ((gemx_ep_unit_launch_fn)h->ep_launch)(h, actions, K, obs, done, st);
+        if (rc != GEMX_OK) return rc;
+        h->steps_total += (unsigned long long)K;
+        char key[256];
+        snprintf(key, sizeof(key), "%s<%d, %d, %d, %d, float>", h->ll.pipe == EP_LAUNCH_STEP ? "envparams_step_kernel" : "envparams_rollout_kernel", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver);
+        gemx_cov_note(key);
+        return GEMX_OK;
+    }
     if (h->unit_launch == nullptr) return fail(GEMX_ERR_ARG, "internal: the handle's kernel unit is not loaded");
     const int lin_before = h->linmap_state;
     const int rc = ((gemx_unit_launch_fn)h->unit_launch)(h, actions, K, obs, done, obs_every, st);
@@ -818,6 +854,7 @@ int gemx_destroy(gemx_handle *h) {
     if (h->fifo_phase) (void)hipFree(h->fifo_phase);
     if (h->reset_obs_dev) (void)hipFree(h->reset_obs_dev);
     if (h->cw_dev) (void)hipFree(h->cw_dev);
+    if (h->envp) (void)hipFree(h->envp);
     if (h->pcal.ev_init)
         for (int i = 0; i < gemx_handle::PaceCal::RING; ++i) {
             if (h->pcal.ev0[i]) (void)hipEventDestroy((hipEvent_t)h->pcal.ev0[i]);
@@ -1125,10 +1162,149 @@ int gemx_set_switch_state(gemx_handle *h, const uint8_t *in_dev, void *stream) {
     HIP_TRY(hipMemcpyAsync(h->sw, in_dev, (size_t)h->n * h->sw_rows, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return GEMX_OK;
 }
+// ---- per-env motor / load / supply parameters (include/gemx.h; gemx_envparams.hpp, gemx_envparams.hip) ------------------------------------
+// the per-env units, libgemx_ep<S>_<C>.so beside this library: loaded like the stepping units, by the first gemx_set_env_params that needs one
+typedef int (*gemx_ep_unit_init_fn)(unsigned long long handle_bytes, int abi, void (*set_error)(const char *));
+struct EpUnitLib { void *dl = nullptr; gemx_ep_unit_launch_fn launch = nullptr; };
+static EpUnitLib g_ep_units[8][12];
+static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) {
+    if (s < 0 || s >= 8 || c < 0 || c >= 12) return fail(GEMX_ERR_ARG, "per-env parameters: unsupported system/converter combination %d/%d", s, c);
+    std::lock_guard<std::mutex> lock(g_units_mu);
+    EpUnitLib &u = g_ep_units[s][c];
+    if (u.launch == nullptr) {
+        char dir[1024] = "";
+        const char *ud = getenv("GEMX_UNIT_DIR");
+        if (ud != nullptr && ud[0] != 0) snprintf(dir, sizeof(dir), "%s", ud);
+        else {
+            Dl_info info;
+            if (dladdr((const void *)&gemx_abi_version, &info) == 0 || info.dli_fname == nullptr) return fail(GEMX_ERR_DEVICE, "dladdr failed: cannot locate libgemx.so's directory");
+            snprintf(dir, sizeof(dir), "%s", info.dli_fname);
+            char *slash = strrchr(dir, '/');
+            if (slash != nullptr) *slash = 0;
+            else snprintf(dir, sizeof(dir), ".");
+        }
+        char path[1200];
+        snprintf(path, sizeof(path), "%s/libgemx_ep%d_%d.so", dir, s, c);
+        void *dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
+        if (dl == nullptr) {
+            const char *e = dlerror();
+            return fail(GEMX_ERR_ARG, "per-env parameter unit %s cannot be loaded (%s): the package's build is incomplete (python -m gym_electric_motor_amd.build)", path, e ? e : "?");
+        }
+        auto init = (gemx_ep_unit_init_fn)dlsym(dl, "gemx_ep_unit_init");
+        auto launch = (gemx_ep_unit_launch_fn)dlsym(dl, "gemx_ep_unit_launch");
+        if (init == nullptr || launch == nullptr) { dlclose(dl); return fail(GEMX_ERR_ARG, "%s exports no gemx_ep_unit_init / gemx_ep_unit_launch", path); }
+        if (init((unsigned long long)sizeof(gemx_handle), GEMX_ABI_VERSION, unit_set_error) != GEMX_OK) {
+            dlclose(dl);
+            return fail(GEMX_ERR_ARG, "%s was built from other sources than libgemx.so (handle layout / ABI differ): rebuild the package", path);
+        }
+        u.dl = dl;
+        u.launch = launch;
+    }
+    *out = u.launch;
+    return GEMX_OK;
+}
+
+int gemx_env_params_fields(const gemx_handle *h) { return h ? ep_fields(h->cfg.system_kind) : GEMX_ERR_ARG; }
+
+int gemx_set_env_params(gemx_handle *h, const gemx_env_params *p) {
+    if (!h || !p) return fail(GEMX_ERR_ARG, "null argument");
+    if (p->struct_size != (int32_t)sizeof(gemx_env_params)) return fail(GEMX_ERR_ARG, "gemx_env_params size mismatch");
+    const gemx_config &c = h->cfg;
+    // what the per-env kernels do not serve: refused here, before anything is launched or changed
+    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "per-env parameters: fp32 handles only (the fp64 build is a diagnostic of one parameter set)");
+    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "per-env parameters: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver");
+    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "per-env parameters: solver kind %d is not built; EulerSolver or RK4Solver", c.solver_kind);
+    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "per-env parameters: a converter interlocking time (dead time) is not available");
+    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "per-env parameters: a DeadTimeProcessor (action_delay > 0) is not available");
+    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "per-env parameters: an RCVoltageSupply is not available (IdealVoltageSupply with a per-env u_nominal)");
+    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "per-env parameters: random initial states are not available (initial states are one per handle)");
+    if (p->n_envs != h->n) return fail(GEMX_ERR_ARG, "per-env parameters: the arrays hold %lld envs, the handle %lld", (long long)p->n_envs, (long long)h->n);
+    const int64_t N = h->n;
+    const int nm = ep_model_entries(c.system_kind), F = ep_fields(c.system_kind);
+    double m0[20] = {0}, pole0 = 0;
+    if (pack_model(c, m0, &pole0) != GEMX_OK) return GEMX_ERR_ARG;
+    // validation: every value finite, j_total > 0, the model inside the system's sparsity pattern with the handle's pole pair number
+    auto finite_all = [&](const double *a, int64_t n, const char *name) {
+        if (a == nullptr) return true;
+        for (int64_t i = 0; i < n; ++i)
+            if (!std::isfinite(a[i])) { fail(GEMX_ERR_ARG, "per-env parameters: %s[%lld] is not finite", name, (long long)i); return false; }
+        return true;
+    };
+    if (!finite_all(p->model, N * GEMX_MODEL_ROWS * GEMX_MODEL_COLS, "model") || !finite_all(p->torque_coef, N * 4, "torque_coef") ||
+        !finite_all(p->j_total, N, "j_total") || !finite_all(p->load_a, N, "load_a") || !finite_all(p->load_b, N, "load_b") ||
+        !finite_all(p->load_c, N, "load_c") || !finite_all(p->u_nominal, N, "u_nominal"))
+        return GEMX_ERR_ARG;
+    if (p->j_total != nullptr)
+        for (int64_t e = 0; e < N; ++e)
+            if (!(p->j_total[e] > 0.0)) return fail(GEMX_ERR_ARG, "per-env parameters: j_total[%lld] = %g must be positive", (long long)e, p->j_total[e]);
+    std::unique_ptr<float[]> tab(new (std::nothrow) float[(size_t)F * (size_t)N]);  // (nothrow: no exception may cross the C ABI)
+    if (!tab) return fail(GEMX_ERR_ALLOC, "per-env parameters: host staging of %lld x %d values failed", (long long)N, F);
+    gemx_config ce = c;  // (pack_model reads a gemx_config: env e's matrix in a copy of the handle's)
+    for (int64_t e = 0; e < N; ++e) {
+        double m[20] = {0}, pole = pole0;
+        if (p->model != nullptr) {
+            memcpy(ce.model, p->model + e * GEMX_MODEL_ROWS * GEMX_MODEL_COLS, sizeof(ce.model));
+            if (pack_model(ce, m, &pole) != GEMX_OK) {
+                char inner[400];
+                snprintf(inner, sizeof(inner), "%s", g_err);
+                return fail(GEMX_ERR_ARG, "per-env parameters: env %lld: %s", (long long)e, inner);
+            }
+            if (pole != pole0) return fail(GEMX_ERR_ARG, "per-env parameters: env %lld has pole pair entry %g, the handle %g: p is one value per handle", (long long)e, pole, pole0);
+        } else {
+            memcpy(m, m0, sizeof(m));
+        }
+        MachineParams M;
+        derive_machine_params(m, nm, p->torque_coef != nullptr ? p->torque_coef + 4 * e : c.torque_coef, p->j_total != nullptr ? p->j_total[e] : c.j_total,
+                              p->load_a != nullptr ? p->load_a[e] : c.load_a, p->load_b != nullptr ? p->load_b[e] : c.load_b,
+                              p->load_c != nullptr ? p->load_c[e] : c.load_c, c.tau_decay, p->u_nominal != nullptr ? p->u_nominal[e] : c.u_nominal, M);
+        const double tail[EP_TAIL] = {M.tc[0], M.tc[1], M.tc[2], M.tc[3], M.inv_j, M.la, M.lb, M.lc, M.omega_lim, M.lin_factor, M.inv_tau_decay, M.u_sup};
+        for (int i = 0; i < nm; ++i) tab[(size_t)i * N + e] = (float)M.m[i];
+        for (int i = 0; i < EP_TAIL; ++i) tab[(size_t)(nm + i) * N + e] = (float)tail[i];
+    }
+    gemx::DeviceGuard guard(h->device);
+    gemx_ep_unit_launch_fn fn = nullptr;
+    const int rc = load_ep_unit(c.system_kind, h->conv_unit, &fn);
+    if (rc != GEMX_OK) return rc;
+    void *dev = h->envp;
+    if (dev == nullptr && hipMalloc(&dev, sizeof(float) * (size_t)F * (size_t)N) != hipSuccess) return fail(GEMX_ERR_ALLOC, "hipMalloc(per-env parameter table) failed");
+    // (synchronous, from pageable memory: launches already enqueued on other streams are the caller's to order, as with gemx_set_state)
+    if (hipMemcpy(dev, tab.get(), sizeof(float) * (size_t)F * (size_t)N, hipMemcpyHostToDevice) != hipSuccess) {
+        if (h->envp == nullptr) (void)hipFree(dev);
+        return fail(GEMX_ERR_DEVICE, "hipMemcpy(per-env parameter table) failed");
+    }
+    h->envp = dev;
+    h->envp_fields = F;
+    h->ep_launch = (void *)fn;
+    return GEMX_OK;
+}
+
+int gemx_clear_env_params(gemx_handle *h) {
+    if (!h) return fail(GEMX_ERR_ARG, "null handle");
+    if (h->envp != nullptr) {
+        gemx::DeviceGuard guard(h->device);
+        HIP_TRY(hipDeviceSynchronize());  // (launches that still read the table)
+        (void)hipFree(h->envp);
+    }
+    h->envp = nullptr;
+    h->envp_fields = 0;
+    return GEMX_OK;
+}
+
+int gemx_get_env_params(gemx_handle *h, void *out_dev, void *stream) {
+    if (!h || !out_dev) return fail(GEMX_ERR_ARG, "null argument");
+    if (h->envp == nullptr) return fail(GEMX_ERR_ARG, "per-env parameters: the handle has no parameter table (gemx_set_env_params)");
+    gemx::DeviceGuard guard(h->device);
+    HIP_TRY(hipMemcpyAsync(out_dev, h->envp, sizeof(float) * (size_t)h->envp_fields * (size_t)h->n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return GEMX_OK;
+}
+
 const char *gemx_last_launch(const gemx_handle *h) {
     if (!h) return "";
     const auto &l = h->ll;
-    if (l.pipe == 3)
+    if (l.pipe == EP_LAUNCH_STEP || l.pipe == EP_LAUNCH_ROLLOUT)
+        snprintf(h->last_launch, sizeof(h->last_launch), "gemx::%s<sys=%d,conv=%d,load=%d,solver=%d,f32> grid=%lld x %d threads, K=%d, per-env parameters (%d fields)",
+                 l.pipe == EP_LAUNCH_STEP ? "envparams_step_kernel" : "envparams_rollout_kernel", l.sys, l.conv, l.load, l.solver, l.blocks, l.threads, l.k, h->envp_fields);
+    else if (l.pipe == 3)
         snprintf(h->last_launch, sizeof(h->last_launch),
                  "gemx::dc_stream_kernel<sys=%d,conv=%d,solver=%d,f32,D=%d> grid=%lld x %d threads, lds=%zu B, K=%d", l.sys, l.conv, l.solver, l.d,
                  l.blocks, l.threads, l.lds, l.k);

@@ -669,6 +669,11 @@ struct gemx_handle {
     bool warned_fallback = false;  // the one-time note that fused rollouts of this handle take the single-wave kernel has been printed
     bool omega_is_init = true;  // every env's omega equals init[0] (constant-speed loads): false between gemx_set_state and the next full reset
     bool omega_unknown = false; // a state-changing call was CAPTURED into a graph: the host cannot know when it runs -> omega_is_init stays false
+    // per-env motor / load / supply parameters (gemx_set_env_params; gemx_envparams.hpp): the table [envp_fields][n] R on the device, nullptr
+    // without one, and gemx_ep_unit_launch of libgemx_ep<system>_<conv_unit>.so, which serves step / rollout while a table is set
+    void *envp = nullptr;
+    int envp_fields = 0;
+    void *ep_launch = nullptr;
 };
 
 namespace gemx {

@@ -158,6 +158,8 @@ def make_sharded(env_id, n_envs_total, rank, world, device, **kwargs):
     holder = as_profile_holder(kwargs.get("reference_generator"))
     if holder is not None:  # a per-env table [T, n_envs_total, n_ref] is cut to this shard's envs; the start rows are keyed by env_base
         kwargs["reference_generator"] = holder.shard(lo, hi, n_envs_total)
+    if kwargs.get("env_parameters") is not None:  # per-env parameter arrays [n_envs_total] are cut to this shard's envs by global index
+        kwargs["env_parameters"] = kwargs["env_parameters"].shard(lo, hi, n_envs_total)
     env = make(env_id, n_envs=hi - lo, device=device, **kwargs)
     env.shard = (lo, hi)
     env.n_envs_total = n_envs_total

@@ -280,6 +280,13 @@ class BatchedElectricMotorEnv:
                                                    reward_config=_reward_config, episode=episodes, episode_reward=_episode_reward)
         self.episodes = pipe.episode
         self.observation_stage, self.flux, self.flux_action, self._flux_only = pipe.stage, pipe.flux, pipe.flux_action, pipe.flux_only
+        if pipe.flux is not None:  # the observer holds ONE machine's parameters: the system refuses a table now and later (set_env_parameters)
+            from .env_parameters import REFUSAL as EP_REFUSAL
+
+            why = EP_REFUSAL + "a FluxObserver or a FluxOrientedDqToAbcActionProcessor (the observer holds one machine's parameters)"
+            if getattr(physical_system, "env_parameters", None) is not None:
+                raise NotImplementedError(why)
+            physical_system._env_parameters_refusal = why
         self.state_noise = pipe.noise
         self.action_space = pipe.action_space
         self.state_space = physical_system.state_space if pipe.stage is None else pipe.stage.observation_space
@@ -738,7 +745,9 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
     generators, and the generator built from holders, like every other device random stream.  Both None: the physics-only env.
     max_episode_steps: None | int >= 1 -- gymnasium's TimeLimit on the device: `step()` returns `truncated` [N], truncated envs restart in
     front of the next step; episode_statistics: `env.episode_statistics()` hands out per-env episode length and return counters
-    (episodes.py).  Both off: nothing is built and nothing more is launched."""
+    (episodes.py).  Both off: nothing is built and nothing more is launched.
+    env_parameters (through **kwargs to the system): None | EnvParameters(motor=, load=, supply=) -- per-env motor, load and supply parameters
+    (env_parameters.py): every env steps with its own machine, everything behind the physics runs unchanged."""
     from .episodes import check_max_episode_steps
     from .physical_system_wrappers import fold_wrappers
 
@@ -759,6 +768,10 @@ def make(env_id, n_envs=1, device=0, supply=None, converter=None, motor=None, lo
         flux_action = folded.pop("flux_action", None)  # (served by the flux-observer stage, not by the system's action stage)
         state_noise = folded.pop("state_noise", None)  # (served by the state-noise stage behind the physics)
         kwargs = dict(kwargs, **folded)
+    if kwargs.get("env_parameters") is not None and (flux_action is not None or any(spec[0] == "flux" for spec in chain)):
+        from .env_parameters import REFUSAL as EP_REFUSAL
+
+        raise NotImplementedError(EP_REFUSAL + "a FluxObserver or a FluxOrientedDqToAbcActionProcessor (the observer holds one machine's parameters)")
     if state_noise is not None and obs_layout != "aos":
         from .state_noise import REFUSAL
 

@@ -100,7 +100,7 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
 
     def __init__(self, converter, motor, load, supply, ode_solver, tau=1e-4, calc_jacobian=None, n_envs=1, device=0,
                  dtype="float32", constraints=(), auto_reset=None, obs_layout="aos", control_space="abc", action_frame=None,
-                 action_delay=0, action_delay_reset=None, seed=0, env_base=0, _defer_create=False):
+                 action_delay=0, action_delay_reset=None, seed=0, env_base=0, env_parameters=None, _defer_create=False):
         """
         Args (first six as in SCMLSystem.__init__, physical_systems.py:54-65):
             converter, motor, load, supply: component instances (this package's or the reference's).
@@ -129,6 +129,8 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
                 one job (`distributed.make_sharded` sets env_base to the shard's first env) draw, env by env, what one unsharded
                 system draws -- the reference gives every env object its own branch of the seed sequence (core.py:373-385,
                 physical_systems.py:164-169, random_component.py:60-87).
+            env_parameters: None | EnvParameters(motor=, load=, supply=) -- per-env motor, load and supply parameters (env_parameters.py):
+                every env steps with its own machine; limits, initial state, p, tau, constraints and solver stay the system's own.
         """
         if control_space not in ("abc", "dq"):
             raise ValueError(f"control_space must be 'abc' or 'dq', got {control_space!r}")
@@ -184,6 +186,9 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         self._auto_reset = bool(auto_reset)
         self._cfg = self._build_config(limit_mask, squared_mask)
         self._handle = None
+        self._env_parameters = self._env_parameter_arrays = None
+        if env_parameters is not None:
+            self.set_env_parameters(env_parameters)
         if not _defer_create:  # (_defer_create: host-side config only, used by the CPU unit tests)
             self._create()
 
@@ -223,6 +228,65 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
 
     def _set_indices(self):
         raise NotImplementedError
+
+    # ------------------------------------------------------------------ per-env parameters (env_parameters.py)
+    env_parameters = property(lambda self: self._env_parameters, doc="the EnvParameters holder of this system, or None")
+
+    def set_env_parameters(self, env_parameters):
+        """Give every env its own motor, load and supply parameters (`EnvParameters`), or replace them.  Everything is checked -- what the
+        per-env kernels do not serve, lengths, finiteness, j_total > 0, p -- before the handle changes."""
+        from . import env_parameters as ep
+
+        if not isinstance(env_parameters, ep.EnvParameters):
+            raise ValueError("env_parameters: an EnvParameters(motor=, load=, supply=) holder")
+        why = getattr(self, "_env_parameters_refusal", None) or ep.refusal(self)  # (the first: set by an env that runs a FluxObserver on this system)
+        if why is not None:
+            raise NotImplementedError(why)
+        arrays = env_parameters.resolve(self)
+        if self._handle is not None:
+            ep.install(self, arrays)
+        self._env_parameters, self._env_parameter_arrays = env_parameters, arrays
+
+    def clear_env_parameters(self):
+        """Back to one parameter set for every env: the system's own (`gemx_clear_env_params`)."""
+        if self._handle is not None:
+            _lib.check(self._L.gemx_clear_env_params(self._handle))
+        self._env_parameters = self._env_parameter_arrays = None
+
+    def get_env_parameter_table(self):
+        """The device table [F, N] as it sits on the device (`gemx_get_env_params`; field order: include/gemx.h), or None without one."""
+        if self._env_parameters is None:
+            return None
+        from .env_parameters import table_fields
+
+        out = _torch().empty((table_fields(self._SYSTEM_KIND), self._n_envs), dtype=self._tdtype, device=self._tdev)
+        _lib.check(self._L.gemx_get_env_params(self._handle, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def _refuse_with_env_parameters(self, what):
+        if self._env_parameters is not None:
+            from .env_parameters import REFUSAL
+
+            raise NotImplementedError(REFUSAL + what)
+
+    def _check_env_parameters_checkpoint(self, ckpt):
+        """The checkpoint's table and this system's agree in presence, shape and, on a created system, value (before anything is restored)."""
+        from .env_parameters import table_fields
+
+        tab = ckpt.get("env_parameters")
+        if (tab is None) != (self._env_parameters is None):
+            raise ValueError("checkpoint and system disagree on per-env parameters: " +
+                             ("the checkpoint carries a parameter table, this system has none" if tab is not None else
+                              "this system has a parameter table (env_parameters=), the checkpoint carries none"))
+        if tab is not None and tuple(tab.shape) != (table_fields(self._SYSTEM_KIND), self._n_envs):
+            raise ValueError(f"checkpoint per-env parameter table has shape {tuple(tab.shape)}, this system's is "
+                             f"{(table_fields(self._SYSTEM_KIND), self._n_envs)}: it was taken from a system of another n_envs or motor")
+        if tab is not None and self._handle is not None:  # the same machines, value for value: a run continues only on the parameters it ran on
+            torch = _torch()
+            own = self.get_env_parameter_table()
+            if not torch.equal(torch.as_tensor(tab).to(device=own.device, dtype=own.dtype), own):
+                raise ValueError("checkpoint per-env parameter table differs in value from this system's: the checkpoint was taken with other "
+                                 "per-env parameters (build the system with the env_parameters= of the run it continues)")
 
     # ------------------------------------------------------------------ config extraction
     def _constraint_masks(self, constraints):
@@ -337,24 +401,10 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         raise ValueError(f"load {type(ld).__name__} is not on the accelerated path (supported: ConstantSpeedLoad, PolynomialStaticLoad)")
 
     def _torque_coefficients(self):
+        from . import components as comp
+
         m = self._electrical_motor
-        mp = m.motor_parameter
-        if _is_a(m, "DcPermanentlyExcitedMotor"):
-            return [mp["psi_e"], 0.0]
-        if _is_a(m, "DcSeriesMotor", "DcShuntMotor", "DcExternallyExcitedMotor"):
-            return [mp["l_e_prime"], 0.0]
-        if _is_a(m, "ExternallyExcitedSynchronousMotor"):
-            return [1.5 * mp["p"] * mp["l_M"] * mp["i_k_rs"], 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
-        if _is_a(m, "PermanentMagnetSynchronousMotor"):
-            return [1.5 * mp["p"] * mp["psi_p"], 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
-        if _is_a(m, "SynchronousReluctanceMotor"):
-            return [0.0, 1.5 * mp["p"] * (mp["l_d"] - mp["l_q"])]
-        if _is_a(m, "DoublyFedInductionMotor"):  # + rotor current reconstruction i_r = psi_r / l_r - l_m / l_r * i_s
-            l_r = mp["l_m"] + mp["l_sigr"]
-            return [1.5 * mp["p"] * mp["l_m"] / l_r, 0.0, 1 / l_r, mp["l_m"] / l_r]
-        if _is_a(m, "SquirrelCageInductionMotor"):
-            return [1.5 * mp["p"] * mp["l_m"] / (mp["l_m"] + mp["l_sigr"]), 0.0]
-        raise ValueError(f"motor {type(m).__name__} is not on the accelerated path")
+        return comp.torque_coefficients(m, comp.derived_parameters(m, m.motor_parameter))
 
     def _initial_motor_state(self):
         m = self._electrical_motor
@@ -557,6 +607,10 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         self._gemx_step = L.gemx_step
         self._raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)  # the current stream's handle without a Stream object
         self._cur_stream = torch.cuda.current_stream
+        if getattr(self, "_env_parameter_arrays", None) is not None:  # (a system re-created after close() keeps its table)
+            from .env_parameters import install
+
+            install(self, self._env_parameter_arrays)
 
     def _stream(self):
         return C.c_void_p(_torch().cuda.current_stream(self._tdev).cuda_stream)
@@ -708,6 +762,8 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         K = int(actions.shape[0])
         a = actions
         half = a.dtype is torch.float16 and not self._discrete and self._tdtype == torch.float32 and K >= 2  # (narrow action tensor: gemx_rollout_half)
+        if half:
+            self._refuse_with_env_parameters("a half-precision action tensor (fp32 actions)")
         if not (a.device == self._tdev and a.is_contiguous() and (a.dtype is self._want_dtype or half) and a.numel() == K * self._act_numel):
             raise ValueError(f"bind_rollout needs a contiguous {self._want_dtype} (continuous converters, fp32: or float16) tensor of {K} x {self._act_numel} elements on {self._tdev}")
         oshape, dshape = (K,) + tuple(self._obs.shape), (K, self._n_envs)
@@ -742,7 +798,10 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         # a HALF action tensor (continuous converters, fp32 systems): taken as it is -- gemx_rollout_half widens the values while they are
         # staged (6 instead of 12 bytes per env-step for three duty cycles; the results are those of the same values fed as fp32)
         half = (torch.is_tensor(actions) and actions.dtype == torch.float16 and not self._discrete and self._tdtype == torch.float32 and not last_only)
+        if last_only:
+            self._refuse_with_env_parameters("last-step-only launches (last_only=True)")
         if half:
+            self._refuse_with_env_parameters("a half-precision action tensor (fp32 actions)")
             if not (actions.device == self._tdev and actions.is_contiguous() and actions.numel() == K * self._act_numel and K >= 2):
                 raise ValueError(f"rollout: a float16 action tensor must be a contiguous device tensor of {K} x {self._act_numel} elements on {self._tdev}, K >= 2")
             a = actions
@@ -795,6 +854,7 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         """K fused control steps on SYNTHETIC random actions generated inside the launch (no action tensor is read: include/gemx.h,
         gemx_rollout_synthetic) -- random-action rollouts of the continuous converters at large batch sizes run 15-20 % faster without
         the action stream coming from the HBM between the observation stores.  Returns (obs [K, N, S_out], done [K, N])."""
+        self._refuse_with_env_parameters("rollout_synthetic (synthetic_actions + rollout)")
         torch = _torch()
         K = int(K)
         s0 = int(self._k if step0 is None else step0) & 0xFFFFFFFF
@@ -985,10 +1045,14 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         nb = int(self._L.gemx_aux_state_bytes(self._handle))
         aux = torch.empty(nb, dtype=torch.uint8, device=self._tdev)  # (gemx_get_aux_state zeroes the sections' padding itself: equal states, equal blobs)
         _lib.check(self._L.gemx_get_aux_state(self._handle, C.c_void_p(aux.data_ptr()), self._stream()))
-        return {"state": self.get_state(), "switch_state": self.get_switch_state(), "aux": aux, "k": int(self._k)}
+        ck = {"state": self.get_state(), "switch_state": self.get_switch_state(), "aux": aux, "k": int(self._k)}
+        if self._env_parameters is not None:  # the table as the device holds it (the parameters themselves are a construction argument)
+            ck["env_parameters"] = self.get_env_parameter_table()
+        return ck
 
     def check_checkpoint(self, ckpt):
         """The size checks of `set_checkpoint`, which restore nothing -> the aux blob on this system's device."""
+        self._check_env_parameters_checkpoint(ckpt)
         torch = _torch()
         aux = torch.as_tensor(ckpt["aux"]).to(device=self._tdev, dtype=torch.uint8).contiguous()
         if aux.numel() != int(self._L.gemx_aux_state_bytes(self._handle)):

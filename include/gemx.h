@@ -736,6 +736,38 @@ int gemx_returns_rows(const gemx_returns_config *cfg, int64_t n_envs, int32_t K,
                       const void *last_value_dev, const uint8_t *terminated_dev, const uint8_t *ended_dev, const void *final_value_dev,
                       const double *carry_in_dev, double *carry_out_dev, void *advantage_out_dev, void *return_out_dev, void *stream);
 
+/* PER-ENV MOTOR, LOAD AND SUPPLY PARAMETERS: domain randomisation inside one handle (new struct and entry points only, ABI number
+ * unchanged).  gemx_set_env_params gives every env its own machine: host float64 arrays, one entry per env, of the quantities gemx_config
+ * carries per handle -- `model` as gemx_config.model ([n_envs][GEMX_MODEL_ROWS * GEMX_MODEL_COLS]), `torque_coef` ([n_envs][4]), `j_total`,
+ * `load_a`, `load_b`, `load_c`, `u_nominal` ([n_envs]).  A NULL array means the handle's own value for every env.  The library derives, with
+ * the double-precision expressions gemx_create uses for the handle's own parameters, a device table [F][n_envs] of R, field-major:
+ *     the system's structurally non-zero model entries | tc0..tc3 | 1 / j_total, a, b, c, omega_lim, lin_factor, 1 / tau_decay | u_sup
+ * (F = gemx_env_params_fields(h)), rounded to R once.  From then on gemx_step, gemx_rollout and gemx_rollout_reward run
+ * envparams_step_kernel / envparams_rollout_kernel (gemx_last_launch names them), in which lane e computes, bit for bit, what a handle
+ * created with env e's values computes.  Everything else stays one value per handle: tau, the pole pair number, the limits the
+ * observations are normalised by, the initial state (gemx_reset and the reset observation are unchanged), the constraint set, the
+ * solver, the action frame.  The one-step map of the constant-speed loads is never taken with a table (it belongs to one parameter set).
+ * GEMX_ERR_ARG, naming per-env parameters, and nothing changed, for: a NULL argument, struct_size, n_envs other than the handle's, a value
+ * that is not finite, j_total <= 0, a model entry outside the system's sparsity pattern or a pole pair entry other than the handle's; and
+ * for handles the per-env kernels do not serve: fp64, the Dormand-Prince solver (fixed step or GEMX_SOLVER_ADAPTIVE), interlocking_time > 0,
+ * action_delay > 0, GEMX_SUPPLY_RC, random initial states.  While a table is set gemx_rollout_synthetic, gemx_rollout_half and
+ * gemx_rollout(obs_every = 0) return GEMX_ERR_ARG before anything is launched.
+ * gemx_set_env_params copies synchronously (not inside a stream capture); calling it again replaces the table's contents in place, so a
+ * captured graph keeps working with the new values.  gemx_clear_env_params synchronises the device, frees the table and returns the handle
+ * to the kernels it ran before.  gemx_get_env_params copies the table as it sits on the device to out_dev ([F][n_envs] R) on `stream`. */
+typedef struct gemx_env_params {
+    int32_t struct_size; /* = sizeof(gemx_env_params) */
+    int64_t n_envs;      /* length of every array: the handle's n_envs */
+    const double *model;
+    const double *torque_coef;
+    const double *j_total, *load_a, *load_b, *load_c;
+    const double *u_nominal;
+} gemx_env_params;
+int gemx_set_env_params(gemx_handle *h, const gemx_env_params *p);
+int gemx_clear_env_params(gemx_handle *h);
+int gemx_get_env_params(gemx_handle *h, void *out_dev, void *stream);
+int gemx_env_params_fields(const gemx_handle *h);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
