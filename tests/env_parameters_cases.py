@@ -1,45 +1,102 @@
-"""Shared by tests/test_env_parameters_cpu.py and tests/test_gpu_env_parameters.py: the envs, the four parameter sets per env, the
-seeded actions, and the fp64 oracle run once per (env, set).
+"""Shared by tests/test_env_parameters_cpu.py, tests/test_gpu_env_parameters.py and tests/test_gpu_env_parameters_units.py: the envs, the
+parameter sets per env, the seeded actions, and the fp64 oracle run once per (env, family).
 
-Shape: N = 197 envs (three full waves and a partial one), K = 48 steps, set index = env % 4 (every wave holds all four sets).  A set is
-the default machine with its resistances, its inductances, J_load and u_nominal scaled by factors in [0.6, 1.6].  The factors and the
-action amplitude of every env were chosen on the CPU with the fp64 oracle so that within the 48 steps at least one set violates its
-constraint (and auto-resets) and at least one never does; `oracle_runs` lets the tests assert exactly that."""
+Shape: N = 197 envs (three full waves and a partial one), K = 48 steps.  Three FAMILIES of per-env parameters:
+
+  "factors"  set index = env % 4 (every wave holds all four sets).  A set is the default machine with its resistances, its inductances,
+             J_load and u_nominal scaled by factors in [0.6, 1.6] (FACTORS).
+  "fields"   set index = env % 4 again: the factors of the set AND what they leave alone -- the load's a, b and c (each different between
+             the sets; set 1 has a = 0, i.e. no kink, in a wave whose other lanes have one; three sets have c > 0), psi_p / psi_e where the
+             motor has it, and j_rotor (FIELD_SETS).  PolynomialStaticLoad cases only: psi_p varies (PMSM, also per lane), psi_e does not --
+             the one motor that has it, the permanently excited DC motor, runs here at a constant speed, where the search on the CPU found
+             no seeded actions that meet the conditions below with field sets or per-lane machines.
+  "lanes"    every env its own machine: every overridable key (motor parameters but p, j_load, a / b / c where the default is not zero,
+             u_nominal) scaled by an independent seeded draw, log-uniform in [0.6, 1.6], per env.  No two envs share a value.
+
+CASES are the seven envs of tests/test_gpu_env_parameters.py; UNIT_CASES add one env per per-env kernel unit libgemx_ep<S>_<C>.so that the
+seven do not launch (the `unit` entry: (system kind, converter unit)).  (6,11) is reached through the DqToAbcActionProcessor('EESM') --
+control_space='dq' is refused for an EESM --, and (2,10) through make("Cont-SC-SCIM-v0", control_space="dq"): a system built with
+control_space='dq' rotates by the rotor-flux angle of its OWN state, it needs no FluxObserver (which refuses a table), so every one of the
+19 units is reachable with a table.
+
+The factors, the field sets, the draws' seed and the actions (amplitude, bias, hold, seed, tau) of every (env, family) were chosen on the
+CPU with the fp64 oracle so that within the 48 steps
+  * at least one set (family "lanes": lane) violates its constraint and at least one never does                   (`exercised`),
+  * no step of any lane brings a monitored constraint quantity within MARGIN = 1e-3 (10 x the parity tolerance) of its limit, which is
+    what makes the exact comparison of done masks legitimate: no lane is excluded                                     (`margin`),
+  * lanes whose load has a = 0 run the oracle's plain "rk4" and the others "rk4_kink", as fill_params decides it for a uniform handle
+    from omega_lim = a / j_total * tau_decay > 0                                                                     (`oracle_solver`);
+tests/test_env_parameters_cpu.py asserts all three for every new (case, family) without a GPU."""
 import functools
 import json
+import zlib
 
 import numpy as np
 
 import gym_electric_motor_amd as ga
 from oracle import oracle as orc
+from parity_contract import REL_FLOOR
 
 N, K, NSETS = 197, 48, 4
+MARGIN = 1e-3
 
 # per set: (resistances, inductances, J_load, u_nominal), each in [0.6, 1.6]
 FACTORS = ((1.0, 1.0, 1.0, 1.0), (1.6, 1.5, 0.6, 0.6), (0.6, 0.7, 1.6, 1.6), (1.3, 0.6, 1.2, 0.8))
+# per set of the "fields" family, on top of FACTORS: (a, b, c, psi_p | psi_e, j_rotor).  a, b: factors of the load's own a, b (of A_REF, B_REF
+# where its own is zero); c: the fraction of b * omega that c * omega^2 is at the speed limit; psi, j_rotor: factors of the motor's own
+FIELD_SETS = ((1.0, 1.0, 0.0, 1.0, 1.0), (0.0, 1.5, 0.5, 1.3, 0.7), (1.6, 0.6, 1.0, 0.75, 1.5), (0.7, 1.3, 0.25, 1.15, 1.25))
+A_REF, B_REF = 0.01, 0.01
+LANE_LO, LANE_HI, LANE_SEED = 0.6, 1.6, 2029
+FAMILIES = ("factors", "fields", "lanes")
 
 _RES = ("r_a", "r_e", "r_s", "r_r")
 _IND = ("l_a", "l_e", "l_e_prime", "l_d", "l_q", "l_m", "l_sigs", "l_sigr")
+_PSI = ("psi_p", "psi_e")
 
 # env id -> make() keywords, the seeded actions (continuous: bias + amp * U(-1, 1); discrete: uniform over the action set, each draw held for
 # `hold` steps) and whether the load is a PolynomialStaticLoad (else a uniform system may take the one-step linear map)
 CASES = {
     "Cont-CC-PermExDc-v0": dict(kw=dict(ode_solver=ga.EulerSolver()), amp=0.02, bias=0.275, poly=False),
     "Finite-CC-PMSM-v0": dict(kw=dict(ode_solver=ga.RK4Solver(), tau=1e-4), amp=None, poly=False),
-    "Cont-SC-SCIM-v0": dict(kw=dict(), amp=1.0, poly=True),
+    "Cont-SC-SCIM-v0": dict(kw=dict(), amp=1.0, poly=True, lanes=dict(amp=1.0, bias=0.85)),
     "Cont-CC-EESM-v0": dict(kw=dict(), amp=0.25, poly=False),
     "Finite-TC-DFIM-v0": dict(kw=dict(tau=1e-4), amp=None, hold=8, poly=False),
     "Cont-SC-SeriesDc-v0": dict(kw=dict(tau=4e-4), amp=0.3, bias=0.7, poly=True),
     "dq-PMSM": dict(env_id="Cont-SC-PMSM-v0", kw=dict(control_space="dq"), amp=0.6, poly=True),
 }
+# One env per per-env unit the seven above never launch.  `unit`: (system kind, converter unit) as the launch string names them; an entry
+# named like a family overrides the action settings (amp, bias, hold, seed) for that family.
+UNIT_CASES = {}  # filled below (UNIT_CASES.update): the tuned settings
+
+
+def _case(case):
+    return CASES[case] if case in CASES else UNIT_CASES[case]
+
+
+def _setting(case, family, key, default=None):
+    c = _case(case)
+    return c.get(family, {}).get(key, c.get(key, default))
 
 
 def env_id_of(case):
-    return CASES[case].get("env_id", case)
+    return _case(case).get("env_id", case)
 
 
 def make_kwargs(case):
-    return dict(CASES[case]["kw"])
+    return dict(_case(case)["kw"])
+
+
+def families_of(case):
+    """The set families of a case: the field sets belong to the PolynomialStaticLoad cases (they vary its coefficients and j_rotor)."""
+    return ("factors", "fields") if _case(case)["poly"] else ("factors",)
+
+
+def n_sets(family):
+    return N if family == "lanes" else NSETS
+
+
+def set_of_env(family, n=N):
+    return np.arange(n) if family == "lanes" else np.arange(n) % NSETS
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,51 +105,92 @@ def base_env(case):
     return ga.make(env_id_of(case), n_envs=N, _defer_create=True, **make_kwargs(case))
 
 
-def set_values(case, s):
-    """-> (motor overrides, load overrides, supply overrides) of set s as scalars."""
+def _own_motor_parameters(ps):
+    motor = ps.electrical_motor
+    return {k: float(v) for k, v in motor.motor_parameter.items() if k not in getattr(motor, "DERIVED_PARAMETERS", ()) and k != "p"}
+
+
+def _polynomial(ps):
+    return type(ps.mechanical_load).__name__ == "PolynomialStaticLoad"
+
+
+@functools.lru_cache(maxsize=None)
+def lane_keys(case):
+    """The overridable keys of a case as (group, key, default), defaults of zero left out (a scaled zero is no per-env value)."""
     ps = base_env(case).physical_system
+    keys = [("motor", k, v) for k, v in sorted(_own_motor_parameters(ps).items())]
+    keys.append(("load", "j_load", float(getattr(ps.mechanical_load, "_j_load", 0.0))))
+    if _polynomial(ps):
+        keys += [("load", k, float(ps.mechanical_load.load_parameter[k])) for k in ("a", "b", "c")]
+    keys.append(("supply", "u_nominal", float(ps.supply.u_nominal)))
+    return tuple(k for k in keys if k[2] != 0.0)
+
+
+@functools.lru_cache(maxsize=None)
+def lane_factors(case):
+    """[N, number of lane_keys] independent draws, log-uniform in [LANE_LO, LANE_HI]."""
+    rng = np.random.default_rng([LANE_SEED, zlib.crc32(case.encode())])
+    return np.exp(rng.uniform(np.log(LANE_LO), np.log(LANE_HI), (N, len(lane_keys(case)))))
+
+
+def set_values(case, s, family="factors"):
+    """-> (motor overrides, load overrides, supply overrides) of set s (family "lanes": of env s) as scalars."""
+    ps = base_env(case).physical_system
+    if family == "lanes":
+        out = {"motor": {}, "load": {}, "supply": {}}
+        for (group, key, default), f in zip(lane_keys(case), lane_factors(case)[s]):
+            out[group][key] = default * float(f)
+        return out["motor"], out["load"], out["supply"]
     fr, fl, fj, fu = FACTORS[s]
     mp = ps.electrical_motor.motor_parameter
     motor = {k: mp[k] * fr for k in _RES if k in mp}
     motor.update({k: mp[k] * fl for k in _IND if k in mp})
     j_load = float(getattr(ps.mechanical_load, "_j_load", 0.0))
-    return motor, {"j_load": j_load * fj}, {"u_nominal": float(ps.supply.u_nominal) * fu}
+    load = {"j_load": j_load * fj}
+    if family == "fields":
+        fa, fb, fc, fpsi, fjr = FIELD_SETS[s]
+        if _polynomial(ps):
+            lp = ps.mechanical_load.load_parameter
+            load.update(a=(float(lp["a"]) or A_REF) * fa, b=(float(lp["b"]) or B_REF) * fb, c=fc * (float(lp["b"]) or B_REF) / float(ps.limits[0]))
+        motor.update({k: mp[k] * fpsi for k in _PSI if k in mp})
+        motor["j_rotor"] = mp["j_rotor"] * fjr
+    return motor, load, {"u_nominal": float(ps.supply.u_nominal) * fu}
 
 
-def env_parameters(case, n=N, sets=None):
-    """EnvParameters with set index = env % 4 (or `sets` [n]: the set of every env)."""
-    sets = np.arange(n) % NSETS if sets is None else np.asarray(sets)
-    vals = [set_values(case, s) for s in range(NSETS)]
+def env_parameters(case, n=N, sets=None, family="factors"):
+    """EnvParameters with set index = env % 4, family "lanes": = env (or `sets` [n]: the set of every env)."""
+    sets = set_of_env(family, n) if sets is None else np.asarray(sets)
+    vals = [set_values(case, s, family) for s in range(n_sets(family))]
     groups = []
     for g in range(3):
-        groups.append({k: np.array([vals[s][g][k] for s in range(NSETS)])[sets] for k in vals[0][g]})
+        groups.append({k: np.array([v[g][k] for v in vals])[sets] for k in vals[0][g]})
     return ga.EnvParameters(motor=groups[0], load=groups[1], supply=groups[2])
 
 
-def uniform_kwargs(case, s):
+def uniform_kwargs(case, s, family="factors"):
     """make() keywords of the uniform env built with set s."""
-    motor, load, supply = set_values(case, s)
+    motor, load, supply = set_values(case, s, family)
     ps = base_env(case).physical_system
     kw = make_kwargs(case)
     kw["motor"] = dict(motor_parameter=motor)
     ld = ps.mechanical_load
     if type(ld).__name__ == "PolynomialStaticLoad":
-        kw["load"] = dict(load_parameter=dict(ld.load_parameter, j_load=load["j_load"]))
+        kw["load"] = dict(load_parameter=dict(ld.load_parameter, **load))
     kw["supply"] = dict(u_nominal=supply["u_nominal"])
     return kw
 
 
-def actions(case, seed=11):
+def actions(case, seed=11, family="factors"):
     """Seeded actions [K, N, A] float32 / [K, N] uint8."""
     ps = base_env(case).physical_system
-    rng = np.random.default_rng(seed)
-    amp = CASES[case]["amp"]
+    rng = np.random.default_rng(_setting(case, family, "seed", seed))
+    amp = _setting(case, family, "amp")
     space = ps.action_space
     if amp is None:
         n = int(np.prod(space.nvec)) if hasattr(space, "nvec") else int(space.n)
-        hold = CASES[case].get("hold", 1)
+        hold = _setting(case, family, "hold", 1)
         return np.repeat(rng.integers(0, n, ((K + hold - 1) // hold, N)), hold, axis=0)[:K].astype(np.uint8)
-    return np.clip(CASES[case].get("bias", 0.0) + amp * rng.uniform(-1.0, 1.0, (K, N, int(space.shape[0]))), -1.0, 1.0).astype(np.float32)
+    return np.clip(_setting(case, family, "bias", 0.0) + amp * rng.uniform(-1.0, 1.0, (K, N, int(space.shape[0]))), -1.0, 1.0).astype(np.float32)
 
 
 def _converter_name(conv):
@@ -101,15 +199,27 @@ def _converter_name(conv):
     return name if subs is None else name + "[" + ",".join(type(c).__name__ for c in subs) + "]"
 
 
-def oracle_params(case, s):
+def oracle_solver(case, s, family="factors"):
+    """The oracle's solver for set s.  RK4 behind a PolynomialStaticLoad corrects the load's kink in closed form ("rk4_kink") when the solver
+    splits kinks AND the load has one: omega_lim = a / j_total * tau_decay > 0, i.e. a > 0 (fill_params for a handle, ep_apply per lane)."""
+    ps = base_env(case).physical_system
+    name = type(ps._ode_solver).__name__
+    if name == "EulerSolver":
+        return "euler"
+    assert name == "RK4Solver", name
+    if not (getattr(ps._ode_solver, "_split_kinks", False) and _case(case)["poly"]):
+        return "rk4"
+    a = set_values(case, s, family)[1].get("a", float(ps.mechanical_load.load_parameter["a"]))
+    return "rk4_kink" if a > 0 else "rk4"
+
+
+def oracle_params(case, s, family="factors"):
     """OrcParams of set s: the uniform env's components, normalised by the COMMON limits (those of the env without a table)."""
     base = base_env(case).physical_system
-    env = ga.make(env_id_of(case), n_envs=1, _defer_create=True, **uniform_kwargs(case, s))
+    env = ga.make(env_id_of(case), n_envs=1, _defer_create=True, **uniform_kwargs(case, s, family))
     ps = env.physical_system
-    solver = type(ps._ode_solver).__name__
-    solver = {"EulerSolver": "euler", "RK4Solver": "rk4_kink" if getattr(ps._ode_solver, "_split_kinks", False) and CASES[case]["poly"] else "rk4"}[solver]
     meta = dict(system=type(ps).__name__.replace("Batched", ""), motor=type(ps.electrical_motor).__name__, converter=_converter_name(ps.converter),
-                load=type(ps.mechanical_load).__name__, solver=solver, episodic=True, tau=float(ps.tau), interlocking_time=0.0,
+                load=type(ps.mechanical_load).__name__, solver=oracle_solver(case, s, family), episodic=True, tau=float(ps.tau), interlocking_time=0.0,
                 u_nominal=float(ps.supply.u_nominal), motor_parameter={k: float(v) for k, v in ps.electrical_motor.motor_parameter.items()},
                 j_total=float(ps.mechanical_load.j_total), load_parameter=dict(getattr(ps.mechanical_load, "load_parameter", {}) or {}),
                 tau_decay=float(getattr(ps.mechanical_load, "tau_decay", 1e-3)), limits=[float(v) for v in base.limits],
@@ -120,20 +230,164 @@ def oracle_params(case, s):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_runs(case):
-    """fp64 oracle, once per (set, lane of that set): -> obs [K, N, S_out], done [K, N] with lane e run under set e % 4 and lane e's actions."""
-    a = actions(case)
+def oracle_runs(case, family="factors", auto_reset=True):
+    """fp64 oracle, once per (set, lane of that set): -> obs [K, N, S_out], done [K, N] with lane e run under its set and lane e's actions.
+    Read-only: the arrays are shared between tests."""
+    a = actions(case, family=family)
     nvec = getattr(base_env(case).physical_system.action_space, "nvec", None)
     if nvec is not None:  # MultiDiscrete: the device reads the flat index a0 + n0 * a1, the oracle one entry per sub-converter
         a = np.stack([a % int(nvec[0]), a // int(nvec[0])], axis=-1)
     obs = done = None
-    for s in range(NSETS):
-        p = oracle_params(case, s)
-        for e in range(s, N, NSETS):
+    sets = set_of_env(family)
+    for s in range(n_sets(family)):
+        p = oracle_params(case, s, family)
+        for e in np.flatnonzero(sets == s):
             env = orc.OracleEnv(p)
             env.reset()
-            o, d = env.rollout(a[:, e].astype(np.float64), auto_reset=True)
+            o, d = env.rollout(a[:, e].astype(np.float64), auto_reset=auto_reset)
             if obs is None:
                 obs, done = np.zeros((K, N, o.shape[-1])), np.zeros((K, N), dtype=bool)
             obs[:, e], done[:, e] = o, d
+    obs.setflags(write=False)
+    done.setflags(write=False)
     return obs, done
+
+
+def live_steps(done, auto_reset=True):
+    """[K, N] bool: the steps a lane's rows are compared at -- all of them with auto-reset, else up to and including its first done step."""
+    if auto_reset:
+        return np.ones(done.shape, dtype=bool)
+    before = np.cumsum(done, axis=0) - done  # number of done steps BEFORE step k
+    return before == 0
+
+
+def constraint_quantities(case, obs):
+    """The values the env's default constraints compare with 1 -> [K, N, number of quantities]: |state| of a LimitConstraint, the sum of
+    squares of the SquaredConstraint (oracle.default_masks: the masks the oracle itself terminates by)."""
+    ps = base_env(case).physical_system
+    names = list(ps.state_names)
+    meta = dict(system=type(ps).__name__.replace("Batched", ""), motor=type(ps.electrical_motor).__name__, state_names=names)
+    lim, sq = orc.default_masks(meta)
+    q = [np.abs(obs[..., i]) for i in range(len(names)) if lim >> i & 1]
+    if sq:
+        q.append(sum(obs[..., i] ** 2 for i in range(len(names)) if sq >> i & 1))
+    return np.stack(q, axis=-1)
+
+
+def margin(case, family="factors", auto_reset=True):
+    """The smallest distance of a monitored constraint quantity from its limit over the live steps of all lanes, by the oracle."""
+    obs, done = oracle_runs(case, family, auto_reset)
+    q = constraint_quantities(case, obs)
+    return float(np.abs(q - 1.0)[live_steps(done, auto_reset)].min())
+
+
+def exercised(case, family="factors"):
+    """(some set terminates within K, some set never does) by the oracle; per LANE for the family "lanes" and for a case marked
+    `per_set=False` (Finite-CC-PermExDc-v0: at its constant speed every held switching state ends in an overcurrent, so no set of 49 lanes
+    is spared as a whole)."""
+    _, done = oracle_runs(case, family)
+    sets = set_of_env(family) if _case(case).get("per_set", True) else np.arange(N)
+    per_set = [bool(done[:, sets == s].any()) for s in np.unique(sets)]
+    return any(per_set), not all(per_set)
+
+
+def kink_crossings(case, family="fields"):
+    """By the oracle: (lanes with a > 0 whose |omega| leaves the kink's neighbourhood |omega| < omega_lim = a / j_total * tau_decay within K --
+    every episode starts inside it, at omega = 0 --, lanes with a = 0), both as env indices."""
+    obs, _ = oracle_runs(case, family)
+    omega = np.abs(obs[..., 0]) * float(base_env(case).physical_system.limits[0])
+    sets = set_of_env(family)
+    crossing, without = [], []
+    for s in range(n_sets(family)):
+        p = oracle_params(case, s, family)
+        lanes = np.flatnonzero(sets == s)
+        if p.load_a == 0.0:
+            without += list(lanes)
+        else:
+            lim = p.load_a / p.j_total * p.tau_decay
+            crossing += [e for e in lanes if (omega[:, e] > lim).any()]
+    return np.array(sorted(crossing), dtype=int), np.array(sorted(without), dtype=int)
+
+
+def oracle_error(names, got, got_done, ref, ref_done, live=None):
+    """Worst relative error of rows [K, N, S_out] against the oracle's over the `live` steps [K, N] (all), per column relative to the
+    column's largest reference magnitude; done masks exact.  Induction machines: the field-oriented pairs through their rotation-invariant
+    magnitudes (the frame is undefined at zero flux, where every episode starts)."""
+    live = np.ones(ref_done.shape, dtype=bool) if live is None else live
+    assert np.array_equal(got_done.astype(bool)[live], ref_done[live]), int((got_done.astype(bool) != ref_done)[live].sum())
+    got, ref = got.astype(np.float64)[live], ref[live]
+    cols = {n: i for i, n in enumerate(names)}
+    worst = 0.0
+    skip = set()
+    if "i_sa" in cols:
+        for p, q in (("i_sd", "i_sq"), ("u_sd", "u_sq"), ("i_rd", "i_rq"), ("u_rd", "u_rq")):
+            if p in cols:
+                skip |= {cols[p], cols[q]}
+                mg, mr = np.hypot(got[..., cols[p]], got[..., cols[q]]), np.hypot(ref[..., cols[p]], ref[..., cols[q]])
+                worst = max(worst, float(np.abs(mg - mr).max() / max(float(mr.max()), REL_FLOOR)))
+    for j, n in enumerate(names):
+        if j in skip:
+            continue
+        d = np.abs(got[..., j] - ref[..., j])
+        if n == "epsilon":
+            d = np.minimum(d, 2.0 - d)  # normalised angle wraps at +-1
+        worst = max(worst, float(d.max() / max(float(np.abs(ref[..., j]).max()), REL_FLOOR)))
+    return worst
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# A float64 host restatement of the device table [F, N] (gemx_envparams.hpp: the packed model entries, then tc0..tc3, inv_j, la, lb, lc,
+# omega_lim, lin_factor, inv_tau_decay, u_sup), from the arrays of EnvParameters.resolve, rounded ONCE to fp32: no kernel in the loop.
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# (row, column) of the structurally non-zero entries of motor._model_constants per system kind, in the table's order
+_SHUNT = ((0, 0), (0, 2), (0, 3), (1, 1), (1, 4))
+_SCIM = ((0, 1), (0, 3), (0, 6), (0, 7), (1, 2), (1, 4), (1, 5), (1, 8), (2, 1), (2, 3), (2, 6), (3, 2), (3, 4), (3, 5))
+MODEL_ENTRIES = {
+    "DcPermanentlyExcitedMotor": ((0, 0), (0, 1), (0, 2)), "DcSeriesMotor": ((0, 0), (0, 1), (0, 2)), "DcShuntMotor": _SHUNT,
+    "DcExternallyExcitedMotor": _SHUNT,
+    "PermanentMagnetSynchronousMotor": ((0, 1), (0, 3), (0, 6), (1, 0), (1, 2), (1, 4), (1, 5)),
+    "SynchronousReluctanceMotor": ((0, 1), (0, 3), (0, 6), (1, 0), (1, 2), (1, 4), (1, 5)),
+    "ExternallyExcitedSynchronousMotor": ((0, 1), (0, 3), (0, 4), (0, 6), (0, 8), (1, 2), (1, 5), (1, 7), (1, 9), (2, 1), (2, 3), (2, 4), (2, 6), (2, 8)),
+    "SquirrelCageInductionMotor": _SCIM,
+    "DoublyFedInductionMotor": _SCIM + ((0, 9), (1, 10), (2, 9), (3, 10)),
+}
+TAIL_FIELDS = ("tc0", "tc1", "tc2", "tc3", "inv_j", "la", "lb", "lc", "omega_lim", "lin_factor", "inv_tau_decay", "u_sup")
+
+
+def restated_table(system, arrays, model_cols):
+    """-> (float32 [F, N], field names).  `arrays`: EnvParameters.resolve(system); `model_cols`: the row pitch of arrays["model"]."""
+    entries = MODEL_ENTRIES[type(system.electrical_motor).__name__]
+    n = len(arrays["j_total"])
+    tau_decay = np.float64(getattr(system.mechanical_load, "tau_decay", 1e-3))  # (a ConstantSpeedLoad's handle carries 1e-3)
+    j = arrays["j_total"].astype(np.float64)
+    rows = [arrays["model"][:, r * model_cols + c] for r, c in entries]
+    rows += [arrays["torque_coef"][:, i] for i in range(4)]
+    rows += [1.0 / j, arrays["load_a"], arrays["load_b"], arrays["load_c"], arrays["load_a"] / j * tau_decay, j / tau_decay,
+             np.full(n, 1.0 / tau_decay), arrays["u_nominal"]]
+    names = ["m%d" % i for i in range(len(entries))] + list(TAIL_FIELDS)
+    return np.stack([np.asarray(r, dtype=np.float64) for r in rows]).astype(np.float32), names
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# The unit cases and the per-lane cases, with the action settings the conditions above were met with
+# ---------------------------------------------------------------------------------------------------------------------------------------
+UNIT_CASES.update({
+    "Cont-SC-PMSM-v0": dict(kw=dict(), amp=1.0, poly=True, unit=(1, 2)),
+    "Cont-SC-SynRM-v0": dict(kw=dict(), amp=0.6, poly=True, unit=(1, 2), fields=dict(amp=1.0, bias=0.85)),
+    "Finite-SC-SCIM-v0": dict(kw=dict(), amp=None, hold=2, poly=True, unit=(2, 1)),
+    "Finite-CC-PermExDc-v0": dict(kw=dict(), amp=None, hold=2, seed=15, poly=False, unit=(0, 3), per_set=False),
+    "Finite-SC-SeriesDc-v0": dict(kw=dict(tau=1e-3), amp=None, hold=8, poly=True, unit=(3, 3)),
+    "Cont-SC-ShuntDc-v0": dict(kw=dict(), amp=0.15, poly=True, unit=(4, 0), lanes=dict(seed=12)),
+    "Finite-SC-ShuntDc-v0": dict(kw=dict(tau=2e-5), amp=None, hold=1, seed=17, poly=True, unit=(4, 3)),
+    "Cont-SC-ExtExDc-v0": dict(kw=dict(), amp=0.15, seed=15, poly=True, unit=(5, 4)),
+    "Finite-CC-ExtExDc-v0": dict(kw=dict(tau=2e-5), amp=None, hold=1, seed=22, poly=False, unit=(5, 5)),
+    "Finite-SC-EESM-v0": dict(kw=dict(), amp=None, hold=2, seed=12, poly=True, unit=(6, 7)),
+    "Cont-SC-DFIM-v0": dict(kw=dict(tau=2e-4), amp=1.0, bias=0.6, poly=True, unit=(7, 8), fields=dict(bias=0.3), lanes=dict(bias=0.0)),
+    "dqproc-EESM": dict(env_id="Cont-SC-EESM-v0", kw=dict(physical_system_wrappers=(ga.DqToAbcActionProcessor("EESM"),)), amp=0.15, seed=21, poly=True,
+                        unit=(6, 11)),
+    "dq-SCIM": dict(env_id="Cont-SC-SCIM-v0", kw=dict(control_space="dq"), amp=0.3, poly=True, unit=(2, 10)),
+})
+# every lane its own machine, one case per table width (model entries: 3, 5, 7, 14, 18); the first is finite-set
+LANE_CASES = ("Finite-SC-SeriesDc-v0", "Cont-SC-ShuntDc-v0", "Cont-SC-PMSM-v0", "Cont-SC-SCIM-v0", "Cont-SC-DFIM-v0")
+EDGE_LANES = (0, 63, 64, 65, 196)  # block edges and the tail: the lanes compared with uniform handles of their own
+SOA_CASE, NO_RESET_CASE, MIXED_KINK_CASE = "Cont-SC-ShuntDc-v0", "Cont-SC-PMSM-v0", "Cont-SC-ShuntDc-v0"

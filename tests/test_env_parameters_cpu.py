@@ -41,13 +41,18 @@ def test_vectorised_constants_equal_those_of_single_motors(cls):
         assert got == [float(w) for w in want], (cls.__name__, i)
 
 
-@pytest.mark.parametrize("case", list(cases.CASES))
-def test_arrays_of_the_sets_equal_the_uniform_systems_configs(case):
+SET_FAMILIES = [(c, "factors") for c in cases.CASES] + [(c, f) for c in cases.UNIT_CASES for f in cases.families_of(c)]
+NEW_FAMILIES = [(c, f) for c in cases.UNIT_CASES for f in cases.families_of(c)] + [(c, "lanes") for c in cases.LANE_CASES]
+
+
+@pytest.mark.parametrize("case, family", SET_FAMILIES, ids=[c if c in cases.CASES else c + "-" + f for c, f in SET_FAMILIES])
+def test_arrays_of_the_sets_equal_the_uniform_systems_configs(case, family):
     """What goes to gemx_set_env_params for lane e is what a uniform system built with lane e's set puts into its gemx_config."""
-    env = ga.make(cases.env_id_of(case), n_envs=cases.N, _defer_create=True, env_parameters=cases.env_parameters(case), **cases.make_kwargs(case))
+    env = ga.make(cases.env_id_of(case), n_envs=cases.N, _defer_create=True, env_parameters=cases.env_parameters(case, family=family),
+                  **cases.make_kwargs(case))
     arr = env.physical_system._env_parameter_arrays
     for s in range(cases.NSETS):
-        cfg = ga.make(cases.env_id_of(case), n_envs=1, _defer_create=True, **cases.uniform_kwargs(case, s)).physical_system._cfg
+        cfg = ga.make(cases.env_id_of(case), n_envs=1, _defer_create=True, **cases.uniform_kwargs(case, s, family)).physical_system._cfg
         for e in (s, s + 4 * 20, s + 4 * 48):
             assert np.array_equal(arr["model"][e], np.array(cfg.model[:])), (case, s)
             assert np.array_equal(arr["torque_coef"][e], np.array(cfg.torque_coef[:]))
@@ -161,6 +166,73 @@ def test_the_chosen_sets_exercise_both_outcomes():
         per_set = [bool(done[:, s::cases.NSETS].any()) for s in range(cases.NSETS)]
         assert any(per_set) and not all(per_set), (case, per_set)
     assert all(0.6 <= f <= 1.6 for fs in cases.FACTORS for f in fs)
+
+
+@pytest.mark.parametrize("case", cases.LANE_CASES)
+def test_arrays_of_a_lane_equal_the_config_of_a_system_built_with_its_machine(case):
+    """Family "lanes": what `resolve()` hands over for lane e is the gemx_config of a one-env system built with lane e's values; and the
+    float64 restatement of the device table tells every env from every other by one field alone."""
+    ps = ga.make(cases.env_id_of(case), n_envs=cases.N, _defer_create=True, env_parameters=cases.env_parameters(case, family="lanes"),
+                 **cases.make_kwargs(case)).physical_system
+    arr = ps._env_parameter_arrays
+    for e in cases.EDGE_LANES + (1, 100):
+        cfg = ga.make(cases.env_id_of(case), n_envs=1, _defer_create=True, **cases.uniform_kwargs(case, e, "lanes")).physical_system._cfg
+        assert np.array_equal(arr["model"][e], np.array(cfg.model[:])), (case, e)
+        assert np.array_equal(arr["torque_coef"][e], np.array(cfg.torque_coef[:]))
+        assert arr["j_total"][e] == cfg.j_total and arr["u_nominal"][e] == cfg.u_nominal
+        assert (arr["load_a"][e], arr["load_b"][e], arr["load_c"][e]) == (cfg.load_a, cfg.load_b, cfg.load_c)
+    f = cases.lane_factors(case)
+    assert f.min() >= cases.LANE_LO and f.max() <= cases.LANE_HI and all(len(np.unique(f[:, i])) == cases.N for i in range(f.shape[1]))
+    tab, names = cases.restated_table(ps, arr, _lib.MODEL_COLS)
+    assert tab.shape == (table_fields(ps._SYSTEM_KIND), cases.N) and tab.dtype == np.float32
+    distinct = [n for i, n in enumerate(names) if len(np.unique(tab[i])) == cases.N]
+    assert "u_sup" in distinct and "inv_j" in distinct and "m0" in distinct, (case, distinct)
+    # a table read by the lane within its block, or at an index off by a constant, is another table: every env is told from every other
+    for shift in (1, 4, 64):
+        assert not np.any(np.all(tab[:, shift:] == tab[:, :-shift], axis=0))
+    assert not np.any(np.all(tab[:, 64:] == tab[:, np.arange(64, cases.N) % 64], axis=0))
+    # ... which the 4-periodic sets cannot show: their table is the same at any index off by a multiple of 4, the lane within the block included
+    four, _ = cases.restated_table(ps, cases.env_parameters(case, family="factors").resolve(ps), _lib.MODEL_COLS)
+    assert np.array_equal(four[:, 64:], four[:, np.arange(64, cases.N) % 64]) and np.array_equal(four[:, 4:], four[:, :-4])
+
+
+def test_the_lane_cases_cover_every_table_width_and_a_finite_set_converter():
+    widths = {c: table_fields(cases.base_env(c).physical_system._SYSTEM_KIND) - 12 for c in cases.LANE_CASES}
+    assert sorted(widths.values()) == [3, 5, 7, 14, 18], widths
+    assert any(hasattr(cases.base_env(c).physical_system.action_space, "n") for c in cases.LANE_CASES)
+
+
+@pytest.mark.parametrize("case, family", NEW_FAMILIES, ids=["-".join(p) for p in NEW_FAMILIES])
+def test_the_new_cases_meet_their_conditions_by_the_oracle(case, family):
+    """From the fp64 oracle alone: one set (lane) terminates and one never does; no step of any lane brings a monitored constraint quantity
+    within 1e-3 of its limit (no lane is excluded from the exact done-mask comparison); a = 0 runs plain RK4, a > 0 the kink-corrected one."""
+    assert cases.exercised(case, family) == (True, True), (case, family)
+    assert cases.margin(case, family) >= cases.MARGIN == 1e-3, (case, family, cases.margin(case, family))
+    ps = cases.base_env(case).physical_system
+    for s in (range(cases.NSETS) if family != "lanes" else cases.EDGE_LANES):
+        p = cases.oracle_params(case, s, family)
+        want = "euler" if type(ps._ode_solver).__name__ == "EulerSolver" else (
+            "rk4_kink" if cases._case(case)["poly"] and getattr(ps._ode_solver, "_split_kinks", False) and p.load_a > 0 else "rk4")
+        assert cases.oracle_solver(case, s, family) == want, (case, family, s)
+        from oracle import oracle as orc
+        assert (p.solver, p.nsteps) == orc._SOLVER[want]
+
+
+def test_the_field_sets_vary_what_the_factors_leave_alone():
+    a, b, c, psi, jr = (np.array(v) for v in zip(*cases.FIELD_SETS))
+    assert len(set(a)) == len(set(b)) == len(set(c)) == len(set(psi)) == len(set(jr)) == 4 and (a == 0).sum() == 1 and (c > 0).any()
+    assert all(0.6 <= f <= 1.6 for f in list(b) + list(psi) + list(jr) + [x for x in a if x > 0])
+    case = cases.MIXED_KINK_CASE
+    arr = cases.env_parameters(case, family="fields").resolve(cases.base_env(case).physical_system)
+    for k in ("load_a", "load_b", "load_c", "j_total"):
+        assert len(np.unique(arr[k][:4])) == 4, k
+    pm = cases.env_parameters("Cont-SC-PMSM-v0", family="fields")
+    assert len(np.unique(pm.motor["psi_p"][:4])) == 4 and len(np.unique(pm.motor["j_rotor"][:4])) == 4
+    # mixed kink lanes: by the oracle, lanes with a > 0 leave the kink's neighbourhood while lanes with a = 0 sit in the same wave
+    crossing, without = cases.kink_crossings(case)
+    assert crossing.size > 0 and without.size > 0 and np.intersect1d(crossing // 64, without // 64).size > 0
+    assert cases.margin(cases.NO_RESET_CASE, "factors", auto_reset=False) >= cases.MARGIN
+    assert {u["unit"] for u in cases.UNIT_CASES.values()} == {(1, 2), (2, 1), (0, 3), (3, 3), (4, 0), (4, 3), (5, 4), (5, 5), (6, 7), (7, 8), (6, 11), (2, 10)}
 
 
 def test_the_setter_refuses_a_system_whose_env_runs_a_flux_observer():
