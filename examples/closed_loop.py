@@ -9,6 +9,7 @@ trivial proportional dq controller as the "policy" -- everything stays on the GP
     python examples/closed_loop.py --complete --rollout 500                             # open loop: (state, reference, reward, done) datasets
     python examples/closed_loop.py --complete --rollout 500 --gae                       # ... and GAE advantages of each dataset, one launch
     python examples/closed_loop.py --complete --graph 64 --time-limit 500               # episodes of 500 steps, counted on the device
+    python examples/closed_loop.py --complete --rollout 256 --max-episode-steps 100     # the time limit INSIDE the fused rollout, then GAE
 
 Hand-wired (the baseline to time against): the physics launch with the fused reward, then a generator reset and a generator rollout of one
 step per control step.  `--complete`: `ga.make(..., reference_generator="default")` does the wiring -- two launches per control step (physics +
@@ -20,6 +21,10 @@ of K `step()`s on the same actions would have produced, bit for bit.
 `ga.bind_advantages` on each dataset's reward and done rows: advantages and returns [K, N] in one more launch per K steps.
 `--complete --time-limit M`: `make(..., max_episode_steps=M, episode_statistics=True)` -- an env is truncated after M steps and restarts in
 front of its next step; the mean return and length of the finished episodes come from the device counters (`env.episode_statistics()`).
+`--complete --rollout K --max-episode-steps M`: what a learner on time-limited episodes runs per K steps, all on the device -- the episodic
+rollout (`bind_rollout_complete_episodic`: the time limit inside the fused launch; terminated and truncated rows), the episode statistics,
+and `ga.advantages(..., ended=terminated | truncated, final_value=...)`, which cuts the recursion where an episode ended and bootstraps a
+truncated one from the value of its final observation.  Works with `--env-parameters` (domain randomisation) too.
 
 The same loop with the reference package is `env.step(policy(obs))` on ONE env per Python call (reference: core.py:329-372).
 """
@@ -52,13 +57,18 @@ def main():
     ap.add_argument("--gae", action="store_true", help="--complete --rollout K: GAE(0.99, 0.95) advantages of every dataset (ga.bind_advantages, one launch)")
     ap.add_argument("--time-limit", type=int, default=0, metavar="M", help="--complete: episodes of at most M steps (max_episode_steps) and the device-side "
                                                                             "episode statistics")
+    ap.add_argument("--max-episode-steps", type=int, default=0, metavar="M", dest="max_episode_steps",
+                    help="--complete --rollout K: episodes of at most M steps with the time limit inside the fused rollout (rollout_complete_episodic), "
+                         "ending in ga.advantages(..., ended=terminated | truncated)")
     ap.add_argument("--env-parameters", type=float, default=0.0, metavar="SPREAD", dest="env_parameters",
                     help="domain randomisation: every env gets its own r_s, l_d, l_q and J_load, uniform within +-SPREAD (relative) of the motor's, from a seeded numpy Generator")
     args = ap.parse_args()
-    if args.env_parameters and args.rollout:
+    if args.max_episode_steps and (not args.rollout or args.time_limit or args.gae):
+        ap.error("--max-episode-steps needs --complete --rollout K (and neither --time-limit nor --gae: it runs its own advantages)")
+    if args.env_parameters and args.rollout and not args.max_episode_steps:
         ap.error("--env-parameters: the synthetic-action rollouts are not available with per-env parameters")
-    if args.time_limit and (not args.complete or args.rollout):
-        ap.error("--time-limit needs --complete (and no --rollout: a fused K-step launch cannot restart a truncated env)")
+    if args.time_limit and (not args.complete or args.rollout):  # (--max-episode-steps: the episodic rollout)
+        ap.error("--time-limit needs --complete (and no --rollout: with --rollout K the time limit goes inside the fused launch, --max-episode-steps M)")
     if args.rollout and (not args.complete or args.bind or args.graph):
         ap.error("--rollout needs --complete (and neither --bind nor --graph)")
     if args.gae and not args.rollout:
@@ -139,11 +149,13 @@ def complete(args):
     if args.flat:  # cos / sin instead of the angle, the four columns the policy reads, state and references in one tensor
         wrappers += (ga.CosSinProcessor(remove_angle=True),)
         obs_kw = dict(observed_states=["i_sd", "i_sq", "cos(epsilon)", "sin(epsilon)"], flatten_observation=True)
-    if args.time_limit:
-        obs_kw.update(max_episode_steps=args.time_limit, episode_statistics=True)
+    if args.time_limit or args.max_episode_steps:
+        obs_kw.update(max_episode_steps=args.time_limit or args.max_episode_steps, episode_statistics=True)
     env = ga.make("Cont-CC-PMSM-v0", n_envs=n, ode_solver=ga.RK4Solver(), physical_system_wrappers=wrappers, reference_generator=generator, seed=1, **obs_kw,
                   **env_parameter_kw(args, ga))
     ps = env.physical_system
+    if args.max_episode_steps:
+        return episodic_rollout_loop(args, env)
     if args.rollout:
         return rollout_loop(args, env)
     if args.flat:
@@ -212,6 +224,56 @@ def episode_report(env):
         return
     print(f"episodes (limit {env.episodes.max_steps}): {int(stats['n_finished'].sum())} finished; last finished per env: mean return "
           f"{float(stats['last_ret'][finished].mean()):.2f}, mean length {float(stats['last_length'][finished].double().mean()):.1f}")
+
+
+def episodic_rollout_loop(args, env):
+    """Open loop on time-limited episodes: K control steps per launch of `bind_rollout_complete_episodic`, then GAE with the episode ends."""
+    import torch
+
+    import gym_electric_motor_amd as ga
+
+    n, K, M = args.envs, args.rollout, args.max_episode_steps
+    ps = env.physical_system
+    shapes = env._complete_shapes(K)
+    state, refs, reward = (torch.empty(s, device="cuda") for s in shapes[:3])
+    terminated, truncated, ended = (torch.empty(shapes[3], dtype=torch.uint8, device="cuda") for _ in range(3))
+    stats = dict(ended=ended, finished_return=torch.empty(shapes[3], dtype=torch.float64, device="cuda"),
+                 finished_length=torch.empty(shapes[3], dtype=torch.int32, device="cuda"))
+    env.reset()
+    actions = ps.synthetic_actions(K, seed=1, step0=0)  # (fixed random actions: the policy of a learner would overwrite this tensor)
+    rollout = env.bind_rollout_complete_episodic(actions, state, refs, reward, terminated, truncated, episode_statistics=stats)
+    gamma, lam = 0.99, 0.95
+    cols = torch.tensor([ps.state_positions[s] for s in env.reference_names], device="cuda")
+    value, advantage, returns = (torch.empty_like(reward) for _ in range(3))
+    ret = torch.zeros(n, device="cuda")
+
+    def dataset():
+        rollout()  # pending reset, episodic physics, generators, reward pass, episode rows, row K-1 shown: all on one stream
+        # the value head: minus the tracking error over the discount's horizon.  (A row that ended shows the episode's FINAL state, so the
+        # value of that row is the final_value of a truncated episode.)
+        torch.sum((state[..., cols] - refs).abs(), dim=-1, out=value).mul_(-0.5 / (1.0 - gamma))
+        ga.advantages(reward, value, terminated, gamma=gamma, lam=lam, ended=ended, final_value=value, advantage_out=advantage, return_out=returns)
+        ret.add_(reward.sum(dim=0))
+
+    dataset()  # (untimed: first launches)
+    assert torch.equal(ended, terminated | truncated)
+    reps = max(1, args.steps // K)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        dataset()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    steps = reps * K
+    print(f"complete env (bind_rollout_complete_episodic, K = {K}, max_episode_steps = {M}, {args.reference} references): {n} envs x {steps} steps in {dt:.3f} s = "
+          f"{n * steps / dt / 1e6:.1f} M env-steps/s ({dt / steps * 1e6:.2f} us/step), GAE included; last chunk: {int(terminated.sum())} terminations, "
+          f"{int(truncated.sum())} truncations; kernel: {ps.last_launch().split(' grid')[0]}")
+    print(f"GAE(gamma {gamma}, lambda {lam}) with ended = terminated | truncated: advantage mean {float(advantage.mean()):+.4f} std {float(advantage.std()):.4f}; "
+          f"returns mean {float(returns.mean()):+.3f}")
+    assert torch.isfinite(ret).all() and torch.isfinite(advantage).all() and torch.isfinite(returns).all()
+    assert int(truncated.sum()) > 0 or M > steps
+    episode_report(env)
+    env.close()
 
 
 def rollout_loop(args, env):

@@ -233,6 +233,7 @@ EXPORTS = (
     "gemx_refprofile_rollout_shell", "gemx_refprofile_get_state", "gemx_refprofile_state_bytes", "gemx_refprofile_get_blob", "gemx_refprofile_set_blob",
     "gemx_returns_rows",
     "gemx_set_env_params", "gemx_clear_env_params", "gemx_get_env_params", "gemx_env_params_fields",
+    "gemx_rollout_episodic",
 )
 
 
@@ -334,6 +335,7 @@ def load():
     L.gemx_clear_env_params.argtypes = [vp]
     L.gemx_get_env_params.argtypes = [vp, vp, vp]
     L.gemx_env_params_fields.argtypes = [vp]
+    L.gemx_rollout_episodic.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]
     L.gemx_get_switch_state.argtypes = [vp, vp, vp]

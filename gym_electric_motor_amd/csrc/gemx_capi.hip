@@ -1165,12 +1165,17 @@ int gemx_set_switch_state(gemx_handle *h, const uint8_t *in_dev, void *stream) {
 // ---- per-env motor / load / supply parameters (include/gemx.h; gemx_envparams.hpp, gemx_envparams.hip) ------------------------------------
 // the per-env units, libgemx_ep<S>_<C>.so beside this library: loaded like the stepping units, by the first gemx_set_env_params that needs one
 typedef int (*gemx_ep_unit_init_fn)(unsigned long long handle_bytes, int abi, void (*set_error)(const char *));
-struct EpUnitLib { void *dl = nullptr; gemx_ep_unit_launch_fn launch = nullptr; };
-static EpUnitLib g_ep_units[8][12];
-static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) {
-    if (s < 0 || s >= 8 || c < 0 || c >= 12) return fail(GEMX_ERR_ARG, "per-env parameters: unsupported system/converter combination %d/%d", s, c);
+extern "C++" {  // (templates: this part of the file sits inside the C ABI's linkage block)
+template <class Fn> struct SideUnitLib { void *dl = nullptr; Fn launch = nullptr; };
+static SideUnitLib<gemx_ep_unit_launch_fn> g_ep_units[8][12];
+// ... and the episodic rollout units, libgemx_tl<S>_<C>.so: the same loader under another name, by the first gemx_rollout_episodic
+static SideUnitLib<gemx_tl_unit_launch_fn> g_tl_units[8][12];
+// tag: "ep" | "tl" (file name libgemx_<tag><S>_<C>.so, symbols gemx_<tag>_unit_init / gemx_<tag>_unit_launch); feature, what: the messages' names
+template <class Fn>
+static int load_side_unit(SideUnitLib<Fn> (&units)[8][12], const char *tag, const char *feature, const char *what, int s, int c, Fn *out) {
+    if (s < 0 || s >= 8 || c < 0 || c >= 12) return fail(GEMX_ERR_ARG, "%s: unsupported system/converter combination %d/%d", feature, s, c);
     std::lock_guard<std::mutex> lock(g_units_mu);
-    EpUnitLib &u = g_ep_units[s][c];
+    SideUnitLib<Fn> &u = units[s][c];
     if (u.launch == nullptr) {
         char dir[1024] = "";
         const char *ud = getenv("GEMX_UNIT_DIR");
@@ -1183,16 +1188,18 @@ static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) {
             if (slash != nullptr) *slash = 0;
             else snprintf(dir, sizeof(dir), ".");
         }
-        char path[1200];
-        snprintf(path, sizeof(path), "%s/libgemx_ep%d_%d.so", dir, s, c);
+        char path[1200], init_name[64], launch_name[64];
+        snprintf(path, sizeof(path), "%s/libgemx_%s%d_%d.so", dir, tag, s, c);
+        snprintf(init_name, sizeof(init_name), "gemx_%s_unit_init", tag);
+        snprintf(launch_name, sizeof(launch_name), "gemx_%s_unit_launch", tag);
         void *dl = dlopen(path, RTLD_NOW | RTLD_LOCAL);
         if (dl == nullptr) {
             const char *e = dlerror();
-            return fail(GEMX_ERR_ARG, "per-env parameter unit %s cannot be loaded (%s): the package's build is incomplete (python -m gym_electric_motor_amd.build)", path, e ? e : "?");
+            return fail(GEMX_ERR_ARG, "%s unit %s cannot be loaded (%s): the package's build is incomplete (python -m gym_electric_motor_amd.build)", what, path, e ? e : "?");
         }
-        auto init = (gemx_ep_unit_init_fn)dlsym(dl, "gemx_ep_unit_init");
-        auto launch = (gemx_ep_unit_launch_fn)dlsym(dl, "gemx_ep_unit_launch");
-        if (init == nullptr || launch == nullptr) { dlclose(dl); return fail(GEMX_ERR_ARG, "%s exports no gemx_ep_unit_init / gemx_ep_unit_launch", path); }
+        auto init = (gemx_ep_unit_init_fn)dlsym(dl, init_name);
+        auto launch = (Fn)dlsym(dl, launch_name);
+        if (init == nullptr || launch == nullptr) { dlclose(dl); return fail(GEMX_ERR_ARG, "%s exports no %s / %s", path, init_name, launch_name); }
         if (init((unsigned long long)sizeof(gemx_handle), GEMX_ABI_VERSION, unit_set_error) != GEMX_OK) {
             dlclose(dl);
             return fail(GEMX_ERR_ARG, "%s was built from other sources than libgemx.so (handle layout / ABI differ): rebuild the package", path);
@@ -1203,6 +1210,9 @@ static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) {
     *out = u.launch;
     return GEMX_OK;
 }
+}  // extern "C++"
+static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) { return load_side_unit(g_ep_units, "ep", "per-env parameters", "per-env parameter", s, c, out); }
+static int load_tl_unit(int s, int c, gemx_tl_unit_launch_fn *out) { return load_side_unit(g_tl_units, "tl", "episodic rollout", "episodic rollout", s, c, out); }
 
 int gemx_env_params_fields(const gemx_handle *h) { return h ? ep_fields(h->cfg.system_kind) : GEMX_ERR_ARG; }
 
@@ -1298,10 +1308,45 @@ int gemx_get_env_params(gemx_handle *h, void *out_dev, void *stream) {
     return GEMX_OK;
 }
 
+// ---- episodic rollout: K fused steps with the episode time limit inside the launch (include/gemx.h; gemx_episodic.hip) ---------------------
+int gemx_rollout_episodic(gemx_handle *h, const void *actions_dev, int32_t K, const int32_t *length_dev, int32_t max_steps, void *obs_out_dev,
+                          uint8_t *terminated_out_dev, uint8_t *truncated_out_dev, uint8_t *ended_out_dev, void *stream) {
+    if (!h) return fail(GEMX_ERR_ARG, "null handle");
+    if (!actions_dev || !length_dev || !obs_out_dev) return fail(GEMX_ERR_ARG, "episodic rollout: actions_dev, length_dev and obs_out_dev must not be null");
+    if (K < 1) return fail(GEMX_ERR_ARG, "episodic rollout: K must be >= 1");
+    if (max_steps < 1) return fail(GEMX_ERR_ARG, "episodic rollout: max_steps must be >= 1 (an env without a time limit takes gemx_rollout)");
+    if (((uintptr_t)obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "episodic rollout: obs_out_dev must be 16-byte aligned");
+    if (((uintptr_t)length_dev & 3u) != 0) return fail(GEMX_ERR_ARG, "episodic rollout: length_dev must be 4-byte aligned");
+    const gemx_config &c = h->cfg;
+    // what the episodic kernel does not serve: refused here, before anything is launched
+    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "episodic rollout: fp32 handles only (the fp64 build is a diagnostic; step it)");
+    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "episodic rollout: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver");
+    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "episodic rollout: solver kind %d is not built; EulerSolver or RK4Solver", c.solver_kind);
+    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "episodic rollout: a converter interlocking time (dead time) is not available");
+    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "episodic rollout: a DeadTimeProcessor (action_delay > 0) is not available");
+    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "episodic rollout: an RCVoltageSupply is not available");
+    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "episodic rollout: random initial states are not available (an env restarts inside the launch from the handle's one initial state)");
+    gemx::DeviceGuard guard(h->device);
+    gemx_tl_unit_launch_fn fn = nullptr;
+    if (const int rc = load_tl_unit(c.system_kind, h->conv_unit, &fn)) return rc;
+    int linmap_built = 0;
+    const int rc = fn(h, actions_dev, K, length_dev, max_steps, obs_out_dev, terminated_out_dev, truncated_out_dev, ended_out_dev, (hipStream_t)stream, &linmap_built);
+    if (rc != GEMX_OK) return rc;
+    h->steps_total += (unsigned long long)K;
+    char key[256];
+    snprintf(key, sizeof(key), "episodic_rollout_kernel<%d, %d, %d, %d, %s, float>", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver, h->ll.d ? "true" : "false");
+    gemx_cov_note(key);
+    if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
+    return GEMX_OK;
+}
+
 const char *gemx_last_launch(const gemx_handle *h) {
     if (!h) return "";
     const auto &l = h->ll;
-    if (l.pipe == EP_LAUNCH_STEP || l.pipe == EP_LAUNCH_ROLLOUT)
+    if (l.pipe == EP_LAUNCH_EPISODIC)
+        snprintf(h->last_launch, sizeof(h->last_launch), "gemx::episodic_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,f32> grid=%lld x %d threads, K=%d, max_steps=%d, unit libgemx_tl%d_%d.so%s",
+                 l.sys, l.conv, l.load, l.solver, l.d, l.blocks, l.threads, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
+    else if (l.pipe == EP_LAUNCH_STEP || l.pipe == EP_LAUNCH_ROLLOUT)
         snprintf(h->last_launch, sizeof(h->last_launch), "gemx::%s<sys=%d,conv=%d,load=%d,solver=%d,f32> grid=%lld x %d threads, K=%d, per-env parameters (%d fields)",
                  l.pipe == EP_LAUNCH_STEP ? "envparams_step_kernel" : "envparams_rollout_kernel", l.sys, l.conv, l.load, l.solver, l.blocks, l.threads, l.k, h->envp_fields);
     else if (l.pipe == 3)

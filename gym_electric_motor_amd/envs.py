@@ -417,6 +417,121 @@ class BatchedElectricMotorEnv:
         return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), episodes, pipe.bind_after_rollout(raw, done_out, None, obs_out, stream),
                                  result=(obs_out, done_out) + ((stats,) if stats else ()))
 
+    # ------------------------------------------------------------------ episodic rollouts: the time limit inside the fused launch
+    def _episodic_actions(self, what, actions, convert):
+        """The checks every episodic entry point makes before anything is launched (they need no device), then the action tensor the
+        kernel reads: -> (K, actions).  `convert`: the eager entry points take what `rollout` takes; the bound ones a device tensor."""
+        self.pipeline.need_episodic()
+        if not hasattr(actions, "shape") or len(actions.shape) < 1:
+            raise ValueError(f"{what} needs actions [K, N, A] / [K, N]")
+        K = int(actions.shape[0])
+        if K < 1:
+            raise ValueError(f"{what}: K must be >= 1, not {K}")
+        ps = self.physical_system
+        torch = bps._torch()
+        if torch.is_tensor(actions) and actions.dtype is torch.float16:
+            from .episodes import episodic_refusal
+
+            raise NotImplementedError(episodic_refusal(ps, "a half-precision action tensor (fp32 actions)"))
+        if convert and getattr(ps, "_handle", None) is not None:
+            actions = ps._actions_to_device(actions, (K, ps._n_envs))
+        return K, actions
+
+    def _check_tensor(self, what, t, name, dtype, shape=None, numel=None):
+        """One tensor of a bound or eager call, in `_check_complete`'s order and wording: dtype, shape, contiguity, device (needs no device)."""
+        torch = bps._torch()
+        ps = self.physical_system
+        tdev = getattr(ps, "_tdev", None) or torch.device("cuda", ps._device)
+        if not torch.is_tensor(t):
+            raise ValueError(f"{what}: {name} must be a tensor")
+        if t.dtype != dtype:
+            raise ValueError(f"{what}: {name} must have dtype {dtype}, not {t.dtype}")
+        if (shape is not None and tuple(t.shape) != shape) or (numel is not None and t.numel() != numel):
+            raise ValueError(f"{what}: {name} must have shape {shape if shape is not None else f'of {numel} elements'}, not {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what}: {name} must be contiguous")
+        if t.device != tdev:
+            raise ValueError(f"{what}: {name} must be on device {tdev}, not {t.device}")
+
+    def _check_episodic(self, what, K, actions=None, obs_out=None, **masks):
+        """The tensors of an episodic rollout: actions (the bound entry points), the trajectory, the uint8 [K, N] masks by name."""
+        torch = bps._torch()
+        ps = self.physical_system
+        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
+        if actions is not None:
+            space = ps.action_space
+            discrete = hasattr(space, "n") or hasattr(space, "nvec")
+            self._check_tensor(what, actions, "actions", torch.uint8 if discrete else tdtype, numel=K * ps.n_envs * (1 if discrete else int(space.shape[0])))
+        if obs_out is not None:
+            stage = self.observation_stage
+            n_state = len(ps.state_names) if stage is None else stage.n_out
+            shape = (K, ps.n_envs, n_state) if getattr(ps, "_obs_layout", "aos") == "aos" else (K, n_state, ps.n_envs)
+            self._check_tensor(what, obs_out, "obs_out", tdtype, shape)
+        for name, t in masks.items():
+            if t is not None:
+                self._check_tensor(what, t, name, torch.uint8, (K, ps.n_envs))
+
+    def _need_device(self):
+        if getattr(self.physical_system, "_handle", None) is None:
+            raise bps._lib.GemxError("the physical system has no device handle (built with _defer_create, or closed)")
+
+    def _episodic_physics(self, a, raw, terminated, truncated, ended, stream):
+        """-> the first two launches of every episodic rollout: the reset a truncating `step()` left pending in the stage's `reset_mask`
+        (the masked `gemx_reset`), then the episodic physics reading the stage's `length`."""
+        pipe = self.pipeline
+        return bps._lib.sequence(pipe.bind_before_step(stream),
+                                 self.physical_system.bind_rollout_episodic(a, pipe.episode.length, pipe.episode.max_steps, raw, terminated, truncated, ended, stream=stream))
+
+    def bind_rollout_episodic(self, actions, obs_out, terminated_out, truncated_out, stream=None, episode_statistics=None):
+        """-> zero-argument launch() of `rollout_episodic` on fixed tensors (every output must be given: a bound launch allocates
+        nothing); `launch()` returns `(obs_out, terminated_out, truncated_out[, stats])`.  Every launch goes to ONE stream and nothing
+        lives on the host, so it can be captured with `torch.cuda.graph` and replayed: the counters carry from replay to replay.
+        episode_statistics: dict(ended=, finished_return=, finished_length=) of [K, N] tensors the episode stage's pass writes."""
+        K, a = self._episodic_actions("bind_rollout_episodic", actions, convert=False)
+        for t, name in ((obs_out, "obs_out"), (terminated_out, "terminated_out"), (truncated_out, "truncated_out")):
+            if t is None:
+                raise ValueError(f"bind_rollout_episodic: {name} must be given (a bound launch allocates nothing)")
+        if episode_statistics is True:
+            raise ValueError("bind_rollout_episodic: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
+        self._check_episodic("bind_rollout_episodic", K, a, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
+        self._need_device()
+        ps, pipe = self.physical_system, self.pipeline
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        raw = pipe.raw_rows(K, obs_out)
+        episodes, stats = pipe.bind_episode_rows(terminated_out, outputs=episode_statistics, stream=stream)  # (the physics-only env: lengths, no reward)
+        ended = stats["ended"] if stats else pipe.ended_scratch
+        return bps._lib.sequence(self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream), episodes,
+                                 pipe.bind_after_rollout(raw, ended, None, obs_out, stream), pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream),
+                                 result=(obs_out, terminated_out, truncated_out) + ((stats,) if stats else ()))
+
+    def rollout_episodic(self, actions, obs_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
+        """K fused control steps of an env built with `max_episode_steps=M`, the time limit INSIDE the launch (csrc/gemx_episodic.hip):
+        -> (traj [K, N, S_out], terminated [K, N], truncated [K, N][, stats]) uint8 masks -- what K calls of `step(actions[k])` return,
+        stacked, bit for bit; the row of a step that ended is the final state, and the env restarts within the launch.  The launches, on
+        the current stream: the reset a truncating `step()` left pending; the episodic physics; the episode stage's pass over the rows;
+        the pipeline's launches (a FluxObserver resets on the ENDED rows); row K-1 into `env.truncated`, with the stage's `reset_mask`
+        cleared.  `step()` and further rollouts continue the same episodes.  On an env without a time limit: ValueError.
+        episode_statistics (an env built with `episode_statistics=True`): as `rollout` takes it."""
+        K, a = self._episodic_actions("rollout_episodic", actions, convert=True)
+        self._check_episodic("rollout_episodic", K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
+        self._need_device()
+        torch = bps._torch()
+        ps = self.physical_system
+        mask = lambda t: torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if t is None else t  # noqa: E731
+        if obs_out is None and self.observation_stage is None:
+            obs_out = torch.empty((K,) + tuple(ps._obs.shape), dtype=ps._tdtype, device=ps._tdev)
+        terminated_out, truncated_out = mask(terminated_out), mask(truncated_out)
+        pipe = self.pipeline
+        stream = torch.cuda.current_stream(ps._tdev)
+        raw = pipe.raw_rows(K, obs_out)
+        episodes, stats = pipe.bind_episode_rows(terminated_out, outputs=episode_statistics, stream=stream)
+        ended = stats["ended"] if stats else pipe.ended_scratch
+        self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream)()
+        episodes()
+        traj = pipe.after_rollout(raw, ended, None, obs_out)
+        pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream)()
+        return (traj, terminated_out, truncated_out) + ((stats,) if stats else ())
+
     def close(self):
         self.pipeline.close()
         self.physical_system.close()
@@ -616,17 +731,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 check(t, name, dtype, shape)
         return K
 
-    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False, episodes=None):
+    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False, episodes=None, restart=None):
         """-> the launchers that follow the physics of a complete K-step rollout, in order, on fixed tensors: the generators in the shell's
         order on the done mask; the reward of row k against the references shown before step k; `episodes` (the episode stage's pass over
         the done and reward rows, directly behind the launch that completes them); the pipeline's launches over the stored rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
-        rollouts continue from it)."""
+        rollouts continue from it).  restart [K, N]: the rows the generators restart on and the flux observer resets on, where they are not
+        `done_out` -- the ENDED rows of an episodic rollout, whose reward pass still reads the terminated rows `done_out`."""
         torch = bps._torch()
         ps, gen = self.physical_system, self.reference_generator
+        restart = done_out if restart is None else restart
         if eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
-            generators = lambda: gen.rollout_shell(K, done_out, out=refs_out)  # noqa: E731
+            generators = lambda: gen.rollout_shell(K, restart, out=refs_out)  # noqa: E731
         else:
-            generators = gen.bind_rollout_shell(done_out, refs_out, stream=stream)
+            generators = gen.bind_rollout_shell(restart, refs_out, stream=stream)
         reward = self.bind_reward_rows(raw, refs_out, done_out, reward_out, stream=stream)
         shown, last = self._refs, refs_out[K - 1]
 
@@ -637,7 +754,7 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 with _on(stream):
                     shown.copy_(last)
 
-        return generators, reward, episodes, self.pipeline.bind_after_rollout(raw, done_out, refs_out, state_out, stream), show
+        return generators, reward, episodes, self.pipeline.bind_after_rollout(raw, restart, refs_out, state_out, stream), show
 
     def bind_reward_rows(self, rows, refs_rows, done, reward_out, stream=None):
         """-> zero-argument launch() of the reward pass (`gemx_reward_rows`) on fixed tensors: the base system's rows [K, N, S] of a
@@ -718,6 +835,73 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         episodes, stats = self.pipeline.bind_episode_rows(done_out, reward_out, episode_statistics, stream)
         return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), *self._tail(K, raw, *outs, stream, episodes=episodes),
                                  result=outs + ((stats,) if stats else ()))
+
+    # ------------------------------------------------------------------ complete episodic rollouts: the time limit inside the fused launch
+    def _bind_complete_episodic(self, K, a, outs, truncated_out, stream, episode_statistics, eager=False):
+        """-> launch() of a complete episodic rollout on fixed tensors, all on `stream`, in this order: the reset a truncating `step()` left
+        pending; the episodic physics; the generators' `rollout_shell` on the ENDED rows; the reward pass on the TERMINATED rows; the
+        episode stage's pass over the terminated and reward rows; the pipeline's launches, the flux observer resetting on the ended rows;
+        row K-1 into the references shown -- and into the stage's truncated / ended bytes, with its `reset_mask` cleared."""
+        pipe = self.pipeline
+        state_out, refs_out, reward_out, terminated_out = outs
+        raw = pipe.raw_rows(K, state_out)
+        episodes, stats = pipe.bind_episode_rows(terminated_out, reward_out, episode_statistics, stream)
+        ended = stats["ended"] if stats else pipe.ended_scratch
+        result = outs + (truncated_out,) + ((stats,) if stats else ())
+        return bps._lib.sequence(self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream),
+                                 *self._tail(K, raw, *outs, stream, eager=eager, episodes=episodes, restart=ended),
+                                 pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream), result=result)
+
+    def rollout_complete_episodic(self, actions, state_out=None, refs_out=None, reward_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
+        """`rollout_complete` for an env built with `max_episode_steps=M`, the time limit INSIDE the fused launch (csrc/gemx_episodic.hip):
+        -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], terminated [K, N], truncated [K, N][, stats]) -- what K calls of
+        `step(actions[k])` return, stacked, bit for bit: the row of a step that ended is the final state, an ended env restarts within the
+        launch, its generators restart and its flux observer resets with it, and a step that terminates and reaches the limit at once
+        counts as terminated.  A reset a truncating `step()` left pending is applied first; afterwards `env.truncated` shows row K-1 and no
+        reset is pending, so `step()` and further rollouts continue the same episodes.  `ended = terminated | truncated` is what
+        `ga.advantages(..., ended=)` takes.  On an env without a time limit: ValueError; what the kernel does not serve:
+        NotImplementedError (episodes.episodic_refusal).  episode_statistics: as `rollout_complete` takes it."""
+        K, a = self._episodic_actions("rollout_complete_episodic", actions, convert=True)
+        self._check_complete_episodic("rollout_complete_episodic", K, None, state_out, refs_out, reward_out, terminated_out, truncated_out)
+        self._need_device()
+        torch = bps._torch()
+        ps = self.physical_system
+        outs = tuple(torch.empty(shape, dtype=torch.uint8 if i == 3 else ps._tdtype, device=ps._tdev) if t is None else t
+                     for i, (t, shape) in enumerate(zip((state_out, refs_out, reward_out, terminated_out), self._complete_shapes(K))))
+        truncated_out = torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if truncated_out is None else truncated_out
+        return self._bind_complete_episodic(K, a, outs, truncated_out, torch.cuda.current_stream(ps._tdev), episode_statistics, eager=True)()
+
+    def bind_rollout_complete_episodic(self, actions, state_out, refs_out, reward_out, terminated_out, truncated_out, stream=None, episode_statistics=None):
+        """-> zero-argument launch() of `rollout_complete_episodic` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
+        terminated_out, truncated_out[, stats])`.  Everything is resolved here, once: a call allocates nothing, never synchronises and goes
+        to ONE stream, so it can be captured with `torch.cuda.graph` and replayed -- the episode counters, like the physics and the
+        generators, carry from replay to replay.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
+        K, a = self._episodic_actions("bind_rollout_complete_episodic", actions, convert=False)
+        outs = (state_out, refs_out, reward_out, terminated_out)
+        for t, name in zip(outs + (truncated_out,), ("state_out", "refs_out", "reward_out", "terminated_out", "truncated_out")):
+            if t is None:
+                raise ValueError(f"bind_rollout_complete_episodic: {name} must be given (a bound launch allocates nothing)")
+        if episode_statistics is True:
+            raise ValueError("bind_rollout_complete_episodic: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
+        self._check_complete_episodic("bind_rollout_complete_episodic", K, a, *outs, truncated_out)
+        if isinstance(self.reference_generator, ReplayReferenceGenerator):
+            self.reference_generator.bind_rollout_shell(terminated_out, refs_out)  # (raises: cannot be captured)
+        self._need_device()
+        ps = self.physical_system
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        return self._bind_complete_episodic(K, a, outs, truncated_out, stream, episode_statistics)
+
+    def _check_complete_episodic(self, what, K, actions, state_out, refs_out, reward_out, terminated_out, truncated_out):
+        """`_check_complete`'s validation for the episodic entry points (which that method refuses: it serves the env without a time limit)."""
+        torch = bps._torch()
+        ps = self.physical_system
+        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
+        self._check_episodic(what, K, actions)
+        shapes = self._complete_shapes(K)
+        for t, name, dtype, shape in ((state_out, "state_out", tdtype, shapes[0]), (refs_out, "refs_out", tdtype, shapes[1]), (reward_out, "reward_out", tdtype, shapes[2]),
+                                      (terminated_out, "terminated_out", torch.uint8, shapes[3]), (truncated_out, "truncated_out", torch.uint8, shapes[3])):
+            if t is not None:
+                self._check_tensor(what, t, name, dtype, shape)
 
     def close(self):
         self.reference_generator.close()

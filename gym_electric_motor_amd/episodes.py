@@ -12,7 +12,17 @@ reference generators restart on and the flux observer resets on: a truncated env
 
 `rows(done [K, N], reward [K, N])` is the same arithmetic over the stored rows of a K-step rollout in one pass -- bit for bit what K
 calls of `step` leave -- and writes `ended [K, N]` and, optionally, `finished_return` (float64) / `finished_length` (int32) `[K, N]`: an
-episode's totals at the row where it ended, 0 elsewhere.  A time limit INSIDE a fused K-step launch is not built (ROLLOUT_REFUSAL).
+episode's totals at the row where it ended, 0 elsewhere.
+
+The time limit INSIDE a fused K-step launch: `rollout`, `bind_rollout`, `rollout_complete` and `bind_rollout_complete` refuse an env with a
+time limit (ROLLOUT_REFUSAL) -- their kernels cannot restart an env on a mask they have not seen.  The episodic entry points can
+(`rollout_episodic`, `bind_rollout_episodic`, `rollout_complete_episodic`, `bind_rollout_complete_episodic`; csrc/gemx_episodic.hip,
+gemx_rollout_episodic): truncation is `length >= max_steps and not done`, and `length` depends on nothing but the env's own done history,
+so the kernel that steps the env produces the mask itself.  It reads this stage's `length`, keeps it in a register, applies the rule above
+behind every control step, restarts every ended env within the launch and writes terminated, truncated and ended [K, N]; `rows` then runs
+behind it on the same terminated and reward rows and moves the counters by the same rule from the same value -- the stage stays the one
+owner of its state.  `after_episodic_rollout` leaves the stage as K steps would, except that no reset is pending: they have all happened.
+What the kernel does not serve is listed by `episodic_refusal`.
 """
 import ctypes as C
 import operator
@@ -21,8 +31,34 @@ from . import _lib
 
 ROLLOUT_REFUSAL = ("fused K-step rollouts cannot run with an episode time limit (max_episode_steps): a truncated env restarts from its reset state, and a "
                    "fused K-step launch cannot restart an env on a mask it has not seen; step the env (step / bind_step, HIP-graph capturable), or build "
-                   "it with episode_statistics=True alone: the rollouts then run the statistics pass over their stored rows")
+                   "it with episode_statistics=True alone: the rollouts then run the statistics pass over their stored rows.  The episodic entry points "
+                   "keep the time limit inside the launch: rollout_episodic / bind_rollout_episodic, rollout_complete_episodic / bind_rollout_complete_episodic")
+EPISODIC_REFUSAL = "episodic rollouts (the episode time limit inside a fused K-step launch) are not available with "
+NO_TIME_LIMIT = "episodic rollouts need an env built with a time limit, make(..., max_episode_steps=M); without one rollout / rollout_complete serve"
 FIELDS = ("length", "ret", "last_length", "last_ret", "n_finished")
+
+
+def episodic_refusal(system, what=None):
+    """None, or the message of what the episodic rollout kernel does not serve for this physical system (needs no device: raised before
+    anything is launched).  `what`: the message for a refused way of CALLING it (half-precision actions, last_only, synthetic actions)."""
+    if what is not None:
+        return EPISODIC_REFUSAL + what
+    cfg = system._cfg
+    if cfg.dtype == _lib.F64:
+        return EPISODIC_REFUSAL + "dtype='float64' (the fp64 build is a diagnostic: step it)"
+    if cfg.solver_flags & _lib.SOLVER_ADAPTIVE:
+        return EPISODIC_REFUSAL + "the error-controlled Dormand-Prince solver (ScipyOdeSolver): EulerSolver or RK4Solver"
+    if cfg.solver_kind not in (_lib.SOLVER_EULER, _lib.SOLVER_RK4):
+        return EPISODIC_REFUSAL + "DormandPrince5Solver: EulerSolver or RK4Solver"
+    if cfg.interlocking_time > 0:
+        return EPISODIC_REFUSAL + "a converter interlocking time (dead time)"
+    if cfg.action_delay > 0:
+        return EPISODIC_REFUSAL + "a DeadTimeProcessor"
+    if cfg.supply_kind != _lib.SUPPLY_IDEAL:
+        return EPISODIC_REFUSAL + "an RCVoltageSupply"
+    if cfg.init_kind != _lib.INIT_CONST:
+        return EPISODIC_REFUSAL + "random initial states (an env restarts inside the launch from the system's one initial state)"
+    return None
 
 
 def check_max_episode_steps(value):
@@ -161,6 +197,29 @@ class EpisodeStage:
         new = lambda dtype: torch.empty(tuple(done.shape), dtype=dtype, device=self._tdev)  # noqa: E731
         return self.bind_rows(done, reward, new(torch.uint8) if ended is None else ended, new(torch.float64) if finished_return is None else finished_return,
                               new(torch.int32) if finished_length is None else finished_length, stream)()
+
+    def bind_after_episodic_rollout(self, truncated_rows, ended_rows, stream=None):
+        """-> zero-argument launch() behind an episodic rollout and its `rows` pass: `truncated` and `ended` [N] take row K-1 of
+        truncated_rows / ended_rows [K, N] (what the last of K steps would have left: `env.truncated` shows it), and `reset_mask` is
+        cleared -- every ended env has restarted inside the launch, so the reset in front of the next step's physics has nothing to do.
+        Three asynchronous device operations on `stream`, capturable."""
+        import torch
+
+        self._need_handle()
+        shape = (int(truncated_rows.shape[0]), self.n_envs)
+        self._check(truncated_rows, shape, "truncated", torch.uint8)
+        self._check(ended_rows, shape, "ended", torch.uint8)
+        stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)
+        truncated, ended, mask, last_t, last_e = self.truncated, self.ended, self.reset_mask, truncated_rows[shape[0] - 1], ended_rows[shape[0] - 1]
+
+        def launch(_current=torch.cuda.current_stream, _on=torch.cuda.stream):
+            if _current(self._tdev) == stream:
+                truncated.copy_(last_t), ended.copy_(last_e), mask.zero_()
+            else:
+                with _on(stream):
+                    truncated.copy_(last_t), ended.copy_(last_e), mask.zero_()
+
+        return launch
 
     def restart(self):
         """`env.reset()`: every running episode is dropped (length = 0, ret = 0) and no env waits for a restart; the totals of finished

@@ -362,6 +362,24 @@ class ObservationPipeline:
 
             raise NotImplementedError(ROLLOUT_REFUSAL)
 
+    def need_episodic(self):
+        """What the episodic rollouts (the time limit inside the fused launch) need of this env, checked before anything is launched and
+        without a device: a time limit (ValueError without one), no stage whose mask another launch decides, and a physical system the
+        episodic kernel serves (NotImplementedError, one message each: episodes.episodic_refusal)."""
+        from .episodes import EPISODIC_REFUSAL, NO_TIME_LIMIT, episodic_refusal
+
+        if self.episode is None or not self.episode.max_steps:
+            raise ValueError(NO_TIME_LIMIT)
+        if self.noise is not None:
+            raise NotImplementedError(EPISODIC_REFUSAL + "a StateNoiseProcessor: its done mask is decided on the noisy row by another launch, which a "
+                                      "fused launch has not seen")
+        if self.flux_action:
+            raise NotImplementedError(EPISODIC_REFUSAL + "a FluxOrientedDqToAbcActionProcessor: each step's action frame comes from the previous step's "
+                                      "observation")
+        why = episodic_refusal(self.physical_system)
+        if why is not None:
+            raise NotImplementedError(why)
+
     def _scratch(self, name, shape, dtype=None):
         ps, buf = self.physical_system, getattr(self, name)
         if buf is None or tuple(buf.shape) != shape:

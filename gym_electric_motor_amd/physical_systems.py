@@ -787,6 +787,40 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
 
         return launch
 
+    def bind_rollout_episodic(self, actions, length, max_steps, obs_out, terminated_out, truncated_out, ended_out, stream=None):
+        """A zero-argument `launch()` of `gemx_rollout_episodic` on fixed tensors: K fused control steps with the episode time limit
+        `max_steps` INSIDE the launch (csrc/gemx_episodic.hip) -- per env `length += 1; truncated = length >= max_steps and not
+        terminated`, and every ended env restarts from the reset state within the launch.  actions [K, N, A] / [K, N] as `bind_rollout`
+        takes them (no float16); length [N] int32, the steps of every env's running episode, READ only (the episode stage's rows pass
+        behind this launch moves the counters: episodes.py); obs_out [K, N, S_out] (or [K, S_out, N]); terminated_out, truncated_out,
+        ended_out [K, N] uint8.  The tensors are the caller's to get right -- contiguous, of these dtypes, on the system's device: the
+        envs' `*_episodic` methods validate them and raise what the kernel does not serve before anything is launched; called directly,
+        the C ABI refuses such a handle.  `launch()` returns `(obs_out, terminated_out, truncated_out, ended_out)`."""
+        from .episodes import check_max_episode_steps
+
+        M = check_max_episode_steps(max_steps)
+        if M is None:
+            raise ValueError("bind_rollout_episodic needs max_steps >= 1")
+        if self._handle is None:
+            raise _lib.GemxError("the physical system has no device handle (built with _defer_create, or closed)")
+        torch = _torch()
+        K, a = int(actions.shape[0]), actions
+        stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)  # (the Stream OBJECT is kept: its raw handle must not dangle)
+        call, check = self._L.gemx_rollout_episodic, _lib.check
+        args = (C.c_void_p(a.data_ptr()), K, C.c_void_p(length.data_ptr()), M, C.c_void_p(obs_out.data_ptr()), C.c_void_p(terminated_out.data_ptr()),
+                C.c_void_p(truncated_out.data_ptr()), C.c_void_p(ended_out.data_ptr()), C.c_void_p(stream.cuda_stream))
+        keep = (a, length, obs_out, terminated_out, truncated_out, ended_out, stream)
+        out = (obs_out, terminated_out, truncated_out, ended_out)
+
+        def launch(_args=args, _call=call, _keep=keep):
+            rc = _call(self._handle, *_args)  # (the handle is read per call: None after close() -> the C ABI's "null handle" error)
+            if rc:
+                check(rc)
+            self._k += K
+            return out
+
+        return launch
+
     def rollout(self, actions, obs_out=None, done_out=None, last_only=False, references=None, reward_out=None):
         """K fused control steps in one launch.  actions: [K, N, A] / [K, N]; returns (obs [K, N, S_out], done [K, N])
         device tensors (or the last step's [N, S_out], [N] with last_only=True).

@@ -768,6 +768,30 @@ int gemx_clear_env_params(gemx_handle *h);
 int gemx_get_env_params(gemx_handle *h, void *out_dev, void *stream);
 int gemx_env_params_fields(const gemx_handle *h);
 
+/* EPISODIC ROLLOUT: K fused control steps WITH the episode time limit inside the launch (new entry point only, ABI number unchanged).
+ * Truncation is `length >= max_steps && !done`, and an env's `length` depends on its own done history alone, so the kernel produces the
+ * mask it restarts on.  Per env and step, behind the control step (gemx_episode_step's rule):
+ *     length += 1;  truncated = length >= max_steps && !done;  ended = done | truncated;  where ended: length = 0, the env restarts
+ * Every ended env restarts from the handle's initial state, whatever auto_reset says (with a time limit the stepped path restarts them all:
+ * in the stepping kernel or by the masked gemx_reset).  The switching state survives, as it does there.
+ *   actions_dev  [K][N][A] R | [K][N] uint8, as gemx_rollout reads them
+ *   length_dev   [N] int32: every env's steps in its running episode (the episode stage's `length` field).  READ ONLY: run
+ *                gemx_episode_rows behind this call on terminated_out_dev (and the rewards) with the same max_steps; it moves the counters
+ *                by the same rule from the same value
+ *   obs_out_dev  [K][N][S_out] | [K][S_out][N] R (16-byte aligned): the row of a step that ended is the final state, not the reset state
+ *   terminated_out_dev, truncated_out_dev, ended_out_dev   [K][N] uint8; each may be NULL
+ * With a parameter table (gemx_set_env_params) every lane steps with its column, as envparams_step_kernel does; without one the lane takes
+ * the code path of gemx_step's kernel (the one-step map of the constant-speed loads included).  Either way the rows equal, bit for bit, K
+ * calls of gemx_step with gemx_episode_step and the masked gemx_reset between them.  The kernels live in libgemx_tl<S>_<C>.so beside the
+ * library, loaded by the first call that needs one; gemx_last_launch names episodic_rollout_kernel and that unit.
+ * Asynchronous on `stream`, allocates nothing, can be captured in a HIP graph (a FIRST launch of a handle that is being captured goes
+ * without the one-step map, as a captured first gemx_step does).
+ * GEMX_ERR_ARG, naming the episodic rollout, before anything is launched: a NULL handle / actions / length / obs, K < 1, max_steps < 1, a
+ * misaligned obs_out_dev or length_dev, and handles the kernel does not serve: fp64, the Dormand-Prince solver (fixed step or
+ * GEMX_SOLVER_ADAPTIVE), interlocking_time > 0, action_delay > 0, GEMX_SUPPLY_RC, random initial states. */
+int gemx_rollout_episodic(gemx_handle *h, const void *actions_dev, int32_t K, const int32_t *length_dev, int32_t max_steps, void *obs_out_dev,
+                          uint8_t *terminated_out_dev, uint8_t *truncated_out_dev, uint8_t *ended_out_dev, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
