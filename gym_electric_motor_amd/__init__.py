@@ -42,6 +42,7 @@ from .flux_observer import FluxObserverStage  # noqa: F401
 from .state_noise import StateNoiseStage  # noqa: F401
 from .episodes import EpisodeStage  # noqa: F401
 from .env_parameters import EnvParameters  # noqa: F401
+from .policy import MLPPolicy  # noqa: F401
 from .returns import advantages, bind_advantages, bind_discounted_returns, discounted_returns  # noqa: F401
 from .observation import ObservationStage  # noqa: F401
 from .physical_systems import (  # noqa: F401

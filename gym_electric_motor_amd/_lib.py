@@ -210,6 +210,27 @@ class GemxReturnsConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("gamma", C.c_double), ("lam", C.c_double), ("flags", C.c_int32)]
 
 
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH, POLICY_MAX_INPUT = 3, 64, 48  # GEMX_POLICY_MAX_*
+POLICY_RELU, POLICY_TANH = 0, 1  # GEMX_POLICY_RELU / GEMX_POLICY_TANH
+POLICY_SQUASH_TANH, POLICY_SQUASH_CLIP = 0, 1  # GEMX_POLICY_SQUASH_*
+
+
+class GemxPolicyConfig(C.Structure):
+    """Mirror of `gemx_policy_config` (include/gemx.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("n_layers", C.c_int32), ("n_in", C.c_int32), ("width", C.c_int32 * POLICY_MAX_LAYERS),
+                ("activation", C.c_int32), ("squash", C.c_int32)]
+
+
+class GemxPolicyCall(C.Structure):
+    """Mirror of `gemx_policy_call` (include/gemx.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("K", C.c_int32), ("n_cols", C.c_int32), ("n_ref", C.c_int32), ("columns", C.c_int32 * POLICY_MAX_INPUT),
+                ("max_steps", C.c_int32), ("reserved", C.c_int32), ("obs0_dev", C.c_void_p), ("refs_dev", C.c_void_p), ("noise_dev", C.c_void_p),
+                ("length_dev", C.c_void_p), ("obs_out_dev", C.c_void_p), ("actions_out_dev", C.c_void_p), ("terminated_out_dev", C.c_void_p),
+                ("truncated_out_dev", C.c_void_p), ("ended_out_dev", C.c_void_p)]
+
+
 def refprofile_state_bytes(n_envs):
     """`gemx_refprofile_state_bytes` restated: the header, then k, s, e as int32 [3][N]."""
     return REFPROFILE_BLOB_HEADER_BYTES + 12 * int(n_envs)
@@ -234,6 +255,7 @@ EXPORTS = (
     "gemx_returns_rows",
     "gemx_set_env_params", "gemx_clear_env_params", "gemx_get_env_params", "gemx_env_params_fields",
     "gemx_rollout_episodic",
+    "gemx_policy_create", "gemx_policy_set_weights", "gemx_policy_destroy", "gemx_rollout_policy", "gemx_policy_tanh_probe",
 )
 
 
@@ -336,6 +358,11 @@ def load():
     L.gemx_get_env_params.argtypes = [vp, vp, vp]
     L.gemx_env_params_fields.argtypes = [vp]
     L.gemx_rollout_episodic.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.gemx_policy_create.argtypes = [C.POINTER(GemxPolicyConfig), vp, vp, C.c_int, C.POINTER(vp)]
+    L.gemx_policy_set_weights.argtypes = [vp, vp, vp]
+    L.gemx_policy_destroy.argtypes = [vp]
+    L.gemx_rollout_policy.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp]
+    L.gemx_policy_tanh_probe.argtypes = [vp, vp, vp, i64, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]
     L.gemx_get_switch_state.argtypes = [vp, vp, vp]

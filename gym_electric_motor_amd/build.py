@@ -21,8 +21,11 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_episodic.hip                   K-step rollout with the episode time limit inside the launch: one kernel, with and without a parameter
                                         table, compiled once per (system, converter unit), fp32, into libgemx_tl<S>_<C>.so, which the first
                                         gemx_rollout_episodic of such a handle loads with dlopen
-The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units and the nine objects of libgemx.so are
-compiled in parallel.
+    gemx_policy.hpp, gemx_policy.hip    the policy rollout: the episodic kernel with a device MLP actor in front of every step, compiled once per
+                                        (system, converter unit), fp32, into libgemx_pl<S>_<C>.so, which the first gemx_rollout_policy of such a
+                                        handle loads with dlopen
+The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units and the nine objects
+of libgemx.so are compiled in parallel.
 """
 import concurrent.futures as cf
 import glob
@@ -40,7 +43,7 @@ SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc",
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
            ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05)]
 SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
-                                           "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip"] + [u[1] for u in SUPPORT]]
+                                           "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")
 
@@ -58,6 +61,11 @@ def ep_unit_lib(s, c):
 def tl_unit_lib(s, c):
     """the shared object of one episodic rollout unit (fp32 only; gemx_capi.hip's load_tl_unit looks beside libgemx.so)"""
     return os.path.join(PKG_DIR, f"libgemx_tl{s}_{c}.so")
+
+
+def pl_unit_lib(s, c):
+    """the shared object of one policy rollout unit (fp32 only; gemx_capi.hip's load_pl_unit looks beside libgemx.so)"""
+    return os.path.join(PKG_DIR, f"libgemx_pl{s}_{c}.so")
 
 
 OBJ_DIR = os.path.join(PKG_DIR, "build")
@@ -86,9 +94,10 @@ def _digest(sources=None, header=None):
 
 
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
-_DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp", "gemx_capi.hip"],
+_DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp", "gemx_policy.hpp", "gemx_capi.hip"],
          "envparams": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
          "episodic": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],
+         "policy": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy.hip"],
          **{name: ["gemx_common.hpp"] + headers + [src] for name, src, headers, _ in SUPPORT}}
 # compile cost of an fp32 unit by system kind (object size, MB: induction > synchronous > DC); fp64 units take the single-wave kernel only
 _COST = {7: 6.0, 2: 5.3, 6: 4.9, 1: 4.5, 5: 4.0, 4: 3.9, 3: 3.5, 0: 3.5}
@@ -108,8 +117,13 @@ def tl_libs():
     return [tl_unit_lib(s, c) for s, c in UNITS]
 
 
+def pl_libs():
+    """the policy rollout units (one per episodic unit: the same system/converter pairs, fp32)"""
+    return [pl_unit_lib(s, c) for s, c in UNITS]
+
+
 def is_stale():
-    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs()):
+    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs() + pl_libs()):
         return True
     return open(STAMP).read().strip() != _digest()
 
@@ -161,6 +175,10 @@ def _build_locked(hipcc, force, verbose, jobs):
         out = tl_unit_lib(s, c)
         cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
                                                   os.path.join(csrc, "gemx_episodic.hip"), "-o", out], "episodic", 0.05))
+    for s, c in UNITS:  # the policy units: the episodic kernel with the actor in front of every step
+        out = pl_unit_lib(s, c)
+        cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
+                                                  os.path.join(csrc, "gemx_policy.hip"), "-o", out], "policy", 0.1))
     objects = []  # of libgemx.so
     for name, src, cost in [("capi", "gemx_capi.hip", 0.3)] + [(u[0], u[1], u[3]) for u in SUPPORT]:
         obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
@@ -186,7 +204,7 @@ def _build_locked(hipcc, force, verbose, jobs):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:  # longest first: the big induction-machine units do not end up as the tail
         list(ex.map(compile_one, sorted(cmds, key=lambda j: -j[3])))
     run([hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-o", LIB] + objects + ["-ldl"])
-    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
+    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pl*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
         if stale not in [j[0] for j in cmds]:
             os.remove(stale)
     with open(STAMP, "w") as fh:

@@ -15,6 +15,7 @@
 
 #include "gemx_common.hpp"
 #include "gemx_envparams.hpp"
+#include "gemx_policy.hpp"
 
 namespace gemx {
 
@@ -1213,6 +1214,9 @@ static int load_side_unit(SideUnitLib<Fn> (&units)[8][12], const char *tag, cons
 }  // extern "C++"
 static int load_ep_unit(int s, int c, gemx_ep_unit_launch_fn *out) { return load_side_unit(g_ep_units, "ep", "per-env parameters", "per-env parameter", s, c, out); }
 static int load_tl_unit(int s, int c, gemx_tl_unit_launch_fn *out) { return load_side_unit(g_tl_units, "tl", "episodic rollout", "episodic rollout", s, c, out); }
+// ... and the policy rollout units, libgemx_pl<S>_<C>.so, by the first gemx_rollout_policy
+extern "C++" { static SideUnitLib<gemx_pl_unit_launch_fn> g_pl_units[8][12]; }
+static int load_pl_unit(int s, int c, gemx_pl_unit_launch_fn *out) { return load_side_unit(g_pl_units, "pl", "policy rollout", "policy rollout", s, c, out); }
 
 int gemx_env_params_fields(const gemx_handle *h) { return h ? ep_fields(h->cfg.system_kind) : GEMX_ERR_ARG; }
 
@@ -1340,10 +1344,147 @@ int gemx_rollout_episodic(gemx_handle *h, const void *actions_dev, int32_t K, co
     return GEMX_OK;
 }
 
+// ---- policy rollout: the episodic rollout with a device MLP actor inside the launch (include/gemx.h; gemx_policy.hpp, gemx_policy.hip) ------
+static int policy_pack(const gemx_policy *p, const float *const *weights, const float *const *biases, std::unique_ptr<float[]> &host) {
+    if (!weights || !biases) return fail(GEMX_ERR_ARG, "policy: weights and biases must not be null");
+    for (int l = 0; l < p->n_layers; ++l)
+        if (!weights[l] || !biases[l]) return fail(GEMX_ERR_ARG, "policy: layer %d has a null weight or bias pointer", l);
+    host.reset(new (std::nothrow) float[(size_t)p->blob_words]);
+    if (!host) return fail(GEMX_ERR_ALLOC, "policy: host staging of %d words failed", p->blob_words);
+    int at = 0;
+    for (int l = 0; l < p->n_layers; ++l) at += gemx::pl_pack_layer(host.get() + at, l, p->n_in, p->width, weights[l], biases[l]);
+    return GEMX_OK;
+}
+int gemx_policy_create(const gemx_policy_config *cfg, const float *const *weights, const float *const *biases, int device, gemx_policy **out) {
+    if (!cfg || !out) return fail(GEMX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (cfg->struct_size != (int32_t)sizeof(gemx_policy_config)) return fail(GEMX_ERR_ARG, "gemx_policy_config size mismatch");
+    if (cfg->n_layers < 1 || cfg->n_layers > GEMX_POLICY_MAX_LAYERS) return fail(GEMX_ERR_ARG, "policy: %d layers; 1 to %d", cfg->n_layers, GEMX_POLICY_MAX_LAYERS);
+    if (cfg->n_in < 1 || cfg->n_in > GEMX_POLICY_MAX_INPUT) return fail(GEMX_ERR_ARG, "policy: input width %d; 1 to %d", cfg->n_in, GEMX_POLICY_MAX_INPUT);
+    for (int l = 0; l < cfg->n_layers; ++l)
+        if (cfg->width[l] < 1 || cfg->width[l] > GEMX_POLICY_MAX_WIDTH) return fail(GEMX_ERR_ARG, "policy: layer %d has width %d; 1 to %d", l, cfg->width[l], GEMX_POLICY_MAX_WIDTH);
+    if (cfg->activation != GEMX_POLICY_RELU && cfg->activation != GEMX_POLICY_TANH) return fail(GEMX_ERR_ARG, "policy: unknown activation %d", cfg->activation);
+    if (cfg->squash != GEMX_POLICY_SQUASH_TANH && cfg->squash != GEMX_POLICY_SQUASH_CLIP) return fail(GEMX_ERR_ARG, "policy: unknown squash %d", cfg->squash);
+    std::unique_ptr<gemx_policy> p(new (std::nothrow) gemx_policy());
+    if (!p) return fail(GEMX_ERR_ALLOC, "policy: allocation failed");
+    p->device = device;
+    p->n_layers = cfg->n_layers;
+    p->n_in = cfg->n_in;
+    for (int l = 0; l < gemx::PL_MAX_LAYERS; ++l) p->width[l] = l < cfg->n_layers ? cfg->width[l] : 0;
+    p->activation = cfg->activation;
+    p->squash = cfg->squash;
+    p->blob_words = gemx::pl_blob_words(p->n_layers, p->n_in, p->width);
+    p->blob = nullptr;
+    std::unique_ptr<float[]> host;
+    if (const int rc = policy_pack(p.get(), weights, biases, host)) return rc;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(GEMX_ERR_DEVICE, "policy: no HIP device %d", device);
+    gemx::DeviceGuard guard(device);
+    if (hipMalloc((void **)&p->blob, sizeof(float) * (size_t)p->blob_words) != hipSuccess) return fail(GEMX_ERR_ALLOC, "hipMalloc(policy weights) failed");
+    if (hipMemcpy(p->blob, host.get(), sizeof(float) * (size_t)p->blob_words, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(p->blob);
+        return fail(GEMX_ERR_DEVICE, "hipMemcpy(policy weights) failed");
+    }
+    *out = p.release();
+    return GEMX_OK;
+}
+int gemx_policy_set_weights(gemx_policy *p, const float *const *weights, const float *const *biases) {
+    if (!p) return fail(GEMX_ERR_ARG, "null policy");
+    std::unique_ptr<float[]> host;
+    if (const int rc = policy_pack(p, weights, biases, host)) return rc;
+    gemx::DeviceGuard guard(p->device);
+    // (synchronous, into the SAME blob: launches already enqueued are the caller's to order, as with gemx_set_env_params)
+    if (hipMemcpy(p->blob, host.get(), sizeof(float) * (size_t)p->blob_words, hipMemcpyHostToDevice) != hipSuccess) return fail(GEMX_ERR_DEVICE, "hipMemcpy(policy weights) failed");
+    return GEMX_OK;
+}
+int gemx_policy_destroy(gemx_policy *p) {
+    if (!p) return GEMX_OK;
+    if (p->blob != nullptr) {
+        gemx::DeviceGuard guard(p->device);
+        (void)hipFree(p->blob);
+    }
+    delete p;
+    return GEMX_OK;
+}
+int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *stream) {
+    if (!h) return fail(GEMX_ERR_ARG, "null handle");
+    if (!p || !call) return fail(GEMX_ERR_ARG, "policy rollout: the policy and the call must not be null");
+    if (call->struct_size != (int32_t)sizeof(gemx_policy_call)) return fail(GEMX_ERR_ARG, "gemx_policy_call size mismatch");
+    if (!call->obs0_dev || !call->length_dev || !call->obs_out_dev || !call->actions_out_dev)
+        return fail(GEMX_ERR_ARG, "policy rollout: obs0_dev, length_dev, obs_out_dev and actions_out_dev must not be null");
+    if (call->K < 1) return fail(GEMX_ERR_ARG, "policy rollout: K must be >= 1");
+    if (call->max_steps < 1) return fail(GEMX_ERR_ARG, "policy rollout: max_steps must be >= 1 (pass a large limit for none)");
+    if (((uintptr_t)call->obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "policy rollout: obs_out_dev must be 16-byte aligned");
+    if ((((uintptr_t)call->length_dev | (uintptr_t)call->obs0_dev | (uintptr_t)call->refs_dev | (uintptr_t)call->noise_dev | (uintptr_t)call->actions_out_dev) & 3u) != 0)
+        return fail(GEMX_ERR_ARG, "policy rollout: length_dev, obs0_dev, refs_dev, noise_dev and actions_out_dev must be 4-byte aligned");
+    const gemx_config &c = h->cfg;
+    // what the kernel does not serve (the episodic rollout's list): refused here, before anything is launched
+    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "policy rollout: fp32 handles only (the fp64 build is a diagnostic; step it)");
+    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "policy rollout: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver");
+    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "policy rollout: solver kind %d is not built; EulerSolver or RK4Solver", c.solver_kind);
+    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "policy rollout: a converter interlocking time (dead time) is not available");
+    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "policy rollout: a DeadTimeProcessor (action_delay > 0) is not available");
+    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "policy rollout: an RCVoltageSupply is not available");
+    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "policy rollout: random initial states are not available (an env restarts inside the launch from the handle's one initial state)");
+    if (p->device != h->device) return fail(GEMX_ERR_ARG, "policy rollout: the policy lives on device %d, the handle on device %d", p->device, h->device);
+    if (call->n_ref < 0 || call->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "policy rollout: n_ref = %d; 0 to %d", call->n_ref, GEMX_MAX_REF);
+    if (call->n_ref > 0 && !call->refs_dev) return fail(GEMX_ERR_ARG, "policy rollout: refs_dev must not be null with n_ref = %d", call->n_ref);
+    if (call->n_cols < 0 || call->n_cols > h->nout) return fail(GEMX_ERR_ARG, "policy rollout: n_cols = %d; 0 to %d", call->n_cols, h->nout);
+    if (call->n_cols + call->n_ref != p->n_in)
+        return fail(GEMX_ERR_ARG, "policy rollout: %d observation columns + %d references = %d inputs, the policy's first layer takes %d", call->n_cols, call->n_ref, call->n_cols + call->n_ref, p->n_in);
+    gemx::PolicyDev pol;
+    memset(&pol, 0, sizeof(pol));
+    for (int j = 0; j < GEMX_MAX_OUT; ++j) pol.pos[j] = -1;
+    for (int i = 0; i < call->n_cols; ++i) {
+        const int col = call->columns[i];
+        if (col < 0 || col >= h->nout) return fail(GEMX_ERR_ARG, "policy rollout: columns[%d] = %d is outside the row of %d columns", i, col, h->nout);
+        if (pol.pos[col] >= 0) return fail(GEMX_ERR_ARG, "policy rollout: column %d is selected twice", col);
+        pol.pos[col] = (int8_t)i;
+    }
+    pol.blob = p->blob;
+    pol.blob_words = p->blob_words;
+    pol.n_layers = p->n_layers;
+    pol.n_in = p->n_in;
+    for (int l = 0; l < gemx::PL_MAX_LAYERS; ++l) pol.width[l] = p->width[l];
+    pol.activation = p->activation;
+    pol.squash = p->squash;
+    pol.n_cols = call->n_cols;
+    pol.n_ref = call->n_ref;
+    pol.obs0 = (const float *)call->obs0_dev;
+    pol.refs = (const float *)call->refs_dev;
+    pol.noise = (const float *)call->noise_dev;
+    pol.actions_out = call->actions_out_dev;
+    gemx::DeviceGuard guard(h->device);
+    gemx_pl_unit_launch_fn fn = nullptr;
+    if (const int rc = load_pl_unit(c.system_kind, h->conv_unit, &fn)) return rc;
+    int linmap_built = 0;
+    const int rc = fn(h, &pol, call->K, call->length_dev, call->max_steps, call->obs_out_dev, call->terminated_out_dev, call->truncated_out_dev, call->ended_out_dev,
+                      (hipStream_t)stream, &linmap_built);
+    if (rc != GEMX_OK) return rc;
+    h->steps_total += (unsigned long long)call->K;
+    char key[256];
+    snprintf(key, sizeof(key), "policy_rollout_kernel<%d, %d, %d, %d, %s, float>", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver, h->ll.d ? "true" : "false");
+    gemx_cov_note(key);
+    if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
+    return GEMX_OK;
+}
+int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int64_t n, void *stream) {
+    if (!h || !x_dev || !y_dev || n < 0) return fail(GEMX_ERR_ARG, "policy tanh probe: invalid argument");
+    gemx::DeviceGuard guard(h->device);
+    gemx_pl_unit_launch_fn fn = nullptr;
+    if (const int rc = load_pl_unit(h->cfg.system_kind, h->conv_unit, &fn)) return rc;
+    auto probe = (gemx_pl_unit_tanh_fn)dlsym(g_pl_units[h->cfg.system_kind][h->conv_unit].dl, "gemx_pl_unit_tanh");
+    if (probe == nullptr) return fail(GEMX_ERR_ARG, "the policy rollout unit exports no gemx_pl_unit_tanh");
+    return probe(x_dev, y_dev, (long long)n, (hipStream_t)stream);
+}
+
 const char *gemx_last_launch(const gemx_handle *h) {
     if (!h) return "";
     const auto &l = h->ll;
-    if (l.pipe == EP_LAUNCH_EPISODIC)
+    if (l.pipe == gemx::EP_LAUNCH_POLICY)
+        snprintf(h->last_launch, sizeof(h->last_launch), "gemx::policy_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,f32> grid=%lld x %d threads, lds=%zu B, K=%d, max_steps=%d, unit libgemx_pl%d_%d.so%s",
+                 l.sys, l.conv, l.load, l.solver, l.d, l.blocks, l.threads, l.lds, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
+    else if (l.pipe == EP_LAUNCH_EPISODIC)
         snprintf(h->last_launch, sizeof(h->last_launch), "gemx::episodic_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,f32> grid=%lld x %d threads, K=%d, max_steps=%d, unit libgemx_tl%d_%d.so%s",
                  l.sys, l.conv, l.load, l.solver, l.d, l.blocks, l.threads, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
     else if (l.pipe == EP_LAUNCH_STEP || l.pipe == EP_LAUNCH_ROLLOUT)

@@ -494,15 +494,143 @@ class BatchedElectricMotorEnv:
         if episode_statistics is True:
             raise ValueError("bind_rollout_episodic: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
         self._check_episodic("bind_rollout_episodic", K, a, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
+        return self._bind_episodic(lambda *t: self._episodic_physics(a, *t), K, obs_out, terminated_out, truncated_out, episode_statistics, stream)
+
+    def _bind_episodic(self, physics, K, obs_out, terminated_out, truncated_out, episode_statistics, stream, extra=()):
+        """The launches of every bound episodic rollout around `physics(raw, terminated, truncated, ended, stream)`: the episode stage's
+        rows pass, the pipeline's launches, row K-1 into `env.truncated`; `extra`: results between obs_out and the masks."""
         self._need_device()
         ps, pipe = self.physical_system, self.pipeline
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
         raw = pipe.raw_rows(K, obs_out)
         episodes, stats = pipe.bind_episode_rows(terminated_out, outputs=episode_statistics, stream=stream)  # (the physics-only env: lengths, no reward)
         ended = stats["ended"] if stats else pipe.ended_scratch
-        return bps._lib.sequence(self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream), episodes,
+        return bps._lib.sequence(physics(raw, terminated_out, truncated_out, ended, stream), episodes,
                                  pipe.bind_after_rollout(raw, ended, None, obs_out, stream), pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream),
-                                 result=(obs_out, terminated_out, truncated_out) + ((stats,) if stats else ()))
+                                 result=(obs_out,) + tuple(extra) + (terminated_out, truncated_out) + ((stats,) if stats else ()))
+
+    # ------------------------------------------------------------------ policy rollouts: the actor inside the episodic launch
+    def _policy_call(self, what, policy, K, obs0, references, noise, actions_out):
+        """The checks of a policy rollout (no device call), then -> (columns, n_ref, action shape, action dtype)."""
+        from .episodes import episodic_refusal
+        from .policy import MLPPolicy
+
+        pipe, ps = self.pipeline, self.physical_system
+        pipe.need_episodic()
+        torch = bps._torch()
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"{what}: policy must be an MLPPolicy")
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError(f"{what}: K must be an integer >= 1, not {K!r}")
+        if pipe.stage is not None or pipe.flux is not None:
+            raise NotImplementedError(f"{what} is not available with a FluxObserver or any observation-side processor: the policy reads the raw state row")
+        if getattr(ps, "_obs_layout", "aos") != "aos":
+            raise NotImplementedError(f"{what} is not available with obs_layout='soa': the tensors are [K, N, S_out]")
+        n_state, N = len(ps.state_names), ps.n_envs
+        columns = list(range(n_state)) if policy.columns is None else list(policy.columns)
+        if any(c >= n_state for c in columns):
+            raise ValueError(f"{what}: the policy selects column {max(columns)}, the state row has {n_state} columns")
+        for name, t in (("obs0", obs0), ("references", references), ("noise", noise), ("actions_out", actions_out)):
+            if torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16):
+                raise NotImplementedError(episodic_refusal(ps, f"a half-precision {name} tensor (fp32 tensors)"))
+        n_ref = 0
+        if references is not None:
+            if not torch.is_tensor(references) or references.dim() != 3:
+                raise ValueError(f"{what}: references must be a tensor [K, N, n_ref]")
+            n_ref = int(references.shape[2])
+            if not 1 <= n_ref <= 4:
+                raise ValueError(f"{what}: references has {n_ref} columns; 1 to 4 (GEMX_MAX_REF)")
+            self._check_tensor(what, references, "references", torch.float32, (K, N, n_ref))
+        if len(columns) + n_ref != policy.n_in:
+            raise ValueError(f"{what}: {len(columns)} observation columns + {n_ref} references = {len(columns) + n_ref} inputs, the policy's first layer takes {policy.n_in}")
+        space = ps.action_space
+        discrete = hasattr(space, "n") or hasattr(space, "nvec")
+        n_logit = int(getattr(space, "n", 0) or np.prod(getattr(space, "nvec", [0]))) if discrete else int(space.shape[0])
+        if policy.n_out != n_logit:
+            raise ValueError(f"{what}: the policy's output width is {policy.n_out}, the converter takes {n_logit} "
+                             f"({'one logit per discrete action' if discrete else 'one output per action component'})")
+        if noise is not None:
+            self._check_tensor(what, noise, "noise", torch.float32, (K, N, n_logit))
+        if obs0 is not None:
+            self._check_tensor(what, obs0, "obs0", torch.float32, (N, n_state))
+        ashape, adtype = ((K, N), torch.uint8) if discrete else ((K, N, n_logit), torch.float32)
+        if actions_out is not None:
+            self._check_tensor(what, actions_out, "actions_out", adtype, ashape)
+        return columns, n_ref, ashape, adtype
+
+    def _policy_physics(self, policy, K, columns, n_ref, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream):
+        """-> the pending masked reset, then `gemx_rollout_policy` on fixed tensors (the policy counterpart of `_episodic_physics`)."""
+        import ctypes as C
+
+        ps, pipe = self.physical_system, self.pipeline
+        lib = bps._lib
+        call = lib.GemxPolicyCall()
+        call.struct_size, call.K, call.n_cols, call.n_ref, call.max_steps = C.sizeof(call), K, len(columns), n_ref, pipe.episode.max_steps
+        for i, c in enumerate(columns):
+            call.columns[i] = c
+        obs0 = ps._obs if obs0 is None else obs0
+        call.obs0_dev, call.refs_dev, call.noise_dev = obs0.data_ptr(), (references.data_ptr() if references is not None else None), (noise.data_ptr() if noise is not None else None)
+        call.length_dev, call.obs_out_dev, call.actions_out_dev = pipe.episode.length.data_ptr(), raw.data_ptr(), actions_out.data_ptr()
+        call.terminated_out_dev, call.truncated_out_dev, call.ended_out_dev = terminated.data_ptr(), truncated.data_ptr(), ended.data_ptr()
+        handle = policy._on_device(ps._device)
+        fn, check, st = ps._L.gemx_rollout_policy, lib.check, C.c_void_p(stream.cuda_stream)
+        keep = (policy, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream, pipe.episode.length)
+
+        def launch(_call=call, _keep=keep):
+            rc = fn(ps._handle, handle, C.byref(_call), st)
+            if rc:
+                check(rc)
+            ps._k += K
+            return None
+
+        return lib.sequence(pipe.bind_before_step(stream), launch)
+
+    def bind_rollout_policy_episodic(self, policy, K, obs_out, actions_out, terminated_out, truncated_out, obs0=None, references=None, noise=None, stream=None,
+                                     episode_statistics=None):
+        """-> zero-argument launch() of `rollout_policy_episodic` on fixed tensors (every output must be given); `launch()` returns
+        `(obs_out, actions_out, terminated_out, truncated_out[, stats])`.  One stream, nothing on the host: capturable with
+        `torch.cuda.graph`; `policy.set_weights` between replays changes the weights the next replay reads."""
+        what = "bind_rollout_policy_episodic"
+        columns, n_ref, _, _ = self._policy_call(what, policy, K, obs0, references, noise, actions_out)
+        for t, name in ((obs_out, "obs_out"), (actions_out, "actions_out"), (terminated_out, "terminated_out"), (truncated_out, "truncated_out")):
+            if t is None:
+                raise ValueError(f"{what}: {name} must be given (a bound launch allocates nothing)")
+        if episode_statistics is True:
+            raise ValueError(f"{what}: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
+        self._check_episodic(what, K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
+        self._need_device()
+        return self._bind_episodic(lambda *t: self._policy_physics(policy, K, columns, n_ref, obs0, references, noise, actions_out, *t), K, obs_out,
+                                   terminated_out, truncated_out, episode_statistics, stream, extra=(actions_out,))
+
+    def rollout_policy_episodic(self, policy, K, obs0=None, references=None, noise=None, obs_out=None, actions_out=None, terminated_out=None, truncated_out=None,
+                                episode_statistics=None):
+        """K fused control steps of an env built with `max_episode_steps=M`, each on the action `policy` (an `MLPPolicy`) computes inside
+        the launch from the row the previous step wrote (csrc/gemx_policy.hip): -> (traj [K, N, S_out], actions [K, N, A] or [K, N] uint8,
+        terminated, truncated[, stats]).  Step k's input is `[obs_prev[columns], references[k]]`: obs_prev is `obs0` at k = 0 (default: the
+        system's internal observation buffer), the previous row afterwards, and the reset observation behind a step that ended the episode.
+        `noise [K, N, out]` is added to the output in front of the squash / the argmax (Gaussian: exploration; Gumbel: categorical
+        sampling); the kernel has no random stream of its own.  The physics rows are bit for bit `rollout_episodic(actions)`'s; the
+        launches around the physics are the same.  On an env without a time limit: ValueError (pass a large M for none).
+        The default `obs0` is the buffer `reset()` and `step()` write; the rollouts themselves do not update it, and the masked reset a
+        truncating `step()` left pending writes no observation: after an episodic or policy rollout (pass `traj[-1]`, or the reset
+        observation where row K-1 ended) and after a `step()` that truncated, give `obs0` explicitly."""
+        what = "rollout_policy_episodic"
+        _, _, ashape, adtype = self._policy_call(what, policy, K, obs0, references, noise, actions_out)
+        self._check_episodic(what, K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
+        self._need_device()
+        torch = bps._torch()
+        ps = self.physical_system
+        mask = lambda t: torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if t is None else t  # noqa: E731
+        if obs_out is None:
+            obs_out = torch.empty((K,) + tuple(ps._obs.shape), dtype=ps._tdtype, device=ps._tdev)
+        if actions_out is None:
+            actions_out = torch.empty(ashape, dtype=adtype, device=ps._tdev)
+        stats = episode_statistics
+        if stats is True:
+            stats = dict(ended=mask(None), finished_return=torch.empty((K, ps.n_envs), dtype=torch.float64, device=ps._tdev),
+                         finished_length=torch.empty((K, ps.n_envs), dtype=torch.int32, device=ps._tdev))
+        return self.bind_rollout_policy_episodic(policy, K, obs_out, actions_out, mask(terminated_out), mask(truncated_out), obs0=obs0, references=references,
+                                                 noise=noise, episode_statistics=stats or None)()
 
     def rollout_episodic(self, actions, obs_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
         """K fused control steps of an env built with `max_episode_steps=M`, the time limit INSIDE the launch (csrc/gemx_episodic.hip):

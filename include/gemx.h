@@ -792,6 +792,55 @@ int gemx_env_params_fields(const gemx_handle *h);
 int gemx_rollout_episodic(gemx_handle *h, const void *actions_dev, int32_t K, const int32_t *length_dev, int32_t max_steps, void *obs_out_dev,
                           uint8_t *terminated_out_dev, uint8_t *truncated_out_dev, uint8_t *ended_out_dev, void *stream);
 
+/* POLICY ROLLOUT: the episodic rollout with the ACTOR inside the launch (new structs and entry points only, ABI number unchanged).
+ * A policy is an MLP of 1..GEMX_POLICY_MAX_LAYERS layers, every width <= GEMX_POLICY_MAX_WIDTH, input width <= GEMX_POLICY_MAX_INPUT,
+ * float32: weights[l] is [width[l]][fan-in] row-major, biases[l] [width[l]] (HOST pointers).  Its weights live in one device blob;
+ * setting them again copies into the same blob (synchronously, not inside a stream capture), so a captured launch sees them at its next
+ * replay.  The action of control step k is computed in front of the step from the row step k - 1 wrote:
+ *     x = [obs_prev[columns[0..n_cols)], references[k]];  out = W_L act(... act(W_1 x + b_1)) + b_L   (act: hidden layers only)
+ *     continuous converters (width[L-1] = action components): action = squash(out + noise[k]), tanh or clip to [-1, 1]
+ *     finite converters (width[L-1] = number of actions):     action = the lowest index among the maxima of out + noise[k]
+ * obs_prev is obs0_dev's row at k = 0 and the handle's reset observation behind a step that ended the episode.  Every dot product is an
+ * fp32 fma chain from the bias over the inputs in ascending order: the selected columns in ascending column order, then the references.
+ *   obs0_dev [N][S_out] | [S_out][N] R;  refs_dev [K][N][n_ref] R (NULL with n_ref = 0);  noise_dev [K][N][width[L-1]] R or NULL
+ *   actions_out_dev [K][N][A] R | [K][N] uint8: the actions taken; feeding them to the episodic rollout gives the same rows, bit for bit
+ *   length_dev, max_steps, obs_out_dev, terminated / truncated / ended: as the episodic rollout takes them
+ * The kernels live in libgemx_pl<S>_<C>.so beside the library.  Asynchronous on `stream`, allocates nothing, can be captured.
+ * GEMX_ERR_ARG, naming the policy rollout, before anything is launched: what the episodic rollout refuses; struct_size; a NULL policy /
+ * obs0 / actions_out; n_cols + n_ref != the policy's input width; n_ref outside [0, GEMX_MAX_REF]; a column outside the row or selected
+ * twice; an output width that is not the converter's; a policy on another device.  The tanh probe runs the actor's tanh over n floats. */
+#define GEMX_POLICY_MAX_LAYERS 3
+#define GEMX_POLICY_MAX_WIDTH 64
+#define GEMX_POLICY_MAX_INPUT 48
+enum { GEMX_POLICY_RELU = 0, GEMX_POLICY_TANH = 1 };
+enum { GEMX_POLICY_SQUASH_TANH = 0, GEMX_POLICY_SQUASH_CLIP = 1 };
+typedef struct gemx_policy_config {
+    int32_t struct_size; /* = sizeof(gemx_policy_config) */
+    int32_t n_layers;
+    int32_t n_in;        /* input width of layer 0 */
+    int32_t width[GEMX_POLICY_MAX_LAYERS];
+    int32_t activation;  /* GEMX_POLICY_RELU | GEMX_POLICY_TANH */
+    int32_t squash;      /* GEMX_POLICY_SQUASH_* (continuous converters) */
+} gemx_policy_config;
+typedef struct gemx_policy_call {
+    int32_t struct_size; /* = sizeof(gemx_policy_call) */
+    int32_t K;
+    int32_t n_cols, n_ref;
+    int32_t columns[GEMX_POLICY_MAX_INPUT];
+    int32_t max_steps;
+    int32_t reserved;
+    const void *obs0_dev, *refs_dev, *noise_dev;
+    const int32_t *length_dev;
+    void *obs_out_dev, *actions_out_dev;
+    uint8_t *terminated_out_dev, *truncated_out_dev, *ended_out_dev;
+} gemx_policy_call;
+typedef struct gemx_policy gemx_policy;
+int gemx_policy_create(const gemx_policy_config *cfg, const float *const *weights, const float *const *biases, int device, gemx_policy **out);
+int gemx_policy_set_weights(gemx_policy *p, const float *const *weights, const float *const *biases);
+int gemx_policy_destroy(gemx_policy *p);
+int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *stream);
+int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int64_t n, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
