@@ -400,6 +400,19 @@ def bound_call(fn, owner, args, keep=(), result=None):
     return launch
 
 
+def counting_call(fn, owner, steps, args, keep=(), result=None):
+    """`bound_call` for the launches that advance the physics: every call also moves the owner's host step counter `_k` by `steps`."""
+
+    def launch(_fn=fn, _owner=owner, _steps=steps, _args=args, _result=result, _keep=keep):
+        rc = _fn(_owner._handle, *_args)
+        if rc:
+            check(rc)
+        _owner._k += _steps
+        return _result
+
+    return launch
+
+
 def sequence(*launches, result=None):
     """-> zero-argument launch() that runs the given launchers in order (None entries are left out) and returns `result`; None when
     there is nothing to run.  (One launcher and no `result`: that launcher itself -- no frame of its own around it.)"""

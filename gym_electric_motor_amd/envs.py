@@ -387,9 +387,10 @@ class BatchedElectricMotorEnv:
             pipe.bind_episode_rows(None, outputs=want)  # (raises: the env has no stage)
         res = physics(obs_out=pipe.raw_rows(K, obs_out, kw.get("last_only", False)), **kw)
         episodes, stats = pipe.bind_episode_rows(res[1], outputs=want)  # (the physics-only env: lengths, no reward)
+        episodes, rows = self._tail(K, res[0], (obs_out, res[1]), res[1], episodes, None)
         if episodes is not None:
             episodes()
-        return (pipe.after_rollout(res[0], res[1], None, obs_out),) + tuple(res[1:]) + ((stats,) if want else ())
+        return (res[0] if rows is None else rows(),) + tuple(res[1:]) + ((stats,) if want else ())
 
     def rollout(self, actions, obs_out=None, **kw):
         """PhysicalSystem.rollout; with an observation stage the raw trajectory goes into a scratch tensor and ONE `apply` writes the
@@ -409,36 +410,35 @@ class BatchedElectricMotorEnv:
         pipe.refuse_rollout()
         if pipe.stage is None and pipe.episode is None and not episode_statistics:
             return ps.bind_rollout(actions, obs_out, done_out, stream=stream)
-        if episode_statistics is True:
-            raise ValueError("bind_rollout: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
-        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
-        raw = pipe.raw_rows(int(actions.shape[0]), obs_out)
-        episodes, stats = pipe.bind_episode_rows(done_out, outputs=episode_statistics, stream=stream)
-        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), episodes, pipe.bind_after_rollout(raw, done_out, None, obs_out, stream),
-                                 result=(obs_out, done_out) + ((stats,) if stats else ()))
+        return self._bind("bind_rollout", True, actions, (obs_out, done_out), stream, episode_statistics)
 
-    # ------------------------------------------------------------------ episodic rollouts: the time limit inside the fused launch
-    def _episodic_actions(self, what, actions, convert):
-        """The checks every episodic entry point makes before anything is launched (they need no device), then the action tensor the
-        kernel reads: -> (K, actions).  `convert`: the eager entry points take what `rollout` takes; the bound ones a device tensor."""
-        self.pipeline.need_episodic()
-        if not hasattr(actions, "shape") or len(actions.shape) < 1:
-            raise ValueError(f"{what} needs actions [K, N, A] / [K, N]")
-        K = int(actions.shape[0])
-        if K < 1:
-            raise ValueError(f"{what}: K must be >= 1, not {K}")
-        ps = self.physical_system
+    # ------------------------------------------------------------------ K-step rollouts over stored rows: one table, one check, one allocator, one plan
+    def _specs(self, K, complete=False, episodic=False, actions_out=False):
+        """-> (the `actions` spec, the ordered output specs) of one family of stored-rows rollouts -- physics-only or complete, episodic
+        (the time limit inside the launch) or not, with or without the policy's `actions_out`.  An output spec is (name, dtype, shape);
+        the actions are checked by their element count, (name, dtype, numel) -- None for the physics-only rollout without a time limit,
+        whose actions `PhysicalSystem.bind_rollout` checks itself (it takes float16 tensors too).  Needs no device."""
         torch = bps._torch()
-        if torch.is_tensor(actions) and actions.dtype is torch.float16:
-            from .episodes import episodic_refusal
-
-            raise NotImplementedError(episodic_refusal(ps, "a half-precision action tensor (fp32 actions)"))
-        if convert and getattr(ps, "_handle", None) is not None:
-            actions = ps._actions_to_device(actions, (K, ps._n_envs))
-        return K, actions
+        ps, stage = self.physical_system, self.observation_stage
+        N = ps.n_envs
+        real = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
+        space = ps.action_space
+        discrete = hasattr(space, "n") or hasattr(space, "nvec")
+        n_act = 1 if discrete else int(space.shape[0])
+        n_state = len(ps.state_names) if stage is None else stage.n_out
+        mask = (torch.uint8, (K, N))
+        specs = [("state_out" if complete else "obs_out", real, (K, N, n_state) if getattr(ps, "_obs_layout", "aos") == "aos" else (K, n_state, N))]
+        if complete:
+            specs += [("refs_out", real, (K, N, len(self.reference_names))), ("reward_out", real, (K, N))]
+        if actions_out:  # (what the policy kernel writes: the action rows as the physics reads them)
+            specs.append(("actions_out",) + (mask if discrete else (torch.float32, (K, N, n_act))))
+        specs.append(("terminated_out" if episodic else "done_out",) + mask)
+        if episodic:
+            specs.append(("truncated_out",) + mask)
+        return ("actions", torch.uint8 if discrete else real, K * N * n_act) if complete or episodic else None, specs
 
     def _check_tensor(self, what, t, name, dtype, shape=None, numel=None):
-        """One tensor of a bound or eager call, in `_check_complete`'s order and wording: dtype, shape, contiguity, device (needs no device)."""
+        """One tensor of a bound or eager call: dtype, shape, contiguity, device, in this order (needs no device)."""
         torch = bps._torch()
         ps = self.physical_system
         tdev = getattr(ps, "_tdev", None) or torch.device("cuda", ps._device)
@@ -453,27 +453,78 @@ class BatchedElectricMotorEnv:
         if t.device != tdev:
             raise ValueError(f"{what}: {name} must be on device {tdev}, not {t.device}")
 
-    def _check_episodic(self, what, K, actions=None, obs_out=None, **masks):
-        """The tensors of an episodic rollout: actions (the bound entry points), the trajectory, the uint8 [K, N] masks by name."""
-        torch = bps._torch()
-        ps = self.physical_system
-        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
-        if actions is not None:
-            space = ps.action_space
-            discrete = hasattr(space, "n") or hasattr(space, "nvec")
-            self._check_tensor(what, actions, "actions", torch.uint8 if discrete else tdtype, numel=K * ps.n_envs * (1 if discrete else int(space.shape[0])))
-        if obs_out is not None:
-            stage = self.observation_stage
-            n_state = len(ps.state_names) if stage is None else stage.n_out
-            shape = (K, ps.n_envs, n_state) if getattr(ps, "_obs_layout", "aos") == "aos" else (K, n_state, ps.n_envs)
-            self._check_tensor(what, obs_out, "obs_out", tdtype, shape)
-        for name, t in masks.items():
-            if t is not None:
-                self._check_tensor(what, t, name, torch.uint8, (K, ps.n_envs))
-
     def _need_device(self):
         if getattr(self.physical_system, "_handle", None) is None:
             raise bps._lib.GemxError("the physical system has no device handle (built with _defer_create, or closed)")
+
+    def _check_call(self, what, K, actions, outs, bound, episode_statistics=None, **family):
+        """What every stored-rows entry point `what` checks before anything is launched, in one order -> (K, the output specs of
+        `_specs(K, **family)`): the family's refusal; `actions` (K is None: K is their first dimension) have a shape; K >= 1; a bound launch
+        allocates nothing, so every output is given and `episode_statistics` is not True; every tensor given, in table order -- the
+        actions of a bound launch first (the eager entry points convert what `rollout` takes); a bound launch cannot carry a
+        ReplayReferenceGenerator; the system has a device handle.  Everything but the last needs no device."""
+        torch = bps._torch()
+        episodic = family.get("episodic", False)
+        if episodic:
+            self.pipeline.need_episodic()
+            if torch.is_tensor(actions) and actions.dtype is torch.float16:
+                from .episodes import episodic_refusal
+
+                raise NotImplementedError(episodic_refusal(self.physical_system, "a half-precision action tensor (fp32 actions)"))
+        else:
+            self.pipeline.refuse_rollout()
+        if K is None:
+            if not hasattr(actions, "shape") or len(actions.shape) < 1:
+                raise ValueError(f"{what} needs {'a device tensor of ' if bound and not episodic else ''}actions [K, N, A] / [K, N]")
+            K = actions.shape[0]
+        K = int(K)
+        if K < 1:
+            raise ValueError(f"{what}: K must be >= 1, not {K}")
+        actions_spec, specs = self._specs(K, **family)
+        if bound:
+            for t, (name, _, _) in zip(outs, specs):
+                if t is None:
+                    raise ValueError(f"{what}: {name} must be given (a bound launch allocates nothing)")
+            if episode_statistics is True:
+                raise ValueError(f"{what}: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
+            if actions is not None and actions_spec is not None:  # (a policy rollout reads no action tensor)
+                self._check_tensor(what, actions, *actions_spec[:2], numel=actions_spec[2])
+        for t, (name, dtype, shape) in zip(outs, specs):
+            if t is not None:
+                self._check_tensor(what, t, name, dtype, shape)
+        if bound and family.get("complete") and isinstance(self.reference_generator, ReplayReferenceGenerator):
+            self.reference_generator.bind_rollout_shell(outs[3], outs[1])  # (raises: cannot be captured)
+        self._need_device()
+        return K, specs
+
+    def _allocate(self, specs, given):
+        """-> `given` with a fresh tensor of the spec's dtype and shape in the place of every None."""
+        torch, device = bps._torch(), self.physical_system._tdev
+        return tuple(torch.empty(shape, dtype=dtype, device=device) if t is None else t for t, (_, dtype, shape) in zip(given, specs))
+
+    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False):
+        """-> the launchers behind the physics of a stored-rows rollout, in order: the episode stage's pass over the rows, the pipeline's
+        launches over the stored rows.  The one thing the complete env does differently."""
+        return episodes, self.pipeline.bind_after_rollout(raw, restart, None, outs[0], stream)
+
+    def _plan(self, physics, K, outs, truncated_out, stream, episode_statistics, eager=False, extra=()):
+        """-> launch() of any stored-rows rollout on fixed tensors, all on `stream` (default: the current one): `physics(raw, done |
+        terminated, truncated, ended, stream)` -> its launcher; `_tail` (the complete env: generators and reward pass first, the
+        references shown last); with a time limit (`truncated_out` given) row K-1 into the episode stage's bytes, its `reset_mask`
+        cleared.  outs: (obs_out, done_out) or (state_out, refs_out, reward_out, done_out); `launch()` returns outs[0], `extra`, the rest
+        of outs, truncated_out and the statistics dict, as far as they exist.  Decided here, once: where the physics writes, which rows
+        the episode stage's pass reads and writes, and the rows everything behind it restarts on -- ENDED with a time limit, else done."""
+        ps, pipe = self.physical_system, self.pipeline
+        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
+        done = outs[-1]
+        raw = pipe.raw_rows(K, outs[0])
+        episodes, stats = pipe.bind_episode_rows(done, outs[2] if len(outs) == 4 else None, episode_statistics, stream)  # (no reward rows: lengths only)
+        ended, last, result = done, None, outs[:1] + tuple(extra) + outs[1:]
+        if truncated_out is not None:
+            ended = stats["ended"] if stats else pipe.ended_scratch
+            last, result = pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream), result + (truncated_out,)
+        return bps._lib.sequence(physics(raw, done, truncated_out, ended, stream), *self._tail(K, raw, outs, ended, episodes, stream, eager), last,
+                                 result=result + ((stats,) if stats else ()))
 
     def _episodic_physics(self, a, raw, terminated, truncated, ended, stream):
         """-> the first two launches of every episodic rollout: the reset a truncating `step()` left pending in the stage's `reset_mask`
@@ -482,36 +533,29 @@ class BatchedElectricMotorEnv:
         return bps._lib.sequence(pipe.bind_before_step(stream),
                                  self.physical_system.bind_rollout_episodic(a, pipe.episode.length, pipe.episode.max_steps, raw, terminated, truncated, ended, stream=stream))
 
+    def _bind(self, what, bound, actions, outs, stream, episode_statistics, **family):
+        """-> launch() of the entry point `what` of a family that reads an action tensor: check, allocate what an eager call (bound=False)
+        did not give, plan.  A bound entry point returns the launch; its eager counterpart -- which takes the actions as `rollout` takes
+        them -- calls it once: both reach the device by the same code."""
+        K, specs = self._check_call(what, None, actions, outs, bound, episode_statistics, **family)
+        ps = self.physical_system
+        a = actions if bound else ps._actions_to_device(actions, (K, ps._n_envs))
+        outs = self._allocate(specs, outs)
+        if family.get("episodic"):
+            return self._plan(lambda *t: self._episodic_physics(a, *t), K, outs[:-1], outs[-1], stream, episode_statistics, eager=not bound)
+        return self._plan(lambda raw, done, _truncated, _ended, st: ps.bind_rollout(a, raw, done, stream=st), K, outs, None, stream, episode_statistics, eager=not bound)
+
     def bind_rollout_episodic(self, actions, obs_out, terminated_out, truncated_out, stream=None, episode_statistics=None):
         """-> zero-argument launch() of `rollout_episodic` on fixed tensors (every output must be given: a bound launch allocates
         nothing); `launch()` returns `(obs_out, terminated_out, truncated_out[, stats])`.  Every launch goes to ONE stream and nothing
         lives on the host, so it can be captured with `torch.cuda.graph` and replayed: the counters carry from replay to replay.
         episode_statistics: dict(ended=, finished_return=, finished_length=) of [K, N] tensors the episode stage's pass writes."""
-        K, a = self._episodic_actions("bind_rollout_episodic", actions, convert=False)
-        for t, name in ((obs_out, "obs_out"), (terminated_out, "terminated_out"), (truncated_out, "truncated_out")):
-            if t is None:
-                raise ValueError(f"bind_rollout_episodic: {name} must be given (a bound launch allocates nothing)")
-        if episode_statistics is True:
-            raise ValueError("bind_rollout_episodic: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
-        self._check_episodic("bind_rollout_episodic", K, a, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
-        return self._bind_episodic(lambda *t: self._episodic_physics(a, *t), K, obs_out, terminated_out, truncated_out, episode_statistics, stream)
-
-    def _bind_episodic(self, physics, K, obs_out, terminated_out, truncated_out, episode_statistics, stream, extra=()):
-        """The launches of every bound episodic rollout around `physics(raw, terminated, truncated, ended, stream)`: the episode stage's
-        rows pass, the pipeline's launches, row K-1 into `env.truncated`; `extra`: results between obs_out and the masks."""
-        self._need_device()
-        ps, pipe = self.physical_system, self.pipeline
-        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
-        raw = pipe.raw_rows(K, obs_out)
-        episodes, stats = pipe.bind_episode_rows(terminated_out, outputs=episode_statistics, stream=stream)  # (the physics-only env: lengths, no reward)
-        ended = stats["ended"] if stats else pipe.ended_scratch
-        return bps._lib.sequence(physics(raw, terminated_out, truncated_out, ended, stream), episodes,
-                                 pipe.bind_after_rollout(raw, ended, None, obs_out, stream), pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream),
-                                 result=(obs_out,) + tuple(extra) + (terminated_out, truncated_out) + ((stats,) if stats else ()))
+        return self._bind("bind_rollout_episodic", True, actions, (obs_out, terminated_out, truncated_out), stream, episode_statistics, episodic=True)
 
     # ------------------------------------------------------------------ policy rollouts: the actor inside the episodic launch
-    def _policy_call(self, what, policy, K, obs0, references, noise, actions_out):
-        """The checks of a policy rollout (no device call), then -> (columns, n_ref, action shape, action dtype)."""
+    def _bind_policy(self, what, bound, policy, K, outs, obs0, references, noise, stream, episode_statistics):
+        """-> launch() of the policy entry point `what`: the policy's own checks (no device call), then what `_bind` does -- check,
+        allocate what an eager call did not give, plan.  outs: (obs_out, actions_out, terminated_out, truncated_out)."""
         from .episodes import episodic_refusal
         from .policy import MLPPolicy
 
@@ -530,7 +574,7 @@ class BatchedElectricMotorEnv:
         columns = list(range(n_state)) if policy.columns is None else list(policy.columns)
         if any(c >= n_state for c in columns):
             raise ValueError(f"{what}: the policy selects column {max(columns)}, the state row has {n_state} columns")
-        for name, t in (("obs0", obs0), ("references", references), ("noise", noise), ("actions_out", actions_out)):
+        for name, t in (("obs0", obs0), ("references", references), ("noise", noise), ("actions_out", outs[1])):
             if torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16):
                 raise NotImplementedError(episodic_refusal(ps, f"a half-precision {name} tensor (fp32 tensors)"))
         n_ref = 0
@@ -553,10 +597,10 @@ class BatchedElectricMotorEnv:
             self._check_tensor(what, noise, "noise", torch.float32, (K, N, n_logit))
         if obs0 is not None:
             self._check_tensor(what, obs0, "obs0", torch.float32, (N, n_state))
-        ashape, adtype = ((K, N), torch.uint8) if discrete else ((K, N, n_logit), torch.float32)
-        if actions_out is not None:
-            self._check_tensor(what, actions_out, "actions_out", adtype, ashape)
-        return columns, n_ref, ashape, adtype
+        _, specs = self._check_call(what, K, None, outs, bound, episode_statistics, episodic=True, actions_out=True)
+        obs_out, actions_out, terminated_out, truncated_out = self._allocate(specs, outs)
+        return self._plan(lambda *t: self._policy_physics(policy, K, columns, n_ref, obs0, references, noise, actions_out, *t), K, (obs_out, terminated_out),
+                          truncated_out, stream, episode_statistics, eager=not bound, extra=(actions_out,))
 
     def _policy_physics(self, policy, K, columns, n_ref, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream):
         """-> the pending masked reset, then `gemx_rollout_policy` on fixed tensors (the policy counterpart of `_episodic_physics`)."""
@@ -572,35 +616,17 @@ class BatchedElectricMotorEnv:
         call.obs0_dev, call.refs_dev, call.noise_dev = obs0.data_ptr(), (references.data_ptr() if references is not None else None), (noise.data_ptr() if noise is not None else None)
         call.length_dev, call.obs_out_dev, call.actions_out_dev = pipe.episode.length.data_ptr(), raw.data_ptr(), actions_out.data_ptr()
         call.terminated_out_dev, call.truncated_out_dev, call.ended_out_dev = terminated.data_ptr(), truncated.data_ptr(), ended.data_ptr()
-        handle = policy._on_device(ps._device)
-        fn, check, st = ps._L.gemx_rollout_policy, lib.check, C.c_void_p(stream.cuda_stream)
-        keep = (policy, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream, pipe.episode.length)
-
-        def launch(_call=call, _keep=keep):
-            rc = fn(ps._handle, handle, C.byref(_call), st)
-            if rc:
-                check(rc)
-            ps._k += K
-            return None
-
-        return lib.sequence(pipe.bind_before_step(stream), launch)
+        args = (policy._on_device(ps._device), C.byref(call), C.c_void_p(stream.cuda_stream))
+        keep = (call, policy, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream, pipe.episode.length)
+        return lib.sequence(pipe.bind_before_step(stream), lib.counting_call(ps._L.gemx_rollout_policy, ps, K, args, keep))
 
     def bind_rollout_policy_episodic(self, policy, K, obs_out, actions_out, terminated_out, truncated_out, obs0=None, references=None, noise=None, stream=None,
                                      episode_statistics=None):
         """-> zero-argument launch() of `rollout_policy_episodic` on fixed tensors (every output must be given); `launch()` returns
         `(obs_out, actions_out, terminated_out, truncated_out[, stats])`.  One stream, nothing on the host: capturable with
         `torch.cuda.graph`; `policy.set_weights` between replays changes the weights the next replay reads."""
-        what = "bind_rollout_policy_episodic"
-        columns, n_ref, _, _ = self._policy_call(what, policy, K, obs0, references, noise, actions_out)
-        for t, name in ((obs_out, "obs_out"), (actions_out, "actions_out"), (terminated_out, "terminated_out"), (truncated_out, "truncated_out")):
-            if t is None:
-                raise ValueError(f"{what}: {name} must be given (a bound launch allocates nothing)")
-        if episode_statistics is True:
-            raise ValueError(f"{what}: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
-        self._check_episodic(what, K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
-        self._need_device()
-        return self._bind_episodic(lambda *t: self._policy_physics(policy, K, columns, n_ref, obs0, references, noise, actions_out, *t), K, obs_out,
-                                   terminated_out, truncated_out, episode_statistics, stream, extra=(actions_out,))
+        return self._bind_policy("bind_rollout_policy_episodic", True, policy, K, (obs_out, actions_out, terminated_out, truncated_out), obs0, references, noise,
+                                 stream, episode_statistics)
 
     def rollout_policy_episodic(self, policy, K, obs0=None, references=None, noise=None, obs_out=None, actions_out=None, terminated_out=None, truncated_out=None,
                                 episode_statistics=None):
@@ -614,23 +640,8 @@ class BatchedElectricMotorEnv:
         The default `obs0` is the buffer `reset()` and `step()` write; the rollouts themselves do not update it, and the masked reset a
         truncating `step()` left pending writes no observation: after an episodic or policy rollout (pass `traj[-1]`, or the reset
         observation where row K-1 ended) and after a `step()` that truncated, give `obs0` explicitly."""
-        what = "rollout_policy_episodic"
-        _, _, ashape, adtype = self._policy_call(what, policy, K, obs0, references, noise, actions_out)
-        self._check_episodic(what, K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
-        self._need_device()
-        torch = bps._torch()
-        ps = self.physical_system
-        mask = lambda t: torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if t is None else t  # noqa: E731
-        if obs_out is None:
-            obs_out = torch.empty((K,) + tuple(ps._obs.shape), dtype=ps._tdtype, device=ps._tdev)
-        if actions_out is None:
-            actions_out = torch.empty(ashape, dtype=adtype, device=ps._tdev)
-        stats = episode_statistics
-        if stats is True:
-            stats = dict(ended=mask(None), finished_return=torch.empty((K, ps.n_envs), dtype=torch.float64, device=ps._tdev),
-                         finished_length=torch.empty((K, ps.n_envs), dtype=torch.int32, device=ps._tdev))
-        return self.bind_rollout_policy_episodic(policy, K, obs_out, actions_out, mask(terminated_out), mask(truncated_out), obs0=obs0, references=references,
-                                                 noise=noise, episode_statistics=stats or None)()
+        return self._bind_policy("rollout_policy_episodic", False, policy, K, (obs_out, actions_out, terminated_out, truncated_out), obs0, references, noise,
+                                 None, episode_statistics)()
 
     def rollout_episodic(self, actions, obs_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
         """K fused control steps of an env built with `max_episode_steps=M`, the time limit INSIDE the launch (csrc/gemx_episodic.hip):
@@ -640,25 +651,7 @@ class BatchedElectricMotorEnv:
         the pipeline's launches (a FluxObserver resets on the ENDED rows); row K-1 into `env.truncated`, with the stage's `reset_mask`
         cleared.  `step()` and further rollouts continue the same episodes.  On an env without a time limit: ValueError.
         episode_statistics (an env built with `episode_statistics=True`): as `rollout` takes it."""
-        K, a = self._episodic_actions("rollout_episodic", actions, convert=True)
-        self._check_episodic("rollout_episodic", K, None, obs_out, terminated_out=terminated_out, truncated_out=truncated_out)
-        self._need_device()
-        torch = bps._torch()
-        ps = self.physical_system
-        mask = lambda t: torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if t is None else t  # noqa: E731
-        if obs_out is None and self.observation_stage is None:
-            obs_out = torch.empty((K,) + tuple(ps._obs.shape), dtype=ps._tdtype, device=ps._tdev)
-        terminated_out, truncated_out = mask(terminated_out), mask(truncated_out)
-        pipe = self.pipeline
-        stream = torch.cuda.current_stream(ps._tdev)
-        raw = pipe.raw_rows(K, obs_out)
-        episodes, stats = pipe.bind_episode_rows(terminated_out, outputs=episode_statistics, stream=stream)
-        ended = stats["ended"] if stats else pipe.ended_scratch
-        self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream)()
-        episodes()
-        traj = pipe.after_rollout(raw, ended, None, obs_out)
-        pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream)()
-        return (traj, terminated_out, truncated_out) + ((stats,) if stats else ())
+        return self._bind("rollout_episodic", False, actions, (obs_out, terminated_out, truncated_out), None, episode_statistics, episodic=True)()
 
     def close(self):
         self.pipeline.close()
@@ -771,17 +764,11 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
             to_abc, a = pipe.bind_actions(a, stream), pipe.abc
         args = (C.c_void_p(a.data_ptr()), 1, C.c_void_p(self._refs.data_ptr()) if int(self.reward_config.n_ref) else None, C.c_void_p(ps._obs_ptr),
                 C.c_void_p(ps._done_ptr), C.c_void_p(self._reward.data_ptr()), C.c_void_p(stream.cuda_stream))
-        call, check = ps._L.gemx_rollout_reward, bps._lib.check
+        call = ps._L.gemx_rollout_reward
         noisy = self.state_noise is not None
         if noisy:  # the plain physics step: done and reward come from the noise stage behind it, on the noisy row
             args, call = (C.c_void_p(a.data_ptr()), C.c_void_p(ps._obs_ptr), C.c_void_p(ps._done_ptr), C.c_void_p(stream.cuda_stream)), ps._L.gemx_step
-
-        def physics(_args=args, _call=call, _keep=keep):  # (hand-written, not `bound_call`: the host's step counter moves with it)
-            rc = _call(ps._handle, *_args)
-            if rc:
-                check(rc)
-            ps._k += 1
-
+        physics = bps._lib.counting_call(call, ps, 1, args, keep)  # (the host's step counter moves with it)
         after = pipe.bind_after_step(self._refs, stream, generators=self.reference_generator.bind_step(pipe.restart_mask, stream=stream),
                                      reward=self._reward[0] if noisy else None, returns=self._reward[0])
         return bps._lib.sequence(to_abc, pipe.bind_before_step(stream), physics, after, result=self._obs)
@@ -818,56 +805,22 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
 
     # ------------------------------------------------------------------ complete K-step rollouts: physics -> references -> reward
     def _complete_shapes(self, K):
-        """(state, refs, reward, done) shapes of a complete K-step rollout."""
-        ps = self.physical_system
-        stage = self.observation_stage
-        n_state = len(ps.state_names) if stage is None else stage.n_out
-        return (K, ps.n_envs, n_state), (K, ps.n_envs, len(self.reference_names)), (K, ps.n_envs), (K, ps.n_envs)
+        """(state, refs, reward, done) shapes of a complete K-step rollout: the output table's, for the callers that allocate them."""
+        return tuple(shape for _, _, shape in self._specs(K, complete=True)[1])
 
-    def _check_complete(self, what, K, actions=None, state_out=None, refs_out=None, reward_out=None, done_out=None):
-        """bind_rollout-style validation (K, then per tensor: dtype, shape, contiguity, device) -> K.  Needs no device: it runs
-        before anything is launched, and on an env whose handles were never created."""
-        self.pipeline.refuse_rollout()
-        torch = bps._torch()
-        ps = self.physical_system
-        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
-        tdev = getattr(ps, "_tdev", None) or torch.device("cuda", ps._device)
-        K = int(K)
-        if K < 1:
-            raise ValueError(f"{what}: K must be >= 1, not {K}")
-
-        def check(t, name, dtype, shape=None, numel=None):
-            if not torch.is_tensor(t):
-                raise ValueError(f"{what}: {name} must be a tensor")
-            if t.dtype != dtype:
-                raise ValueError(f"{what}: {name} must have dtype {dtype}, not {t.dtype}")
-            if (shape is not None and tuple(t.shape) != shape) or (numel is not None and t.numel() != numel):
-                raise ValueError(f"{what}: {name} must have shape {shape if shape is not None else f'of {numel} elements'}, not {tuple(t.shape)}")
-            if not t.is_contiguous():
-                raise ValueError(f"{what}: {name} must be contiguous")
-            if t.device != tdev:
-                raise ValueError(f"{what}: {name} must be on device {tdev}, not {t.device}")
-
-        if actions is not None:
-            space = ps.action_space
-            discrete = hasattr(space, "n") or hasattr(space, "nvec")
-            check(actions, "actions", torch.uint8 if discrete else tdtype, numel=K * ps.n_envs * (1 if discrete else int(space.shape[0])))
-        shapes = self._complete_shapes(K)
-        for t, name, dtype, shape in ((state_out, "state_out", tdtype, shapes[0]), (refs_out, "refs_out", tdtype, shapes[1]),
-                                      (reward_out, "reward_out", tdtype, shapes[2]), (done_out, "done_out", torch.uint8, shapes[3])):
-            if t is not None:
-                check(t, name, dtype, shape)
-        return K
-
-    def _tail(self, K, raw, state_out, refs_out, reward_out, done_out, stream, eager=False, episodes=None, restart=None):
+    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False):
         """-> the launchers that follow the physics of a complete K-step rollout, in order, on fixed tensors: the generators in the shell's
-        order on the done mask; the reward of row k against the references shown before step k; `episodes` (the episode stage's pass over
-        the done and reward rows, directly behind the launch that completes them); the pipeline's launches over the stored rows; row K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further
-        rollouts continue from it).  restart [K, N]: the rows the generators restart on and the flux observer resets on, where they are not
-        `done_out` -- the ENDED rows of an episodic rollout, whose reward pass still reads the terminated rows `done_out`."""
+        order on the `restart` rows; the reward of row k against the references shown before step k; `episodes` (the episode stage's pass
+        over the done and reward rows, directly behind the launch that completes them); the pipeline's launches over the stored rows; row
+        K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further rollouts
+        continue from it).  restart [K, N]: the rows the generators restart on and the flux observer resets on -- `done_out`, or the ENDED
+        rows of an episodic rollout, whose reward pass still reads the terminated rows `done_out`.  eager: run once, on the current
+        stream, so a ReplayReferenceGenerator (host state) can take part."""
+        if len(outs) != 4:  # (the inherited physics-only rollouts: no references, no reward)
+            return super()._tail(K, raw, outs, restart, episodes, stream, eager)
         torch = bps._torch()
         ps, gen = self.physical_system, self.reference_generator
-        restart = done_out if restart is None else restart
+        state_out, refs_out, reward_out, done_out = outs
         if eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
             generators = lambda: gen.rollout_shell(K, restart, out=refs_out)  # noqa: E731
         else:
@@ -897,20 +850,6 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
                 C.c_void_p(done.data_ptr()), int(rows.shape[0]), C.c_void_p(reward_out.data_ptr()), C.c_void_p(stream.cuda_stream))
         return bps._lib.bound_call(ps._L.gemx_reward_rows, ps, args, (rows, refs_rows, done, reward_out, stream))
 
-    def _rollout_complete(self, K, physics, outs, episode_statistics=None):
-        """The eager entry points: allocate what was not given, run `physics(raw, done_out)` and then the tail, once."""
-        torch = bps._torch()
-        ps = self.physical_system
-        if self.pipeline.episode is None and episode_statistics:
-            self.pipeline.bind_episode_rows(None, outputs=episode_statistics)  # (raises: the env has no stage)
-        outs = tuple(torch.empty(shape, dtype=torch.uint8 if i == 3 else ps._tdtype, device=ps._tdev) if t is None else t
-                     for i, (t, shape) in enumerate(zip(outs, self._complete_shapes(K))))
-        raw = self.pipeline.raw_rows(K, outs[0])
-        episodes, stats = self.pipeline.bind_episode_rows(outs[3], outs[2], episode_statistics)
-        physics(raw, outs[3])
-        result = outs + ((stats,) if episode_statistics else ())
-        return bps._lib.sequence(*self._tail(K, raw, *outs, torch.cuda.current_stream(ps._tdev), eager=True, episodes=episodes), result=result)()
-
     def rollout_complete(self, actions, state_out=None, refs_out=None, reward_out=None, done_out=None, episode_statistics=None):
         """K complete control steps in THREE launches (four with an observation stage) instead of K x (two or three):
         -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], done [K, N]) -- exactly what K calls of `step(actions[k])` return,
@@ -923,21 +862,16 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         episode_statistics (an env built with `episode_statistics=True`; its counters follow every rollout either way): True -> a fifth
         result dict(ended [K, N] uint8, finished_return [K, N] float64, finished_length [K, N] int32) -- an episode's totals at the row where
         it ended, 0 elsewhere -- in the pipeline's scratch (the next rollout overwrites it), or a dict of the caller's tensors."""
-        if not hasattr(actions, "shape") or len(actions.shape) < 1:
-            raise ValueError("rollout_complete needs actions [K, N, A] / [K, N]")
-        K = self._check_complete("rollout_complete", actions.shape[0], None, state_out, refs_out, reward_out, done_out)
-        ps = self.physical_system
-        a = ps._actions_to_device(actions, (K, ps._n_envs))
-        return self._rollout_complete(K, lambda raw, done: ps.rollout(a, obs_out=raw, done_out=done), (state_out, refs_out, reward_out, done_out),
-                                      episode_statistics)
+        return self._bind("rollout_complete", False, actions, (state_out, refs_out, reward_out, done_out), None, episode_statistics, complete=True)()
 
     def rollout_complete_synthetic(self, K, seed=0, step0=None, state_out=None, refs_out=None, reward_out=None, done_out=None, episode_statistics=None):
         """`rollout_complete` on the device-side action source (`physical_system.rollout_synthetic(K, seed, step0)`): no action tensor is
         read.  Equal, bit for bit, to `rollout_complete(physical_system.synthetic_actions(K, seed, step0))`."""
-        K = self._check_complete("rollout_complete_synthetic", K, None, state_out, refs_out, reward_out, done_out)
+        outs = (state_out, refs_out, reward_out, done_out)
+        K, specs = self._check_call("rollout_complete_synthetic", K, None, outs, False, complete=True)
         ps = self.physical_system
-        return self._rollout_complete(K, lambda raw, done: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done),
-                                      (state_out, refs_out, reward_out, done_out), episode_statistics)
+        physics = lambda raw, done, *_: lambda: ps.rollout_synthetic(K, seed=seed, step0=step0, obs_out=raw, done_out=done)  # noqa: E731 (no bound synthetic launch)
+        return self._plan(physics, K, self._allocate(specs, outs), None, None, episode_statistics, eager=True)()
 
     def bind_rollout_complete(self, actions, state_out, refs_out, reward_out, done_out, stream=None, episode_statistics=None):
         """-> zero-argument launch() of `rollout_complete` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
@@ -946,40 +880,9 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         replays advance the physics and the generators.  A ReplayReferenceGenerator is refused: its row index lives on the host.
         episode_statistics: dict(ended=, finished_return=, finished_length=) of [K, N] tensors the episode stage's pass writes (a bound
         launch allocates nothing: `True` is refused); `launch()` then returns that dict as a fifth result."""
-        if not hasattr(actions, "shape") or len(actions.shape) < 1:
-            raise ValueError("bind_rollout_complete needs a device tensor of actions [K, N, A] / [K, N]")
-        outs = (state_out, refs_out, reward_out, done_out)
-        for t, name in zip(outs, ("state_out", "refs_out", "reward_out", "done_out")):
-            if t is None:
-                raise ValueError(f"bind_rollout_complete: {name} must be given (a bound launch allocates nothing)")
-        K = self._check_complete("bind_rollout_complete", actions.shape[0], actions, *outs)
-        if isinstance(self.reference_generator, ReplayReferenceGenerator):
-            self.reference_generator.bind_rollout_shell(done_out, refs_out)  # (raises: cannot be captured)
-        ps = self.physical_system
-        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
-        raw = self.pipeline.raw_rows(K, state_out)
-        if episode_statistics is True:
-            raise ValueError("bind_rollout_complete: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
-        episodes, stats = self.pipeline.bind_episode_rows(done_out, reward_out, episode_statistics, stream)
-        return bps._lib.sequence(ps.bind_rollout(actions, raw, done_out, stream=stream), *self._tail(K, raw, *outs, stream, episodes=episodes),
-                                 result=outs + ((stats,) if stats else ()))
+        return self._bind("bind_rollout_complete", True, actions, (state_out, refs_out, reward_out, done_out), stream, episode_statistics, complete=True)
 
     # ------------------------------------------------------------------ complete episodic rollouts: the time limit inside the fused launch
-    def _bind_complete_episodic(self, K, a, outs, truncated_out, stream, episode_statistics, eager=False):
-        """-> launch() of a complete episodic rollout on fixed tensors, all on `stream`, in this order: the reset a truncating `step()` left
-        pending; the episodic physics; the generators' `rollout_shell` on the ENDED rows; the reward pass on the TERMINATED rows; the
-        episode stage's pass over the terminated and reward rows; the pipeline's launches, the flux observer resetting on the ended rows;
-        row K-1 into the references shown -- and into the stage's truncated / ended bytes, with its `reset_mask` cleared."""
-        pipe = self.pipeline
-        state_out, refs_out, reward_out, terminated_out = outs
-        raw = pipe.raw_rows(K, state_out)
-        episodes, stats = pipe.bind_episode_rows(terminated_out, reward_out, episode_statistics, stream)
-        ended = stats["ended"] if stats else pipe.ended_scratch
-        result = outs + (truncated_out,) + ((stats,) if stats else ())
-        return bps._lib.sequence(self._episodic_physics(a, raw, terminated_out, truncated_out, ended, stream),
-                                 *self._tail(K, raw, *outs, stream, eager=eager, episodes=episodes, restart=ended),
-                                 pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream), result=result)
-
     def rollout_complete_episodic(self, actions, state_out=None, refs_out=None, reward_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
         """`rollout_complete` for an env built with `max_episode_steps=M`, the time limit INSIDE the fused launch (csrc/gemx_episodic.hip):
         -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], terminated [K, N], truncated [K, N][, stats]) -- what K calls of
@@ -989,47 +892,16 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         reset is pending, so `step()` and further rollouts continue the same episodes.  `ended = terminated | truncated` is what
         `ga.advantages(..., ended=)` takes.  On an env without a time limit: ValueError; what the kernel does not serve:
         NotImplementedError (episodes.episodic_refusal).  episode_statistics: as `rollout_complete` takes it."""
-        K, a = self._episodic_actions("rollout_complete_episodic", actions, convert=True)
-        self._check_complete_episodic("rollout_complete_episodic", K, None, state_out, refs_out, reward_out, terminated_out, truncated_out)
-        self._need_device()
-        torch = bps._torch()
-        ps = self.physical_system
-        outs = tuple(torch.empty(shape, dtype=torch.uint8 if i == 3 else ps._tdtype, device=ps._tdev) if t is None else t
-                     for i, (t, shape) in enumerate(zip((state_out, refs_out, reward_out, terminated_out), self._complete_shapes(K))))
-        truncated_out = torch.empty((K, ps.n_envs), dtype=torch.uint8, device=ps._tdev) if truncated_out is None else truncated_out
-        return self._bind_complete_episodic(K, a, outs, truncated_out, torch.cuda.current_stream(ps._tdev), episode_statistics, eager=True)()
+        return self._bind("rollout_complete_episodic", False, actions, (state_out, refs_out, reward_out, terminated_out, truncated_out), None, episode_statistics,
+                          complete=True, episodic=True)()
 
     def bind_rollout_complete_episodic(self, actions, state_out, refs_out, reward_out, terminated_out, truncated_out, stream=None, episode_statistics=None):
         """-> zero-argument launch() of `rollout_complete_episodic` on fixed tensors; `launch()` returns `(state_out, refs_out, reward_out,
         terminated_out, truncated_out[, stats])`.  Everything is resolved here, once: a call allocates nothing, never synchronises and goes
         to ONE stream, so it can be captured with `torch.cuda.graph` and replayed -- the episode counters, like the physics and the
         generators, carry from replay to replay.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
-        K, a = self._episodic_actions("bind_rollout_complete_episodic", actions, convert=False)
-        outs = (state_out, refs_out, reward_out, terminated_out)
-        for t, name in zip(outs + (truncated_out,), ("state_out", "refs_out", "reward_out", "terminated_out", "truncated_out")):
-            if t is None:
-                raise ValueError(f"bind_rollout_complete_episodic: {name} must be given (a bound launch allocates nothing)")
-        if episode_statistics is True:
-            raise ValueError("bind_rollout_complete_episodic: episode_statistics must be a dict of tensors (a bound launch allocates nothing)")
-        self._check_complete_episodic("bind_rollout_complete_episodic", K, a, *outs, truncated_out)
-        if isinstance(self.reference_generator, ReplayReferenceGenerator):
-            self.reference_generator.bind_rollout_shell(terminated_out, refs_out)  # (raises: cannot be captured)
-        self._need_device()
-        ps = self.physical_system
-        stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
-        return self._bind_complete_episodic(K, a, outs, truncated_out, stream, episode_statistics)
-
-    def _check_complete_episodic(self, what, K, actions, state_out, refs_out, reward_out, terminated_out, truncated_out):
-        """`_check_complete`'s validation for the episodic entry points (which that method refuses: it serves the env without a time limit)."""
-        torch = bps._torch()
-        ps = self.physical_system
-        tdtype = getattr(ps, "_tdtype", None) or getattr(torch, ps._dtype_name)
-        self._check_episodic(what, K, actions)
-        shapes = self._complete_shapes(K)
-        for t, name, dtype, shape in ((state_out, "state_out", tdtype, shapes[0]), (refs_out, "refs_out", tdtype, shapes[1]), (reward_out, "reward_out", tdtype, shapes[2]),
-                                      (terminated_out, "terminated_out", torch.uint8, shapes[3]), (truncated_out, "truncated_out", torch.uint8, shapes[3])):
-            if t is not None:
-                self._check_tensor(what, t, name, dtype, shape)
+        return self._bind("bind_rollout_complete_episodic", True, actions, (state_out, refs_out, reward_out, terminated_out, truncated_out), stream,
+                          episode_statistics, complete=True, episodic=True)
 
     def close(self):
         self.reference_generator.close()

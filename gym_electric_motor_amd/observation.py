@@ -491,11 +491,6 @@ class ObservationPipeline:
                                         outs.get("finished_length"), stream)
         return launch, (outs if outputs else None)
 
-    def after_rollout(self, raw, done, refs=None, out=None):
-        """`bind_after_rollout` on the current stream, run once -> the processed trajectory."""
-        launch = self.bind_after_rollout(raw, done, refs, out)
-        return raw if launch is None else launch()
-
     def reset(self, refs=None):
         """After the system's reset: the observer's, the extended reset rows -- the system's, then [0, 0] (flux_observer.py:80-83) --
         and the column program -> `state`.  With a StateNoiseProcessor the reset rows are noised first (state_noise_processor.py:70-74: one

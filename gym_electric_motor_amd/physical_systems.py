@@ -734,19 +734,9 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         if not (torch.is_tensor(a) and a.device == self._tdev and a.is_contiguous() and a.dtype is self._want_dtype and a.numel() == self._act_numel):
             raise ValueError(f"bind_step needs a contiguous {self._want_dtype} tensor of {self._act_numel} elements on {self._tdev}")
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)  # (the Stream OBJECT is kept: its raw handle must not dangle)
-        st = stream.cuda_stream
-        call, check, obs = self._gemx_step, _lib.check, self._obs
-        args = (C.c_void_p(a.data_ptr()), C.c_void_p(self._obs_ptr), C.c_void_p(self._done_ptr), C.c_void_p(st))
-        keep = (a, stream)  # the buffers behind the raw pointers stay alive as long as the stepper does
-
-        def step(_args=args, _call=call, _keep=keep):
-            rc = _call(self._handle, *_args)  # (the handle is read per call: None after close() -> the C ABI's "null handle" error, not a stale pointer)
-            if rc:
-                check(rc)
-            self._k += 1
-            return obs
-
-        return step, obs, self._done
+        args = (C.c_void_p(a.data_ptr()), C.c_void_p(self._obs_ptr), C.c_void_p(self._done_ptr), C.c_void_p(stream.cuda_stream))
+        # (the buffers behind the raw pointers stay alive as long as the stepper does; the handle is read per call: _lib.bound_call)
+        return _lib.counting_call(self._gemx_step, self, 1, args, (a, stream), self._obs), self._obs, self._done
 
     def bind_rollout(self, actions, obs_out, done_out, stream=None):
         """A zero-argument `launch()` for a loop that reuses its tensors (a fixed action chunk -- or one the policy overwrites -- and fixed
@@ -772,20 +762,9 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         if not (torch.is_tensor(done_out) and tuple(done_out.shape) == dshape and done_out.is_contiguous() and done_out.dtype == torch.uint8 and done_out.device == self._tdev):
             raise ValueError(f"bind_rollout: done_out must be a contiguous uint8 tensor of shape {dshape} on {self._tdev}")
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)  # (the Stream OBJECT is kept: its raw handle must not dangle)
-        st = stream.cuda_stream
-        call, check = (self._L.gemx_rollout_half if half else self._L.gemx_rollout), _lib.check
-        args = (C.c_void_p(a.data_ptr()), K, C.c_void_p(obs_out.data_ptr()), C.c_void_p(done_out.data_ptr())) + (() if half else (1,)) + (C.c_void_p(st),)
-        keep = (a, obs_out, done_out, stream)  # the buffers and the stream behind the raw pointers stay alive as long as the launcher does
-        out = (obs_out, done_out)
-
-        def launch(_args=args, _call=call, _keep=keep):
-            rc = _call(self._handle, *_args)  # (the handle is read per call: None after close() -> the C ABI's "null handle" error)
-            if rc:
-                check(rc)
-            self._k += K
-            return out
-
-        return launch
+        args = (C.c_void_p(a.data_ptr()), K, C.c_void_p(obs_out.data_ptr()), C.c_void_p(done_out.data_ptr())) + (() if half else (1,)) + (C.c_void_p(stream.cuda_stream),)
+        # (the buffers and the stream behind the raw pointers stay alive as long as the launcher does)
+        return _lib.counting_call(self._L.gemx_rollout_half if half else self._L.gemx_rollout, self, K, args, (a, obs_out, done_out, stream), (obs_out, done_out))
 
     def bind_rollout_episodic(self, actions, length, max_steps, obs_out, terminated_out, truncated_out, ended_out, stream=None):
         """A zero-argument `launch()` of `gemx_rollout_episodic` on fixed tensors: K fused control steps with the episode time limit
@@ -806,20 +785,10 @@ class BatchedSCMLSystem(_PhysicalSystemBase):
         torch = _torch()
         K, a = int(actions.shape[0]), actions
         stream = stream if stream is not None else torch.cuda.current_stream(self._tdev)  # (the Stream OBJECT is kept: its raw handle must not dangle)
-        call, check = self._L.gemx_rollout_episodic, _lib.check
         args = (C.c_void_p(a.data_ptr()), K, C.c_void_p(length.data_ptr()), M, C.c_void_p(obs_out.data_ptr()), C.c_void_p(terminated_out.data_ptr()),
                 C.c_void_p(truncated_out.data_ptr()), C.c_void_p(ended_out.data_ptr()), C.c_void_p(stream.cuda_stream))
-        keep = (a, length, obs_out, terminated_out, truncated_out, ended_out, stream)
         out = (obs_out, terminated_out, truncated_out, ended_out)
-
-        def launch(_args=args, _call=call, _keep=keep):
-            rc = _call(self._handle, *_args)  # (the handle is read per call: None after close() -> the C ABI's "null handle" error)
-            if rc:
-                check(rc)
-            self._k += K
-            return out
-
-        return launch
+        return _lib.counting_call(self._L.gemx_rollout_episodic, self, K, args, (a, length, stream) + out, out)
 
     def rollout(self, actions, obs_out=None, done_out=None, last_only=False, references=None, reward_out=None):
         """K fused control steps in one launch.  actions: [K, N, A] / [K, N]; returns (obs [K, N, S_out], done [K, N])
