@@ -256,6 +256,7 @@ EXPORTS = (
     "gemx_set_env_params", "gemx_clear_env_params", "gemx_get_env_params", "gemx_env_params_fields",
     "gemx_rollout_episodic",
     "gemx_policy_create", "gemx_policy_set_weights", "gemx_policy_destroy", "gemx_rollout_policy", "gemx_policy_tanh_probe",
+    "gemx_rollout_policy_complete",
 )
 
 
@@ -363,6 +364,7 @@ def load():
     L.gemx_policy_destroy.argtypes = [vp]
     L.gemx_rollout_policy.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp]
     L.gemx_policy_tanh_probe.argtypes = [vp, vp, vp, i64, vp]
+    L.gemx_rollout_policy_complete.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp, vp, vp, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]
     L.gemx_get_switch_state.argtypes = [vp, vp, vp]

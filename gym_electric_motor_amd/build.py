@@ -24,8 +24,14 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_policy.hpp, gemx_policy.hip    the policy rollout: the episodic kernel with a device MLP actor in front of every step, compiled once per
                                         (system, converter unit), fp32, into libgemx_pl<S>_<C>.so, which the first gemx_rollout_policy of such a
                                         handle loads with dlopen
-The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units and the nine objects
-of libgemx.so are compiled in parallel.
+    gemx_policy_dev.hpp                 the actor's device helpers, shared by the two kinds of policy unit
+    gemx_refgen_lane.hpp, gemx_refprofile_lane.hpp   the per-lane functions of the all-Wiener and the profile generators, shared by their
+                                        units of libgemx.so and the complete policy units
+    gemx_policy_complete.hpp, gemx_policy_complete.hip   the policy rollout of the complete env: the policy kernel with the reference generators
+                                        stepped in the lane, once per generator kind, compiled once per (system, converter unit), fp32, into
+                                        libgemx_pc<S>_<C>.so, which the first gemx_rollout_policy_complete of such a handle loads with dlopen
+The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units, the 19 complete policy
+units and the nine objects of libgemx.so are compiled in parallel.
 """
 import concurrent.futures as cf
 import glob
@@ -38,12 +44,15 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 # the support objects of libgemx.so beside the C ABI: (name, source, headers beside gemx_common.hpp, compile cost)
+_PC_HEADERS = ["gemx_policy.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp"]  # gemx_policy_complete.hpp and what it includes
+_LANE_HEADERS = ["gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp"]  # gemx_support.hpp includes them: the two generator units' lane functions
 SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc", "gemx_obsproc.hip", ["gemx_support.hpp"], 0.1),
            ("fluxobs", "gemx_fluxobs.hip", ["gemx_support.hpp"], 0.1), ("rewardpass", "gemx_rewardpass.hip", ["gemx_support.hpp"], 0.1),
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
            ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05)]
 SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
-                                           "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip"] + [u[1] for u in SUPPORT]]
+                                           "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip",
+                                           "gemx_policy_dev.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")
 
@@ -61,6 +70,11 @@ def ep_unit_lib(s, c):
 def tl_unit_lib(s, c):
     """the shared object of one episodic rollout unit (fp32 only; gemx_capi.hip's load_tl_unit looks beside libgemx.so)"""
     return os.path.join(PKG_DIR, f"libgemx_tl{s}_{c}.so")
+
+
+def pc_unit_lib(s, c):
+    """the shared object of one complete policy rollout unit (fp32 only; gemx_capi.hip's load_pc_unit looks beside libgemx.so)"""
+    return os.path.join(PKG_DIR, f"libgemx_pc{s}_{c}.so")
 
 
 def pl_unit_lib(s, c):
@@ -94,11 +108,13 @@ def _digest(sources=None, header=None):
 
 
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
-_DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp", "gemx_policy.hpp", "gemx_capi.hip"],
+_DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_capi.hip"],
          "envparams": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
          "episodic": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],
-         "policy": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy.hip"],
-         **{name: ["gemx_common.hpp"] + headers + [src] for name, src, headers, _ in SUPPORT}}
+         "policy": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp", "gemx_policy.hip"],
+         "policy_complete": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy_dev.hpp"] + _PC_HEADERS +
+                            ["gemx_support.hpp", "gemx_refprofile.hip", "gemx_policy_complete.hip"],  # (gemx_refprofile.hip: its head section, the one definition of profile_row)
+         **{name: ["gemx_common.hpp"] + headers + _LANE_HEADERS + [src] for name, src, headers, _ in SUPPORT}}
 # compile cost of an fp32 unit by system kind (object size, MB: induction > synchronous > DC); fp64 units take the single-wave kernel only
 _COST = {7: 6.0, 2: 5.3, 6: 4.9, 1: 4.5, 5: 4.0, 4: 3.9, 3: 3.5, 0: 3.5}
 
@@ -122,8 +138,13 @@ def pl_libs():
     return [pl_unit_lib(s, c) for s, c in UNITS]
 
 
+def pc_libs():
+    """the complete policy rollout units (one per policy unit: the same system/converter pairs, fp32)"""
+    return [pc_unit_lib(s, c) for s, c in UNITS]
+
+
 def is_stale():
-    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs() + pl_libs()):
+    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs() + pl_libs() + pc_libs()):
         return True
     return open(STAMP).read().strip() != _digest()
 
@@ -179,6 +200,10 @@ def _build_locked(hipcc, force, verbose, jobs):
         out = pl_unit_lib(s, c)
         cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
                                                   os.path.join(csrc, "gemx_policy.hip"), "-o", out], "policy", 0.1))
+    for s, c in UNITS:  # the complete policy units: the policy kernel with the generators in the lane, once per generator kind
+        out = pc_unit_lib(s, c)
+        cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
+                                                  os.path.join(csrc, "gemx_policy_complete.hip"), "-o", out], "policy_complete", 0.2))
     objects = []  # of libgemx.so
     for name, src, cost in [("capi", "gemx_capi.hip", 0.3)] + [(u[0], u[1], u[3]) for u in SUPPORT]:
         obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
@@ -204,7 +229,7 @@ def _build_locked(hipcc, force, verbose, jobs):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:  # longest first: the big induction-machine units do not end up as the tail
         list(ex.map(compile_one, sorted(cmds, key=lambda j: -j[3])))
     run([hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-o", LIB] + objects + ["-ldl"])
-    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pl*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
+    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pc*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
         if stale not in [j[0] for j in cmds]:
             os.remove(stale)
     with open(STAMP, "w") as fh:

@@ -16,6 +16,7 @@
 #include "gemx_common.hpp"
 #include "gemx_envparams.hpp"
 #include "gemx_policy.hpp"
+#include "gemx_policy_complete.hpp"
 
 namespace gemx {
 
@@ -1217,6 +1218,9 @@ static int load_tl_unit(int s, int c, gemx_tl_unit_launch_fn *out) { return load
 // ... and the policy rollout units, libgemx_pl<S>_<C>.so, by the first gemx_rollout_policy
 extern "C++" { static SideUnitLib<gemx_pl_unit_launch_fn> g_pl_units[8][12]; }
 static int load_pl_unit(int s, int c, gemx_pl_unit_launch_fn *out) { return load_side_unit(g_pl_units, "pl", "policy rollout", "policy rollout", s, c, out); }
+// ... and the complete policy rollout units, libgemx_pc<S>_<C>.so, by the first gemx_rollout_policy_complete
+extern "C++" { static SideUnitLib<gemx_pc_unit_launch_fn> g_pc_units[8][12]; }
+static int load_pc_unit(int s, int c, gemx_pc_unit_launch_fn *out) { return load_side_unit(g_pc_units, "pc", "complete policy rollout", "complete policy rollout", s, c, out); }
 
 int gemx_env_params_fields(const gemx_handle *h) { return h ? ep_fields(h->cfg.system_kind) : GEMX_ERR_ARG; }
 
@@ -1406,39 +1410,40 @@ int gemx_policy_destroy(gemx_policy *p) {
     delete p;
     return GEMX_OK;
 }
-int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *stream) {
+// what gemx_rollout_policy and gemx_rollout_policy_complete check of the handle, the policy and the call -> the kernel's view of the policy; `what` names
+// the entry point in the messages
+static int policy_prepare(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, const char *what, gemx::PolicyDev &pol) {
     if (!h) return fail(GEMX_ERR_ARG, "null handle");
-    if (!p || !call) return fail(GEMX_ERR_ARG, "policy rollout: the policy and the call must not be null");
+    if (!p || !call) return fail(GEMX_ERR_ARG, "%s: the policy and the call must not be null", what);
     if (call->struct_size != (int32_t)sizeof(gemx_policy_call)) return fail(GEMX_ERR_ARG, "gemx_policy_call size mismatch");
     if (!call->obs0_dev || !call->length_dev || !call->obs_out_dev || !call->actions_out_dev)
-        return fail(GEMX_ERR_ARG, "policy rollout: obs0_dev, length_dev, obs_out_dev and actions_out_dev must not be null");
-    if (call->K < 1) return fail(GEMX_ERR_ARG, "policy rollout: K must be >= 1");
-    if (call->max_steps < 1) return fail(GEMX_ERR_ARG, "policy rollout: max_steps must be >= 1 (pass a large limit for none)");
-    if (((uintptr_t)call->obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "policy rollout: obs_out_dev must be 16-byte aligned");
+        return fail(GEMX_ERR_ARG, "%s: obs0_dev, length_dev, obs_out_dev and actions_out_dev must not be null", what);
+    if (call->K < 1) return fail(GEMX_ERR_ARG, "%s: K must be >= 1", what);
+    if (call->max_steps < 1) return fail(GEMX_ERR_ARG, "%s: max_steps must be >= 1 (pass a large limit for none)", what);
+    if (((uintptr_t)call->obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "%s: obs_out_dev must be 16-byte aligned", what);
     if ((((uintptr_t)call->length_dev | (uintptr_t)call->obs0_dev | (uintptr_t)call->refs_dev | (uintptr_t)call->noise_dev | (uintptr_t)call->actions_out_dev) & 3u) != 0)
-        return fail(GEMX_ERR_ARG, "policy rollout: length_dev, obs0_dev, refs_dev, noise_dev and actions_out_dev must be 4-byte aligned");
+        return fail(GEMX_ERR_ARG, "%s: length_dev, obs0_dev, refs_dev, noise_dev and actions_out_dev must be 4-byte aligned", what);
     const gemx_config &c = h->cfg;
     // what the kernel does not serve (the episodic rollout's list): refused here, before anything is launched
-    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "policy rollout: fp32 handles only (the fp64 build is a diagnostic; step it)");
-    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "policy rollout: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver");
-    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "policy rollout: solver kind %d is not built; EulerSolver or RK4Solver", c.solver_kind);
-    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "policy rollout: a converter interlocking time (dead time) is not available");
-    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "policy rollout: a DeadTimeProcessor (action_delay > 0) is not available");
-    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "policy rollout: an RCVoltageSupply is not available");
-    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "policy rollout: random initial states are not available (an env restarts inside the launch from the handle's one initial state)");
-    if (p->device != h->device) return fail(GEMX_ERR_ARG, "policy rollout: the policy lives on device %d, the handle on device %d", p->device, h->device);
-    if (call->n_ref < 0 || call->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "policy rollout: n_ref = %d; 0 to %d", call->n_ref, GEMX_MAX_REF);
-    if (call->n_ref > 0 && !call->refs_dev) return fail(GEMX_ERR_ARG, "policy rollout: refs_dev must not be null with n_ref = %d", call->n_ref);
-    if (call->n_cols < 0 || call->n_cols > h->nout) return fail(GEMX_ERR_ARG, "policy rollout: n_cols = %d; 0 to %d", call->n_cols, h->nout);
+    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "%s: fp32 handles only (the fp64 build is a diagnostic; step it)", what);
+    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "%s: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver", what);
+    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "%s: solver kind %d is not built; EulerSolver or RK4Solver", what, c.solver_kind);
+    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "%s: a converter interlocking time (dead time) is not available", what);
+    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "%s: a DeadTimeProcessor (action_delay > 0) is not available", what);
+    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "%s: an RCVoltageSupply is not available", what);
+    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "%s: random initial states are not available (an env restarts inside the launch from the handle's one initial state)", what);
+    if (p->device != h->device) return fail(GEMX_ERR_ARG, "%s: the policy lives on device %d, the handle on device %d", what, p->device, h->device);
+    if (call->n_ref < 0 || call->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "%s: n_ref = %d; 0 to %d", what, call->n_ref, GEMX_MAX_REF);
+    if (call->n_ref > 0 && !call->refs_dev) return fail(GEMX_ERR_ARG, "%s: refs_dev must not be null with n_ref = %d", what, call->n_ref);
+    if (call->n_cols < 0 || call->n_cols > h->nout) return fail(GEMX_ERR_ARG, "%s: n_cols = %d; 0 to %d", what, call->n_cols, h->nout);
     if (call->n_cols + call->n_ref != p->n_in)
-        return fail(GEMX_ERR_ARG, "policy rollout: %d observation columns + %d references = %d inputs, the policy's first layer takes %d", call->n_cols, call->n_ref, call->n_cols + call->n_ref, p->n_in);
-    gemx::PolicyDev pol;
+        return fail(GEMX_ERR_ARG, "%s: %d observation columns + %d references = %d inputs, the policy's first layer takes %d", what, call->n_cols, call->n_ref, call->n_cols + call->n_ref, p->n_in);
     memset(&pol, 0, sizeof(pol));
     for (int j = 0; j < GEMX_MAX_OUT; ++j) pol.pos[j] = -1;
     for (int i = 0; i < call->n_cols; ++i) {
         const int col = call->columns[i];
-        if (col < 0 || col >= h->nout) return fail(GEMX_ERR_ARG, "policy rollout: columns[%d] = %d is outside the row of %d columns", i, col, h->nout);
-        if (pol.pos[col] >= 0) return fail(GEMX_ERR_ARG, "policy rollout: column %d is selected twice", col);
+        if (col < 0 || col >= h->nout) return fail(GEMX_ERR_ARG, "%s: columns[%d] = %d is outside the row of %d columns", what, i, col, h->nout);
+        if (pol.pos[col] >= 0) return fail(GEMX_ERR_ARG, "%s: column %d is selected twice", what, col);
         pol.pos[col] = (int8_t)i;
     }
     pol.blob = p->blob;
@@ -1454,6 +1459,12 @@ int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_
     pol.refs = (const float *)call->refs_dev;
     pol.noise = (const float *)call->noise_dev;
     pol.actions_out = call->actions_out_dev;
+    return GEMX_OK;
+}
+int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *stream) {
+    gemx::PolicyDev pol;
+    if (const int rc = policy_prepare(h, p, call, "policy rollout", pol)) return rc;
+    const gemx_config &c = h->cfg;
     gemx::DeviceGuard guard(h->device);
     gemx_pl_unit_launch_fn fn = nullptr;
     if (const int rc = load_pl_unit(c.system_kind, h->conv_unit, &fn)) return rc;
@@ -1464,6 +1475,42 @@ int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_
     h->steps_total += (unsigned long long)call->K;
     char key[256];
     snprintf(key, sizeof(key), "policy_rollout_kernel<%d, %d, %d, %d, %s, float>", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver, h->ll.d ? "true" : "false");
+    gemx_cov_note(key);
+    if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
+    return GEMX_OK;
+}
+// ---- the policy rollout of the complete env: the generators stepped inside the launch (include/gemx.h; gemx_policy_complete.hpp, gemx_policy_complete.hip)
+int gemx_rollout_policy_complete(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *refs_out_dev, gemx_refgen *refgen, gemx_refprofile *refprofile,
+                                 void *stream) {
+    static const char *const what = "complete policy rollout";
+    gemx::PolicyDev pol;
+    if (const int rc = policy_prepare(h, p, call, what, pol)) return rc;
+    if ((refgen != nullptr) == (refprofile != nullptr)) return fail(GEMX_ERR_ARG, "%s: exactly one of the gemx_refgen and the gemx_refprofile must be given", what);
+    if (call->n_ref < 1) return fail(GEMX_ERR_ARG, "%s: n_ref = %d; the generator's 1 to %d columns", what, call->n_ref, GEMX_MAX_REF);
+    if (!refs_out_dev || ((uintptr_t)refs_out_dev & 3u) != 0) return fail(GEMX_ERR_ARG, "%s: refs_out_dev must not be null and must be 4-byte aligned", what);
+    const gemx_config &c = h->cfg;
+    gemx::PcWienerDev wiener;
+    gemx::PcProfileDev profile;
+    int gen_n_ref = 0;
+    if (refgen != nullptr) {
+        if (const int rc = gemx::refgen_policy_view(refgen, what, h->n, h->device, c.env_base, &wiener, &gen_n_ref)) return rc;
+    } else if (const int rc = gemx::refprofile_policy_view(refprofile, what, h->n, h->device, c.env_base, &profile)) return rc;
+    else gen_n_ref = profile.P.n_ref;
+    if (gen_n_ref != call->n_ref) return fail(GEMX_ERR_ARG, "%s: the generator has %d columns, the call n_ref = %d", what, gen_n_ref, call->n_ref);
+    const gemx::PcRefs refs = {(const float *)call->refs_dev, (float *)refs_out_dev};
+    gemx::DeviceGuard guard(h->device);
+    gemx_pc_unit_launch_fn fn = nullptr;
+    if (const int rc = load_pc_unit(c.system_kind, h->conv_unit, &fn)) return rc;
+    // (all-Wiener: the K * N * n_ref standard normals of these steps into refs_out, in front; the lanes write the references over them)
+    if (refgen != nullptr)
+        if (const int rc = gemx::refgen_policy_normals(refgen, call->K, refs_out_dev, (hipStream_t)stream)) return rc;
+    int linmap_built = 0;
+    const int rc = fn(h, &pol, &refs, refgen != nullptr ? &wiener : nullptr, refgen != nullptr ? nullptr : &profile, call->K, call->length_dev, call->max_steps, call->obs_out_dev,
+                      call->terminated_out_dev, call->truncated_out_dev, call->ended_out_dev, (hipStream_t)stream, &linmap_built);
+    if (rc != GEMX_OK) return rc;
+    h->steps_total += (unsigned long long)call->K;
+    char key[256];
+    snprintf(key, sizeof(key), "policy_complete_rollout_kernel<%d, %d, %d, %d, %s, %d, float>", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver, h->ll.d ? "true" : "false", h->ll.il);
     gemx_cov_note(key);
     if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
     return GEMX_OK;
@@ -1481,7 +1528,10 @@ int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int
 const char *gemx_last_launch(const gemx_handle *h) {
     if (!h) return "";
     const auto &l = h->ll;
-    if (l.pipe == gemx::EP_LAUNCH_POLICY)
+    if (l.pipe == gemx::EP_LAUNCH_POLICY_COMPLETE)
+        snprintf(h->last_launch, sizeof(h->last_launch), "gemx::policy_complete_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,gen=%s,f32> grid=%lld x %d threads, lds=%zu B, K=%d, max_steps=%d, unit libgemx_pc%d_%d.so%s",
+                 l.sys, l.conv, l.load, l.solver, l.d, l.il == gemx::PC_GEN_WIENER ? "wiener" : "profile", l.blocks, l.threads, l.lds, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
+    else if (l.pipe == gemx::EP_LAUNCH_POLICY)
         snprintf(h->last_launch, sizeof(h->last_launch), "gemx::policy_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,f32> grid=%lld x %d threads, lds=%zu B, K=%d, max_steps=%d, unit libgemx_pl%d_%d.so%s",
                  l.sys, l.conv, l.load, l.solver, l.d, l.blocks, l.threads, l.lds, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
     else if (l.pipe == EP_LAUNCH_EPISODIC)

@@ -1,40 +1,28 @@
-// gemx_policy.hip -- ONE policy rollout unit: K control steps per launch with the episode time limit AND the actor inside the launch
-// (gemx_rollout_policy), for one (system, converter unit), fp32, built as its own shared object
-//   hipcc -DGEMX_INST_SYS=<0..7> -DGEMX_INST_CONV=<0..11> -shared gemx_policy.hip -o libgemx_pl<S>_<C>.so
-// and loaded with dlopen by the first gemx_rollout_policy of such a handle (gemx_capi.hip: load_pl_unit).  The stepping units, the per-env
-// units and the episodic units (gemx_episodic.hip) are untouched.
+// gemx_policy_complete.hip -- ONE complete policy rollout unit: policy_rollout_kernel (gemx_policy.hip) with the env's own reference
+// generators stepped in the lane that steps the env (gemx_rollout_policy_complete), for one (system, converter unit), fp32, built as its
+// own shared object
+//   hipcc -DGEMX_INST_SYS=<0..7> -DGEMX_INST_CONV=<0..11> -shared gemx_policy_complete.hip -o libgemx_pc<S>_<C>.so
+// and loaded with dlopen by the first gemx_rollout_policy_complete of such a handle (gemx_capi.hip: load_pc_unit).  The policy units
+// (libgemx_pl<S>_<C>.so) are untouched.
 //
-// The kernel is episodic_rollout_kernel (gemx_episodic.hip) with one change: the action of step k is not read from a tensor, it is computed
-// in front of the step by a small MLP from the row step k - 1 left in the lane's registers,
-//     x = [obs_prev[columns], references[k]],   out = W_L act(... act(W_1 x + b_1) ...) + b_L,
-//     continuous converters: action = squash(out + noise[k]);   finite converters: action = the lowest index among the maxima of out + noise[k]
-// obs_prev is obs0 at k = 0 and the handle's reset observation behind a step that ended the episode (what the masked reset writes); it is
-// never re-read from memory.  The action is stored to actions_out [K][N][A] | [K][N] uint8.  Everything behind the action -- the control
-// step, the pin of the stepped state, episode_row's rule, the row store in front of the restart -- is the episodic kernel's code, statement
-// for statement, so the physics rows are bit for bit what gemx_rollout_episodic writes when fed the stored actions (tests).
+// The kernel is policy_rollout_kernel, statement for statement, with two changes:
+//   * the references the actor of step k reads are not row k of a given tensor but the row the env SHOWED in front of step k: `shown`
+//     [N][n_ref] at k = 0, refs_out[k - 1] afterwards -- the fp32 words this lane stored, re-read;
+//   * behind the row store of step k the lane restarts its generators if the step ended the episode, advances them and stores
+//     refs_out[k] -- the shell's order (restart first, then advance), which gemx_refgen_rollout_shell and gemx_refprofile_rollout_shell
+//     replay on the ENDED rows.  The lane functions are the generator units' own (gemx_refgen_lane.hpp, gemx_refprofile_lane.hpp), so the
+//     rows and the state left behind are theirs bit for bit.
+// GEN, a template parameter, is the generator kind: PC_GEN_WIENER (an all-Wiener gemx_refgen) or PC_GEN_PROFILE (a gemx_refprofile).
 //
-// THE ACTOR: per-lane FMAs, not the exact-f32 MFMA.  One lane is one env, and its observation, its hidden activations and its state live in
-// that lane's registers; a dot product is a chain  acc = fmaf(w, x_i, acc)  over the inputs in ASCENDING order starting from the bias --
-// layer 0: the selected observation columns in ascending COLUMN order, then the references; later layers: the previous layer's outputs in
-// order.  v_mfma_f32_16x16x4_f32 has the same numerics and, on gfx950, the same peak rate as the f32 VALU (64 FLOP/clk/SIMD), so it buys no
-// throughput here, and it wants the wave's 64 envs as the N index of four 16-wide tiles with the activations laid ACROSS lanes: every layer
-// would transpose registers <-> lanes through LDS or DPP, in front of a control step that needs them per lane again.  The weights are staged
-// once per workgroup into LDS (gemx_policy.hpp: the blob as it is) and read at wave-uniform addresses: one 16-byte LDS read (4 LDS cycles
-// per wave) feeds 4 FMAs (16 VALU cycles per wave), which four SIMDs sharing one LDS would sustain exactly.  Activations stay in registers: every
-// index into them is a compile-time constant (the loop over 8-output blocks is a runtime loop whose block lands in the array through a
-// switch on the wave-uniform block index), so nothing goes to scratch.  Widths are runtime values: inputs are skipped in wave-uniform
-// blocks of 8, outputs in blocks of 8 -- a (16,) plan costs a quarter of a (64,) plan.
-//
-// Workgroups are 64 lanes (one wave stages the blob for itself) while there are at most four waves per CU, 256 lanes above that: four
-// waves then stage and share one copy of the blob instead of four.
-//
-// What this costs, as compiled: the two activation sets (2 x 64 registers), the accumulators, the weights in flight and the control step's
-// own registers exceed the 256 architectural VGPRs, the allocator parks the rest in AGPRs (profiles/policy_rollout.md lists all 152
-// instantiations: 254-256 VGPRs, up to 160 AGPRs, 120-240 SGPRs spilled to VGPR lanes, no scratch), so ONE wave is resident per SIMD and
-// nothing hides a wave's LDS and memory latency but its own instruction-level parallelism.  The LDS-to-FMA balance above is arithmetic from
-// the documented instruction rates and the MFMA comparison is from the documented peak rates; neither has been measured with this kernel,
-// and no rate of it has been measured at all.  A form with one live activation set (outputs rolled through LDS, or a narrower maximal
-// width) would lift the occupancy; it is not what this file does.
+// Where the generator state lives: in the handle's arrays, not in registers.  The policy kernels already fill the register file
+// (profiles/policy_rollout.md), so the 36 bytes per Wiener column (value, sigma, left, n_sub, n_reset; t is not needed, below) and the 12
+// bytes per env of a profile are read behind the row store, used and written back at once; a lane touches its own words only, they stay
+// in L2 between steps, and against the actor's FMAs the traffic is nothing.  A compiler barrier at the top of the step keeps the
+// optimiser from promoting them to loop-carried registers.  The Wiener step's double log / sqrt / cos do not run here either:
+// refgen_normals_kernel fills refs_out with the K * N * n_ref standard normals in a launch in front (what gemx_refgen_rollout_shell does),
+// the lane reads z from refs_out[k] and writes the reference over it, and the step counters move by K in the epilogue.  The rare paths
+// (new_subepisode's pow, reset_generator) stay in the lane.  The profile's wave-uniform table read is kept: tail lanes recompute env
+// N - 1 (their stores masked), so all 64 lanes arrive at the vote.  What this compiles to: profiles/policy_complete_rollout.md.
 #include <cstdarg>
 #include <cstdio>
 
@@ -42,6 +30,9 @@
 #include "gemx_envparams.hpp"
 #include "gemx_envparams_dev.hpp"
 #include "gemx_policy_dev.hpp"
+#include "gemx_policy_complete.hpp"
+#define GEMX_REFPROFILE_ROW_ONLY  // the head section of gemx_refprofile.hip: the one definition of profile_row
+#include "gemx_refprofile.hip"
 
 #if !defined(GEMX_INST_SYS) || !defined(GEMX_INST_CONV)
 #error "define GEMX_INST_SYS and GEMX_INST_CONV"
@@ -59,11 +50,68 @@ int fail(int code, const char *fmt, ...) {  // gemx_common.hpp declares it; in a
     return code;
 }
 
-// (the activations as register vectors, pl_fma8 and the other helpers of the actor: gemx_policy_dev.hpp, shared with gemx_policy_complete.hip)
+// (the activations as register vectors, pl_fma8 and the other helpers of the actor: gemx_policy_dev.hpp, shared with gemx_policy.hip)
 
-template <int SYS, int CONV, int LOAD, int SOLVER, bool TAB, class R>
-__global__ __launch_bounds__(PL_BLOCK_MAX) void policy_rollout_kernel(const KArgs<R> a, const R *__restrict__ tab, const int32_t *__restrict__ length_in, const int32_t M,
-                                                                      uint8_t *__restrict__ truncated, uint8_t *__restrict__ ended, const PolicyDev pol) {
+template <int GEN> struct PcGenDev { using T = PcWienerDev; };
+template <> struct PcGenDev<PC_GEN_PROFILE> { using T = PcProfileDev; };
+
+// Row k of the references, behind the row store of step k: restart where the episode ended, advance, store.  Everything is read from the
+// handle's arrays and written back here (a lane touches the words of its own env only); nothing of it is live across the actor.
+// Lanes behind N take no part -- but for the profile's wave vote, which all 64 lanes reach together.
+template <int GEN>
+__device__ __forceinline__ void pc_references(const typename PcGenDev<GEN>::T &gen, float *__restrict__ refs_out, int64_t N, int n_ref, int k, int64_t env, bool valid, bool end) {
+    if constexpr (GEN == PC_GEN_WIENER) {
+        using namespace refgen_lane;
+        // (the description is read from device memory, one column after the other in a rolled loop: as a kernel argument its columns'
+        // ranges were computed in front of the K-step loop and carried through the actor in registers, and indexed by a runtime column
+        // it went to scratch)
+        const RefgenDev &G = *gen.G;
+        if (!valid) return;
+#pragma unroll 1
+        for (int g = 0; g < n_ref; ++g) {
+            const int64_t si = (int64_t)g * N + env, o = ((int64_t)k * N + env) * n_ref + g;
+            double v = gen.value[si], sg = gen.sigma[si];
+            int32_t lf = gen.left[si];
+            if (end) {
+                uint32_t nr = gen.n_reset[si], ns = 0u;
+                reset_generator(G, env, g, nr, ns, lf, sg, v);
+                gen.n_reset[si] = nr;
+            }
+            if (lf <= 0) {
+                uint32_t ns = gen.n_sub[si];
+                new_subepisode(G, env, g, ns, lf, sg);
+                gen.n_sub[si] = ns;
+                gen.sigma[si] = sg;
+            }
+            v = walk_step(G, g, v, sg, (double)refs_out[o]);  // (z: refgen_normals_kernel left it there)
+            --lf;
+            gen.value[si] = v;
+            gen.left[si] = lf;
+            refs_out[o] = (float)v;
+        }
+    } else {
+        using namespace profile_lane;
+        const ProfileDev &P = gen.P;
+        ProfileLane s = {0, 0, 0u};
+        float row[GEMX_MAX_REF];
+        if (valid) {
+            s = profile_load(gen.state, N, env);
+            if (end) profile_restart(P, env, s);
+        }
+        profile_row<float>(P, gen.tab, env, valid, s, row);
+        if (valid) {
+            profile_save(gen.state, N, env, s);
+#pragma unroll
+            for (int g = 0; g < GEMX_MAX_REF; ++g)
+                if (g < n_ref) refs_out[((int64_t)k * N + env) * n_ref + g] = row[g];
+        }
+    }
+}
+
+template <int SYS, int CONV, int LOAD, int SOLVER, bool TAB, int GEN, class R>
+__global__ __launch_bounds__(PL_BLOCK_MAX) void policy_complete_rollout_kernel(const KArgs<R> a, const R *__restrict__ tab, const int32_t *__restrict__ length_in, const int32_t M,
+                                                                               uint8_t *__restrict__ truncated, uint8_t *__restrict__ ended, const PolicyDev pol,
+                                                                               const PcRefs refs, const typename PcGenDev<GEN>::T gen) {
     static_assert(sizeof(R) == 4, "the policy rollout is fp32");
     constexpr int ND = SysTraits<SYS>::ND, NOUT = SysTraits<SYS>::NOUT, NACT = ConvTraits<CONV>::NACT;
     constexpr bool DISCRETE = ConvTraits<CONV>::DISCRETE;
@@ -109,12 +157,18 @@ __global__ __launch_bounds__(PL_BLOCK_MAX) void policy_rollout_kernel(const KArg
 
     uint32_t bad_action = 0;
     for (int k = 0; k < K; ++k) {
-        // ---- the actor.  Layer 0: x = [op[columns], references[k]], the observation columns in ascending column order
+        // (a compiler barrier, no instruction: the generator state and the reference row of step k - 1 are re-read from memory, not
+        // carried through the actor in registers)
+        asm volatile("" ::: "memory");
+        // ---- the actor.  Layer 0: x = [op[columns], the references shown in front of step k], the observation columns in ascending
+        // column order; the references: `shown` at k = 0, then the row this lane stored behind step k - 1 (lanes behind N: zeros --
+        // they have stored none)
         const pl_v8 zero8 = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
         PlAct ha = {zero8, zero8, zero8, zero8, zero8, zero8, zero8, zero8}, hb = ha;  // (per step: nothing of them is live across the control step)
         float rf[GEMX_MAX_REF];
+        const float *shown = k == 0 ? refs.shown + e * pol.n_ref : refs.out + ((int64_t)(k - 1) * N + e) * pol.n_ref;
 #pragma unroll
-        for (int r = 0; r < GEMX_MAX_REF; ++r) rf[r] = r < pol.n_ref ? pol.refs[((int64_t)k * N + e) * pol.n_ref + r] : 0.0f;
+        for (int r = 0; r < GEMX_MAX_REF; ++r) rf[r] = (valid && r < pol.n_ref) ? shown[r] : 0.0f;
         const float *lw = lds;
         {
             const int rows = pol.n_in, jb_n = (pol.width[0] + 7) >> 3;
@@ -244,6 +298,8 @@ __global__ __launch_bounds__(PL_BLOCK_MAX) void policy_rollout_kernel(const KArg
             if (truncated != nullptr) truncated[at] = trunc ? 1 : 0;
             if (ended != nullptr) ended[at] = end ? 1 : 0;
         }
+        // ---- the references: the generators of an env that ended restart, then every generator advances -> refs_out[k]
+        pc_references<GEN>(gen, refs.out, N, pol.n_ref, k, env, valid, end);
         // the next step's actor input: the row just stored, or the reset observation where the episode ended -- from registers and LDS
 #pragma unroll
         for (int c = 0; c < NOUT; ++c) op[c] = end ? reset_row[c] : obs[c];
@@ -254,20 +310,22 @@ __global__ __launch_bounds__(PL_BLOCK_MAX) void policy_rollout_kernel(const KArg
         for (int j = 0; j < ND; ++j) a.state[(int64_t)j * N + env] = y[j];
         if (SysTraits<SYS>::HAS_ANGLE) a.angle[env] = ang;
         if (bad_action) atomicOr(a.err, 1u);
+        if constexpr (GEN == PC_GEN_WIENER) {  // the index of the normal draws: K steps on (refgen_walk_kernel's last line)
+#pragma unroll
+            for (int g = 0; g < GEMX_MAX_REF; ++g)
+                if (g < pol.n_ref) gen.t[(int64_t)g * N + env] += (uint64_t)K;
+        }
     }
-}
-
-// the unit's tanhf over n values: the tests' epsilon_tanh is measured on what the actor calls
-__global__ void pl_tanh_kernel(const float *__restrict__ x, float *__restrict__ y, long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) y[i] = tanhf(x[i]);
 }
 
 // ------------------------------------------------------------------------------------------------
 // host launcher
 // ------------------------------------------------------------------------------------------------
-struct PlCall {
+struct PcCall {
     const PolicyDev *pol;
+    const PcRefs *refs;
+    const PcWienerDev *wiener;    // exactly one of the two
+    const PcProfileDev *profile;
     int K;
     const int32_t *length;
     int32_t max_steps;
@@ -276,16 +334,23 @@ struct PlCall {
     int *linmap_built;
 };
 
+template <int SYS, int CONV, int LOAD, int SOLVER, bool TAB, int GEN>
+static void launch_pc_kernel(const KArgs<float> &a, const float *tab, const PcCall &c, const PolicyDev &pol, const typename PcGenDev<GEN>::T &gen, unsigned blocks, int threads,
+                             size_t lds, hipStream_t st) {
+    hipLaunchKernelGGL((policy_complete_rollout_kernel<SYS, CONV, LOAD, SOLVER, TAB, GEN, float>), dim3(blocks), dim3(threads), lds, st, a, tab, c.length, c.max_steps,
+                       c.truncated, c.ended, pol, *c.refs, gen);
+}
+
 template <int SYS, int CONV, int LOAD, int SOLVER>
-static int launch_pl_t(gemx_handle *h, const PlCall &c, hipStream_t st) {
+static int launch_pc_t(gemx_handle *h, const PcCall &c, hipStream_t st) {
     using R = float;
     constexpr int NLOGIT = ConvTraits<CONV>::DISCRETE ? ConvTraits<CONV>::NACTIONS : ConvTraits<CONV>::NACT;
     PolicyDev pol = *c.pol;
     if (pol.width[pol.n_layers - 1] != NLOGIT)
-        return fail(GEMX_ERR_ARG, "policy rollout: the policy's output width is %d, the converter takes %d (%s)", pol.width[pol.n_layers - 1], NLOGIT,
+        return fail(GEMX_ERR_ARG, "complete policy rollout: the policy's output width is %d, the converter takes %d (%s)", pol.width[pol.n_layers - 1], NLOGIT,
                     ConvTraits<CONV>::DISCRETE ? "one logit per discrete action" : "one output per action component");
     const bool tab = h->envp != nullptr;
-    if (!tab && h->linmap_state == 0) {  // once per handle, exactly as the episodic unit's launcher builds it: the electrical subsystem's one-step map
+    if (!tab && h->linmap_state == 0) {  // once per handle, exactly as the policy unit's launcher builds it: the electrical subsystem's one-step map
         if constexpr (linable<SYS, LOAD, SOLVER, false, R>()) {
             hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
             (void)hipStreamIsCapturing(st, &capturing);
@@ -327,48 +392,43 @@ static int launch_pl_t(gemx_handle *h, const PlCall &c, hipStream_t st) {
     const int threads = waves > 4 * (int64_t)h->n_cu ? PL_BLOCK_MAX : 64;
     const int64_t blocks = (h->n + threads - 1) / threads;
     const size_t lds = sizeof(float) * ((size_t)pol.blob_words + SysTraits<SYS>::NOUT);
-    if (tab)
-        hipLaunchKernelGGL((policy_rollout_kernel<SYS, CONV, LOAD, SOLVER, true, R>), dim3((unsigned)blocks), dim3(threads), lds, st, a, (const R *)h->envp, c.length,
-                           c.max_steps, c.truncated, c.ended, pol);
-    else
-        hipLaunchKernelGGL((policy_rollout_kernel<SYS, CONV, LOAD, SOLVER, false, R>), dim3((unsigned)blocks), dim3(threads), lds, st, a, (const R *)nullptr, c.length,
-                           c.max_steps, c.truncated, c.ended, pol);
+    const bool wiener = c.wiener != nullptr;
+    if (tab && wiener) launch_pc_kernel<SYS, CONV, LOAD, SOLVER, true, PC_GEN_WIENER>(a, (const R *)h->envp, c, pol, *c.wiener, (unsigned)blocks, threads, lds, st);
+    else if (tab) launch_pc_kernel<SYS, CONV, LOAD, SOLVER, true, PC_GEN_PROFILE>(a, (const R *)h->envp, c, pol, *c.profile, (unsigned)blocks, threads, lds, st);
+    else if (wiener) launch_pc_kernel<SYS, CONV, LOAD, SOLVER, false, PC_GEN_WIENER>(a, nullptr, c, pol, *c.wiener, (unsigned)blocks, threads, lds, st);
+    else launch_pc_kernel<SYS, CONV, LOAD, SOLVER, false, PC_GEN_PROFILE>(a, nullptr, c, pol, *c.profile, (unsigned)blocks, threads, lds, st);
     GEMX_HIP_TRY(hipGetLastError());
-    h->ll = {EP_LAUNCH_POLICY, SYS, CONV, LOAD, SOLVER, 0, (int)sizeof(R), tab ? 1 : 0, threads, c.K, c.max_steps, (long long)blocks, lds};
+    h->ll = {EP_LAUNCH_POLICY_COMPLETE, SYS, CONV, LOAD, SOLVER, wiener ? PC_GEN_WIENER : PC_GEN_PROFILE, (int)sizeof(R), tab ? 1 : 0, threads, c.K, c.max_steps, (long long)blocks, lds};
     return GEMX_OK;
 }
 
 template <int SYS, int CONV>
-static int launch_pl_unit(gemx_handle *h, const PlCall &c, hipStream_t st) {
+static int launch_pc_unit(gemx_handle *h, const PcCall &c, hipStream_t st) {
     const int ld = h->cfg.load_kind, sv = h->cfg.solver_kind;
-#define GEMX_PL_LS(LD, SV) \
-    if (ld == LD && sv == SV) return launch_pl_t<SYS, CONV, LD, SV>(h, c, st);
-    GEMX_PL_LS(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_EULER)
-    GEMX_PL_LS(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_RK4)
-    GEMX_PL_LS(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_EULER)
-    GEMX_PL_LS(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_RK4)
-#undef GEMX_PL_LS
-    return fail(GEMX_ERR_ARG, "policy rollout: load/solver combination %d/%d is not built (EulerSolver and RK4Solver only)", ld, sv);
+#define GEMX_PC_LS(LD, SV) \
+    if (ld == LD && sv == SV) return launch_pc_t<SYS, CONV, LD, SV>(h, c, st);
+    GEMX_PC_LS(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_EULER)
+    GEMX_PC_LS(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_RK4)
+    GEMX_PC_LS(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_EULER)
+    GEMX_PC_LS(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_RK4)
+#undef GEMX_PC_LS
+    return fail(GEMX_ERR_ARG, "complete policy rollout: load/solver combination %d/%d is not built (EulerSolver and RK4Solver only)", ld, sv);
 }
 }  // namespace gemx
 
 extern "C" {
 // GEMX_OK if this unit was compiled against the caller's handle layout and ABI
-__attribute__((visibility("default"))) int gemx_pl_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
+__attribute__((visibility("default"))) int gemx_pc_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
     if (handle_bytes != (unsigned long long)sizeof(gemx_handle) || abi != GEMX_ABI_VERSION) return GEMX_ERR_ARG;
     gemx::g_set_error = set_error;
     return GEMX_OK;
 }
-__attribute__((visibility("default"))) int gemx_pl_unit_launch(gemx_handle *h, const gemx::PolicyDev *pol, int K, const int32_t *length, int32_t max_steps, void *obs,
-                                                               uint8_t *terminated, uint8_t *truncated, uint8_t *ended, hipStream_t st, int *linmap_built) {
-    if (h->envp != nullptr && h->envp_fields != gemx::ep_fields(GEMX_INST_SYS)) return gemx::fail(GEMX_ERR_ARG, "internal: policy rollout unit launched with another system's table");
-    const gemx::PlCall c = {pol, K, length, max_steps, obs, terminated, truncated, ended, linmap_built};
-    return gemx::launch_pl_unit<GEMX_INST_SYS, GEMX_INST_CONV>(h, c, st);
-}
-__attribute__((visibility("default"))) int gemx_pl_unit_tanh(const float *x, float *y, long long n, hipStream_t st) {
-    if (n <= 0) return GEMX_OK;
-    hipLaunchKernelGGL(gemx::pl_tanh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n);
-    GEMX_HIP_TRY(hipGetLastError());
-    return GEMX_OK;
+__attribute__((visibility("default"))) int gemx_pc_unit_launch(gemx_handle *h, const gemx::PolicyDev *pol, const gemx::PcRefs *refs, const gemx::PcWienerDev *wiener,
+                                                               const gemx::PcProfileDev *profile, int K, const int32_t *length, int32_t max_steps, void *obs, uint8_t *terminated,
+                                                               uint8_t *truncated, uint8_t *ended, hipStream_t st, int *linmap_built) {
+    if (h->envp != nullptr && h->envp_fields != gemx::ep_fields(GEMX_INST_SYS)) return gemx::fail(GEMX_ERR_ARG, "internal: complete policy rollout unit launched with another system's table");
+    if ((wiener != nullptr) == (profile != nullptr)) return gemx::fail(GEMX_ERR_ARG, "internal: complete policy rollout unit launched without exactly one generator view");
+    const gemx::PcCall c = {pol, refs, wiener, profile, K, length, max_steps, obs, terminated, truncated, ended, linmap_built};
+    return gemx::launch_pc_unit<GEMX_INST_SYS, GEMX_INST_CONV>(h, c, st);
 }
 }

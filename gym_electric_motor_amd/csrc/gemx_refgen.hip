@@ -64,32 +64,14 @@ struct gemx_refgen {
     uint32_t *n_super = nullptr;
     void *sdev = nullptr;
     RefgenBlobHeader blob_head;  // written by every gemx_refgen_get_blob, read by its copy
+    void *dev_desc = nullptr;    // RefgenDev of `cfg` in device memory, made by the first complete policy rollout (refgen_policy_view)
 };
 
 namespace {
 
-enum { DRAW_STEP = 0, DRAW_SUB = 1, DRAW_RESET = 2 };
-
-__device__ inline void refgen_block(uint64_t seed, int64_t env, int gen, int kind, uint64_t index, uint32_t (&r)[4]) {
-    // key: seed; counter: (env lo, env hi | gen << 24 | kind << 28, index lo, index hi)
-    const uint64_t env_word = (uint64_t)env | ((uint64_t)gen << 56) | ((uint64_t)kind << 60);
-    uint32_t c[4] = {(uint32_t)env_word, (uint32_t)(env_word >> 32), (uint32_t)index, (uint32_t)(index >> 32)};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    for (int i = 0; i < 10; ++i) {
-        gemx::Philox::round(c, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    for (int i = 0; i < 4; ++i) r[i] = c[i];
-}
-
-// the standard normal of step t of (env, generator): Box-Muller on two Philox words, rounded to the tensor's type
-template <class R> __device__ inline R step_normal(uint64_t seed, int64_t global_env, int g, uint64_t t) {
-    uint32_t r[4];
-    refgen_block(seed, global_env, g, DRAW_STEP, t, r);  // (the GLOBAL env index keys the stream)
-    const double u1 = gemx::Philox::u01(r[0]), u2 = gemx::Philox::u01(r[1]);
-    return (R)(sqrt(-2.0 * log(u1)) * cos(gemx::kTwoPi * u2));
-}
+// the draws, the sub-episode, the restart and the clipped walk of one (column, env): gemx_refgen_lane.hpp, through gemx_support.hpp (shared
+// with the complete policy rollout units, which step the generators in the lane that steps the env)
+using namespace gemx::refgen_lane;
 
 // (1) standard normals for steps t .. t+K-1 of every (env, generator), t = the (generator, env)'s step counter
 template <class R>
@@ -101,38 +83,6 @@ __global__ void refgen_normals_kernel(R *out, int64_t N, int n_ref, int K, uint6
     const int64_t env = (idx / n_ref) % N;
     const int64_t k = idx / ((int64_t)n_ref * N);
     out[idx] = step_normal<R>(seed, env_base + env, g, t[(int64_t)g * N + env] + (uint64_t)k);
-}
-
-struct RefgenDev {
-    int32_t n_ref, len_lo, len_hi;
-    uint64_t seed;
-    int64_t env_base;  // gemx_refgen_config.env_base
-    double log_sig_lo[GEMX_MAX_REF], log_sig_hi[GEMX_MAX_REF], m_lo[GEMX_MAX_REF], m_hi[GEMX_MAX_REF], i_lo[GEMX_MAX_REF], i_hi[GEMX_MAX_REF];
-};
-
-// SubepisodedReferenceGenerator.get_reference_observation, lines 104-111: a new sub-episode draws its length and its sigma
-__device__ inline void new_subepisode(const RefgenDev &G, int64_t env, int g, uint32_t &n_sub, int32_t &left, double &sigma) {
-    uint32_t r[4];
-    refgen_block(G.seed, G.env_base + env, g, DRAW_SUB, n_sub++, r);
-    // int((hi - lo) * U + lo), _get_current_value lines 116-119; then 10 ** U(log10 sigma_range), wiener ... line 31
-    left = (int32_t)((double)(G.len_hi - G.len_lo) * gemx::Philox::u01(r[0]) + (double)G.len_lo);
-    sigma = pow(10.0, (G.log_sig_hi[g] - G.log_sig_lo[g]) * gemx::Philox::u01(r[1]) + G.log_sig_lo[g]);
-}
-// WienerProcessReferenceGenerator.reset, lines 43-49: initial reference ~ U(initial_range); SubepisodedReferenceGenerator.reset 86-93
-__device__ inline void reset_generator(const RefgenDev &G, int64_t env, int g, uint32_t &n_reset, uint32_t &n_sub, int32_t &left, double &sigma,
-                                       double &value) {
-    uint32_t r[4];
-    refgen_block(G.seed, G.env_base + env, g, DRAW_RESET, n_reset++, r);
-    value = (G.i_hi[g] - G.i_lo[g]) * gemx::Philox::u01(r[0]) + G.i_lo[g];
-    left = 0;  // `_current_episode_length = -1`: the next get_reference_observation starts a sub-episode
-    (void)n_sub; (void)sigma;
-}
-// one step of the clipped walk, wiener_process_reference_generator.py:35-41
-__device__ inline double walk_step(const RefgenDev &G, int g, double value, double sigma, double z) {
-    value += sigma * z;
-    if (value > G.m_hi[g]) value = G.m_hi[g];
-    if (value < G.m_lo[g]) value = G.m_lo[g];
-    return value;
 }
 
 // (2) out[k][env][g] holds z on entry and the reference of step k on exit.  done[k][env] != 0: the env terminated in step k, its
@@ -786,6 +736,7 @@ int gemx_refgen_destroy(gemx_refgen *r) {
         if (*a.p) (void)hipFree(*a.p);
     });
     delete (RefgenSwitchedDev *)r->sdev;
+    if (r->dev_desc) (void)hipFree(r->dev_desc);
     delete r;
     return GEMX_OK;
 }
@@ -971,3 +922,37 @@ int gemx_refgen_set_blob(gemx_refgen *r, const void *in_dev, void *stream) {
 }
 
 }  // extern "C"
+
+// ---- the complete policy rollout (gemx_refgen_lane.hpp declares them): the kernel's view of an all-Wiener handle, and the normals in front of it
+namespace gemx {
+int refgen_policy_view(gemx_refgen *r, const char *what, int64_t n_envs, int device, int64_t env_base, PcWienerDev *out, int *n_ref) {
+    if (r->switched || r->mixed || r->has_kinds)
+        return fail(GEMX_ERR_ARG, "%s: a %s gemx_refgen is not served inside the launch (an all-Wiener gemx_refgen_create handle, or a gemx_refprofile)", what,
+                    r->switched ? "switched" : r->mixed ? "mixed-kinds" : "kinds");
+    if (r->n != n_envs) return fail(GEMX_ERR_ARG, "%s: the gemx_refgen serves n_envs = %lld, the handle %lld", what, (long long)r->n, (long long)n_envs);
+    if (r->f64) return fail(GEMX_ERR_ARG, "%s: the gemx_refgen is fp64, the handle fp32", what);
+    if (r->device != device) return fail(GEMX_ERR_ARG, "%s: the gemx_refgen lives on device %d, the handle on device %d", what, r->device, device);
+    if (r->cfg.env_base != env_base) return fail(GEMX_ERR_ARG, "%s: the gemx_refgen's env_base is %lld, the handle's %lld", what, (long long)r->cfg.env_base, (long long)env_base);
+    if (r->dev_desc == nullptr) {  // once per handle (synchronous: the first such call is not made inside a stream capture)
+        DeviceGuard guard(r->device);
+        const RefgenDev G = make_dev(r->cfg);
+        if (hipMalloc(&r->dev_desc, sizeof(G)) != hipSuccess) { r->dev_desc = nullptr; return fail(GEMX_ERR_ALLOC, "%s: hipMalloc(generator description) failed", what); }
+        if (hipMemcpy(r->dev_desc, &G, sizeof(G), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(r->dev_desc);
+            r->dev_desc = nullptr;
+            return fail(GEMX_ERR_DEVICE, "%s: hipMemcpy(generator description) failed", what);
+        }
+    }
+    *out = {(const RefgenDev *)r->dev_desc, r->value, r->sigma, r->left, r->n_sub, r->n_reset, r->t};
+    *n_ref = r->cfg.n_ref;
+    return GEMX_OK;
+}
+int refgen_policy_normals(gemx_refgen *r, int32_t K, void *refs_out_dev, hipStream_t st) {
+    const int64_t total = (int64_t)K * r->n * r->cfg.n_ref;
+    gemx_cov_note("refgen_normals_kernel<float>");
+    hipLaunchKernelGGL(refgen_normals_kernel<float>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)refs_out_dev, r->n, r->cfg.n_ref, K, r->cfg.seed, r->t,
+                       r->cfg.env_base);
+    GEMX_HIP_TRY(hipGetLastError());
+    return GEMX_OK;
+}
+}  // namespace gemx

@@ -19,58 +19,10 @@
 // behind N are predicated, not returned.
 #include "gemx_support.hpp"
 
-namespace {
-
-struct ProfileDev {  // uniform parameters, by value
-    int32_t n_ref, T, per_env, interp, wrap, random;
-    uint64_t seed;
-    int64_t env_base, N;
-    double ratio;  // tau / profile_tau
-};
-
-struct ProfileLane {
-    int32_t k, s;
-    uint32_t e;
-};
-
-constexpr uint32_t PROFILE_BLOCK_TAG = 0x50524F46u;  // "PROF": the block word of the start-row draw
-
-__device__ __forceinline__ void profile_restart(const ProfileDev &P, int64_t env, ProfileLane &s) {
-    s.k = 0;
-    s.e += 1u;
-    s.s = 0;
-    if (P.random) {
-        uint32_t r[4];
-        gemx::Philox::block(P.seed, (uint64_t)(P.env_base + env), s.e, PROFILE_BLOCK_TAG, r);
-        const int32_t row = (int32_t)(gemx::Philox::u01(r[0]) * (double)P.T);
-        s.s = row < P.T - 1 ? row : P.T - 1;
-    }
-}
-
-// the rows (ia, ib) in [0, T - 1] and the weight of the lane's position; whatever k and s hold (a counter that ran over, a foreign blob),
-// the rows stay inside the table
-__device__ __forceinline__ void profile_rows_of(const ProfileDev &P, const ProfileLane &s, int32_t &ia, int32_t &ib, double &w) {
-    const double p = __dadd_rn((double)s.s, __dmul_rn((double)s.k, P.ratio));
-    const int32_t last = P.T - 1;
-    if (P.wrap) {
-        const double fl = floor(p);
-        w = p - fl;
-        int64_t m = (int64_t)fl % (int64_t)P.T;
-        if (m < 0) m += P.T;
-        ia = (int32_t)m;
-        ib = ia == last ? 0 : ia + 1;
-    } else if (p >= (double)last) {
-        ia = ib = last; w = 0.0;
-    } else if (p >= 0.0) {
-        const double fl = floor(p);
-        w = p - fl;
-        ia = (int32_t)fl;
-        ib = ia + 1;
-    } else {
-        ia = ib = 0; w = 0.0;
-    }
-}
-
+// ---- THE row function (declared in gemx_refprofile_lane.hpp).  This section alone is what a complete policy rollout unit compiles of this
+// file: gemx_policy_complete.hip defines GEMX_REFPROFILE_ROW_ONLY and includes it, so that its kernel calls this definition, not a copy
+namespace gemx {
+namespace profile_lane {
 // one step of one env: the n_ref values at the lane's position into row[], then k += 1.  `active`: the lane has an env (all 64 lanes of a
 // wave come here together: the vote below needs them)
 template <class R>
@@ -107,6 +59,15 @@ __device__ __forceinline__ void profile_row(const ProfileDev &P, const R *__rest
         s.k += 1;
     }
 }
+}  // namespace profile_lane
+}  // namespace gemx
+
+#ifndef GEMX_REFPROFILE_ROW_ONLY
+namespace {
+
+// the uniform parameters, the 12 bytes of state and the restart of one env: gemx_refprofile_lane.hpp, through gemx_support.hpp (shared with the
+// complete policy rollout units, which show the profile in the lane that steps the env)
+using namespace gemx::profile_lane;
 
 // row [n_ref] of env `at` (an index into rows of n_ref values): one vector store where the launch found the tensor aligned to the row
 template <class R> __device__ __forceinline__ void profile_store(R *__restrict__ out, int64_t at, const R (&row)[GEMX_MAX_REF], int32_t n_ref, int vec) {
@@ -121,13 +82,6 @@ template <class R> __device__ __forceinline__ void profile_store(R *__restrict__
         for (int g = 0; g < GEMX_MAX_REF; ++g)
             if (g < n_ref) out[at * n_ref + g] = row[g];
     }
-}
-
-__device__ __forceinline__ ProfileLane profile_load(const int32_t *__restrict__ st, int64_t N, int64_t env) {
-    return {st[env], st[N + env], (uint32_t)st[2 * N + env]};
-}
-__device__ __forceinline__ void profile_save(int32_t *__restrict__ st, int64_t N, int64_t env, const ProfileLane &s) {
-    st[env] = s.k; st[N + env] = s.s; st[2 * N + env] = (int32_t)s.e;
 }
 
 __global__ __launch_bounds__(256) void refprofile_reset_kernel(ProfileDev P, int32_t *__restrict__ st, const uint8_t *__restrict__ mask) {
@@ -357,3 +311,16 @@ int gemx_refprofile_set_blob(gemx_refprofile *h, const void *in_dev, void *strea
 }
 
 }  // extern "C"
+
+// ---- the complete policy rollout (gemx_refprofile_lane.hpp declares it): the kernel's view of a profile handle
+namespace gemx {
+int refprofile_policy_view(gemx_refprofile *p, const char *what, int64_t n_envs, int device, int64_t env_base, PcProfileDev *out) {
+    if (p->n != n_envs) return fail(GEMX_ERR_ARG, "%s: the gemx_refprofile serves n_envs = %lld, the handle %lld", what, (long long)p->n, (long long)n_envs);
+    if (p->f64) return fail(GEMX_ERR_ARG, "%s: the gemx_refprofile is fp64, the handle fp32", what);
+    if (p->device != device) return fail(GEMX_ERR_ARG, "%s: the gemx_refprofile lives on device %d, the handle on device %d", what, p->device, device);
+    if (p->cfg.env_base != env_base) return fail(GEMX_ERR_ARG, "%s: the gemx_refprofile's env_base is %lld, the handle's %lld", what, (long long)p->cfg.env_base, (long long)env_base);
+    *out = {p->dev, (const float *)p->table, p->state};
+    return GEMX_OK;
+}
+}  // namespace gemx
+#endif  // GEMX_REFPROFILE_ROW_ONLY

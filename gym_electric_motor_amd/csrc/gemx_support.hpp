@@ -4,8 +4,12 @@
 // Row tile: rows of L dwords, contiguous in global memory, sit in LDS at an ODD dword stride so that lane r reads row r without bank
 // conflicts.  Global memory is moved in 16-byte units, consecutive lanes consecutive units; a unit straddles rows whenever L is no
 // multiple of four, so it is scattered into / gathered from the tile dword by dword.  An fp64 value is a pair of dwords.
+// The per-lane functions of the two generator units that the complete policy rollout units call too come in through this header
+// (gemx_refgen_lane.hpp, gemx_refprofile_lane.hpp): the generator units include nothing else.
 #pragma once
 #include "gemx_common.hpp"
+#include "gemx_refgen_lane.hpp"
+#include "gemx_refprofile_lane.hpp"
 
 void gemx_cov_note(const char *key);  // gemx_capi.hip: instantiation coverage (GEMX_COVERAGE_FILE)
 

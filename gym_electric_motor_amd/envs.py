@@ -90,7 +90,7 @@ import numpy as np
 from .spaces import Box
 from . import components as comp
 from . import physical_systems as bps
-from .reference_generators import ProfileReferences, ReplayReferenceGenerator
+from .reference_generators import BatchedMultipleReferenceGenerator, BatchedWienerProcessReferenceGenerator, ProfileReferences, ReplayReferenceGenerator
 
 _ID = re.compile(r"^(Finite|Cont)-(CC|TC|SC)-(PermExDc|SeriesDc|ShuntDc|ExtExDc|PMSM|SynRM|SCIM|EESM|DFIM)-v0$")
 
@@ -502,28 +502,29 @@ class BatchedElectricMotorEnv:
         torch, device = bps._torch(), self.physical_system._tdev
         return tuple(torch.empty(shape, dtype=dtype, device=device) if t is None else t for t, (_, dtype, shape) in zip(given, specs))
 
-    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False):
+    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False, generators=True):
         """-> the launchers behind the physics of a stored-rows rollout, in order: the episode stage's pass over the rows, the pipeline's
         launches over the stored rows.  The one thing the complete env does differently."""
         return episodes, self.pipeline.bind_after_rollout(raw, restart, None, outs[0], stream)
 
-    def _plan(self, physics, K, outs, truncated_out, stream, episode_statistics, eager=False, extra=()):
+    def _plan(self, physics, K, outs, truncated_out, stream, episode_statistics, eager=False, extra=(), generators=True):
         """-> launch() of any stored-rows rollout on fixed tensors, all on `stream` (default: the current one): `physics(raw, done |
         terminated, truncated, ended, stream)` -> its launcher; `_tail` (the complete env: generators and reward pass first, the
         references shown last); with a time limit (`truncated_out` given) row K-1 into the episode stage's bytes, its `reset_mask`
-        cleared.  outs: (obs_out, done_out) or (state_out, refs_out, reward_out, done_out); `launch()` returns outs[0], `extra`, the rest
-        of outs, truncated_out and the statistics dict, as far as they exist.  Decided here, once: where the physics writes, which rows
+        cleared.  outs: (obs_out, done_out) or (state_out, refs_out, reward_out, done_out); `launch()` returns outs but the last, `extra`
+        (a policy rollout's actions_out), the last of outs, truncated_out and the statistics dict, as far as they exist -- the order of
+        `_specs`.  generators=False: the physics has written refs_out and the generator state itself (the complete policy rollout).  Decided here, once: where the physics writes, which rows
         the episode stage's pass reads and writes, and the rows everything behind it restarts on -- ENDED with a time limit, else done."""
         ps, pipe = self.physical_system, self.pipeline
         stream = stream if stream is not None else bps._torch().cuda.current_stream(ps._tdev)
         done = outs[-1]
         raw = pipe.raw_rows(K, outs[0])
         episodes, stats = pipe.bind_episode_rows(done, outs[2] if len(outs) == 4 else None, episode_statistics, stream)  # (no reward rows: lengths only)
-        ended, last, result = done, None, outs[:1] + tuple(extra) + outs[1:]
+        ended, last, result = done, None, outs[:-1] + tuple(extra) + outs[-1:]
         if truncated_out is not None:
             ended = stats["ended"] if stats else pipe.ended_scratch
             last, result = pipe.episode.bind_after_episodic_rollout(truncated_out, ended, stream), result + (truncated_out,)
-        return bps._lib.sequence(physics(raw, done, truncated_out, ended, stream), *self._tail(K, raw, outs, ended, episodes, stream, eager), last,
+        return bps._lib.sequence(physics(raw, done, truncated_out, ended, stream), *self._tail(K, raw, outs, ended, episodes, stream, eager, generators), last,
                                  result=result + ((stats,) if stats else ()))
 
     def _episodic_physics(self, a, raw, terminated, truncated, ended, stream):
@@ -553,9 +554,11 @@ class BatchedElectricMotorEnv:
         return self._bind("bind_rollout_episodic", True, actions, (obs_out, terminated_out, truncated_out), stream, episode_statistics, episodic=True)
 
     # ------------------------------------------------------------------ policy rollouts: the actor inside the episodic launch
-    def _bind_policy(self, what, bound, policy, K, outs, obs0, references, noise, stream, episode_statistics):
+    def _bind_policy(self, what, bound, policy, K, outs, obs0, references, noise, stream, episode_statistics, complete=False):
         """-> launch() of the policy entry point `what`: the policy's own checks (no device call), then what `_bind` does -- check,
-        allocate what an eager call did not give, plan.  outs: (obs_out, actions_out, terminated_out, truncated_out)."""
+        allocate what an eager call did not give, plan.  outs: (obs_out, actions_out, terminated_out, truncated_out); complete (the
+        complete env's own references and reward in the loop): (state_out, refs_out, reward_out, actions_out, terminated_out,
+        truncated_out), no `references` -- the generator must be one the kernel steps in the lane."""
         from .episodes import episodic_refusal
         from .policy import MLPPolicy
 
@@ -570,14 +573,16 @@ class BatchedElectricMotorEnv:
             raise NotImplementedError(f"{what} is not available with a FluxObserver or any observation-side processor: the policy reads the raw state row")
         if getattr(ps, "_obs_layout", "aos") != "aos":
             raise NotImplementedError(f"{what} is not available with obs_layout='soa': the tensors are [K, N, S_out]")
+        if complete:
+            self._policy_generator(what)
         n_state, N = len(ps.state_names), ps.n_envs
         columns = list(range(n_state)) if policy.columns is None else list(policy.columns)
         if any(c >= n_state for c in columns):
             raise ValueError(f"{what}: the policy selects column {max(columns)}, the state row has {n_state} columns")
-        for name, t in (("obs0", obs0), ("references", references), ("noise", noise), ("actions_out", outs[1])):
+        for name, t in (("obs0", obs0), ("references", references), ("noise", noise), ("actions_out", outs[3 if complete else 1])):
             if torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16):
                 raise NotImplementedError(episodic_refusal(ps, f"a half-precision {name} tensor (fp32 tensors)"))
-        n_ref = 0
+        n_ref = len(self.reference_names) if complete else 0
         if references is not None:
             if not torch.is_tensor(references) or references.dim() != 3:
                 raise ValueError(f"{what}: references must be a tensor [K, N, n_ref]")
@@ -597,13 +602,20 @@ class BatchedElectricMotorEnv:
             self._check_tensor(what, noise, "noise", torch.float32, (K, N, n_logit))
         if obs0 is not None:
             self._check_tensor(what, obs0, "obs0", torch.float32, (N, n_state))
-        _, specs = self._check_call(what, K, None, outs, bound, episode_statistics, episodic=True, actions_out=True)
+        _, specs = self._check_call(what, K, None, outs, bound, episode_statistics, complete=complete, episodic=True, actions_out=True)
+        if complete:
+            state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out = self._allocate(specs, outs)
+            return self._plan(lambda *t: self._policy_physics(policy, K, columns, n_ref, obs0, self._refs, noise, actions_out, *t, refs_out=refs_out), K,
+                              (state_out, refs_out, reward_out, terminated_out), truncated_out, stream, episode_statistics, eager=not bound, extra=(actions_out,),
+                              generators=False)
         obs_out, actions_out, terminated_out, truncated_out = self._allocate(specs, outs)
         return self._plan(lambda *t: self._policy_physics(policy, K, columns, n_ref, obs0, references, noise, actions_out, *t), K, (obs_out, terminated_out),
                           truncated_out, stream, episode_statistics, eager=not bound, extra=(actions_out,))
 
-    def _policy_physics(self, policy, K, columns, n_ref, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream):
-        """-> the pending masked reset, then `gemx_rollout_policy` on fixed tensors (the policy counterpart of `_episodic_physics`)."""
+    def _policy_physics(self, policy, K, columns, n_ref, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream, refs_out=None):
+        """-> the pending masked reset, then `gemx_rollout_policy` on fixed tensors (the policy counterpart of `_episodic_physics`).
+        refs_out given: `gemx_rollout_policy_complete` -- `references` is then the [N, n_ref] row shown now, and the env's generator handle
+        goes with the call: the launch writes refs_out and advances the generators itself."""
         import ctypes as C
 
         ps, pipe = self.physical_system, self.pipeline
@@ -618,7 +630,13 @@ class BatchedElectricMotorEnv:
         call.terminated_out_dev, call.truncated_out_dev, call.ended_out_dev = terminated.data_ptr(), truncated.data_ptr(), ended.data_ptr()
         args = (policy._on_device(ps._device), C.byref(call), C.c_void_p(stream.cuda_stream))
         keep = (call, policy, obs0, references, noise, actions_out, raw, terminated, truncated, ended, stream, pipe.episode.length)
-        return lib.sequence(pipe.bind_before_step(stream), lib.counting_call(ps._L.gemx_rollout_policy, ps, K, args, keep))
+        entry = ps._L.gemx_rollout_policy
+        if refs_out is not None:
+            gen = self.reference_generator
+            profile = isinstance(gen, ProfileReferences)
+            args = args[:2] + (C.c_void_p(refs_out.data_ptr()), None if profile else gen._handle, gen._handle if profile else None) + args[2:]
+            keep, entry = keep + (refs_out, gen), ps._L.gemx_rollout_policy_complete
+        return lib.sequence(pipe.bind_before_step(stream), lib.counting_call(entry, ps, K, args, keep))
 
     def bind_rollout_policy_episodic(self, policy, K, obs_out, actions_out, terminated_out, truncated_out, obs0=None, references=None, noise=None, stream=None,
                                      episode_statistics=None):
@@ -808,20 +826,23 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         """(state, refs, reward, done) shapes of a complete K-step rollout: the output table's, for the callers that allocate them."""
         return tuple(shape for _, _, shape in self._specs(K, complete=True)[1])
 
-    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False):
+    def _tail(self, K, raw, outs, restart, episodes, stream, eager=False, generators=True):
         """-> the launchers that follow the physics of a complete K-step rollout, in order, on fixed tensors: the generators in the shell's
         order on the `restart` rows; the reward of row k against the references shown before step k; `episodes` (the episode stage's pass
         over the done and reward rows, directly behind the launch that completes them); the pipeline's launches over the stored rows; row
         K-1 into the references shown, on the launch stream (after the reward pass has read the old ones: `step()` and further rollouts
         continue from it).  restart [K, N]: the rows the generators restart on and the flux observer resets on -- `done_out`, or the ENDED
         rows of an episodic rollout, whose reward pass still reads the terminated rows `done_out`.  eager: run once, on the current
-        stream, so a ReplayReferenceGenerator (host state) can take part."""
+        stream, so a ReplayReferenceGenerator (host state) can take part.  generators=False: the physics launch has stepped the generators
+        in the lane and written refs_out (the complete policy rollout); their replay on the restart rows drops out, nothing else."""
         if len(outs) != 4:  # (the inherited physics-only rollouts: no references, no reward)
             return super()._tail(K, raw, outs, restart, episodes, stream, eager)
         torch = bps._torch()
         ps, gen = self.physical_system, self.reference_generator
         state_out, refs_out, reward_out, done_out = outs
-        if eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
+        if not generators:
+            generators = None
+        elif eager and isinstance(gen, ReplayReferenceGenerator):  # (host state: cannot be bound)
             generators = lambda: gen.rollout_shell(K, restart, out=refs_out)  # noqa: E731
         else:
             generators = gen.bind_rollout_shell(restart, refs_out, stream=stream)
@@ -902,6 +923,46 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         generators, carry from replay to replay.  A ReplayReferenceGenerator is refused: its row index lives on the host."""
         return self._bind("bind_rollout_complete_episodic", True, actions, (state_out, refs_out, reward_out, terminated_out, truncated_out), stream,
                           episode_statistics, complete=True, episodic=True)
+
+    # ------------------------------------------------------------------ complete policy rollouts: actor, references and reward in the loop
+    def _policy_generator(self, what):
+        """The generator of a complete policy rollout is one the kernel steps in the lane: the all-Wiener handle of a
+        BatchedWienerProcessReferenceGenerator (what `reference_generator='default'` builds) or a ProfileReferenceGenerator's."""
+        gen = self.reference_generator
+        if isinstance(gen, (BatchedWienerProcessReferenceGenerator, ProfileReferences)):
+            return
+        kind = type(gen).__name__
+        if isinstance(gen, BatchedMultipleReferenceGenerator):
+            kind += " (switched)" if getattr(gen, "_switched", False) else f" of {', '.join(type(h).__name__ for h in gen.sub_generators)}"
+        raise NotImplementedError(f"{what} steps the reference generators inside the launch, and serves two kinds: a BatchedWienerProcessReferenceGenerator "
+                                  f"(reference_generator='default') and a ProfileReferenceGenerator; this env's generator is a {kind}")
+
+    def bind_rollout_policy_complete_episodic(self, policy, K, state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out, obs0=None, noise=None,
+                                              stream=None, episode_statistics=None):
+        """-> zero-argument launch() of `rollout_policy_complete_episodic` on fixed tensors (every output must be given); `launch()` returns
+        `(state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out[, stats])`.  One stream, nothing on the host: capturable
+        with `torch.cuda.graph` (make one launch outside the capture first: it loads the kernel unit and builds the one-step map);
+        `policy.set_weights` between replays changes the weights the next replay reads."""
+        return self._bind_policy("bind_rollout_policy_complete_episodic", True, policy, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
+                                 obs0, None, noise, stream, episode_statistics, complete=True)
+
+    def rollout_policy_complete_episodic(self, policy, K, obs0=None, noise=None, state_out=None, refs_out=None, reward_out=None, actions_out=None,
+                                         terminated_out=None, truncated_out=None, episode_statistics=None):
+        """K calls of `step()` with the actor `policy` (an `MLPPolicy`) in between, fused: the env's own reference generators are stepped
+        inside the launch that steps the env and computes the action (csrc/gemx_policy_complete.hip), the reward pass follows.
+        -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], actions [K, N, A] or [K, N] uint8, terminated [K, N], truncated [K, N][, stats])
+        -- what goes into `ga.advantages`.  Step k's actor input is `[obs_prev[columns], refs_prev]`, so `policy.n_in == len(columns) +
+        n_ref`: obs_prev as `rollout_policy_episodic` has it (`obs0`, the previous row, the reset observation behind a step that ended);
+        refs_prev is the reference row shown in front of step k -- the env's currently shown references at k = 0, `refs[k - 1]` afterwards,
+        the second half of the observation `step()` hands out.  Row k of `refs` is the shell's: the generators of an env that ended in step
+        k (terminated or truncated) restart, then every generator advances.  `reward[k]` rewards row k against the references shown before
+        step k.  Bit for bit `rollout_complete_episodic(actions)` of a twin env; afterwards the env stands where that leaves it (references
+        shown: row K-1; generator state advanced; `env.truncated`: row K-1; no reset pending), so `step()` and every other rollout
+        continue the same episodes and the same random streams.  `noise`, `obs0`, episode_statistics: as `rollout_policy_episodic` takes
+        them.  Served generators: BatchedWienerProcessReferenceGenerator (`reference_generator='default'`) and ProfileReferenceGenerator;
+        any other: NotImplementedError.  An env without a time limit: ValueError."""
+        return self._bind_policy("rollout_policy_complete_episodic", False, policy, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
+                                 obs0, None, noise, None, episode_statistics, complete=True)()
 
     def close(self):
         self.reference_generator.close()

@@ -841,6 +841,23 @@ int gemx_policy_destroy(gemx_policy *p);
 int gemx_rollout_policy(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *stream);
 int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int64_t n, void *stream);
 
+/* POLICY ROLLOUT OF THE COMPLETE ENV: the policy rollout with the env's own reference generators stepped INSIDE the launch (one new entry
+ * point, ABI number unchanged).  The call is a gemx_policy_call read differently in two fields: refs_dev is [N][n_ref] R, the references
+ * shown in front of step 0 (not [K][N][n_ref]), and n_ref is the generator's column count (>= 1).  Step k's actor input is
+ * [obs_prev[columns], refs_prev]: refs_prev is refs_dev's row at k = 0 and refs_out_dev[k - 1] afterwards.  Behind the row store of step k
+ * the lane restarts the generators of an env whose episode ended (terminated or truncated), advances them and writes
+ * refs_out_dev[k] -- the row gemx_refgen_rollout_shell / gemx_refprofile_rollout_shell produce on the ENDED rows, bit for bit, and the
+ * generator handle is left in the state they leave it in.  Exactly one generator handle is given, the other NULL:
+ *   refgen      an all-Wiener handle of gemx_refgen_create (its standard normals are drawn by a launch in front, into refs_out_dev)
+ *   refprofile  a gemx_refprofile handle: shared or per-env table, both interpolations, end rules and start rules
+ *   refs_out_dev [K][N][n_ref] R
+ * The kernels live in libgemx_pc<S>_<C>.so beside the library (loaded by the first call).  Asynchronous on `stream`, allocates nothing,
+ * can be captured.  GEMX_ERR_ARG, naming the complete policy rollout, before anything is launched: what gemx_rollout_policy refuses;
+ * both handles or neither; a gemx_refgen of gemx_refgen_create_kinds or gemx_refgen_create_switched (kinds, mixed, switched); a generator
+ * handle of another n_envs, dtype, device, env_base or column count; a NULL or misaligned refs_out_dev. */
+int gemx_rollout_policy_complete(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *refs_out_dev, gemx_refgen *refgen,
+                                 gemx_refprofile *refprofile, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,

@@ -1,6 +1,8 @@
 """Registers, LDS and scratch of every policy_rollout_kernel instantiation, from the compiler's own remarks: compiles the 19 policy units
 (csrc/gemx_policy.hip) with build.py's flags plus -Rpass-analysis=kernel-resource-usage into a temporary directory and prints the
-markdown table of profiles/policy_rollout.md.  Exit status 1 if any instantiation has scratch."""
+markdown table of profiles/policy_rollout.md.  Exit status 1 if any instantiation has scratch.
+--complete: the same for every policy_complete_rollout_kernel instantiation of the 19 complete policy units (csrc/gemx_policy_complete.hip;
+one more column, the generator kind: 0 all-Wiener, 1 profile) -- the table of profiles/policy_complete_rollout.md."""
 import concurrent.futures as cf
 import os
 import re
@@ -11,14 +13,16 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gym_electric_motor_amd import build  # noqa: E402
 
-NAME = re.compile(r"policy_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E")
+COMPLETE = "--complete" in sys.argv[1:]
+SOURCE = "gemx_policy_complete.hip" if COMPLETE else "gemx_policy.hip"
+NAME = re.compile(r"policy_complete_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E" if COMPLETE else r"policy_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E")
 FIELD = re.compile(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 
 
 def unit(sc, tmp):
     s, c = sc
     cmd = [build.hipcc_path()] + build.FLAGS + ["-I" + build.CSRC, "-I" + os.path.dirname(build.HEADER), f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}",
-           "-fvisibility=hidden", "-shared", os.path.join(build.CSRC, "gemx_policy.hip"), "-o", os.path.join(tmp, f"pl{s}_{c}.so"), "-Rpass-analysis=kernel-resource-usage"]
+           "-fvisibility=hidden", "-shared", os.path.join(build.CSRC, SOURCE), "-o", os.path.join(tmp, f"pl{s}_{c}.so"), "-Rpass-analysis=kernel-resource-usage"]
     text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     rows, cur = [], None
     for line in text.splitlines():
@@ -37,10 +41,12 @@ def unit(sc, tmp):
 def main():
     with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
         rows = [r for unit_rows in ex.map(lambda sc: unit(sc, tmp), build.UNITS) for r in unit_rows]
-    print("| sys/conv | load | solver | table | VGPRs | AGPRs | SGPR spills | scratch B/lane | static LDS B | waves/SIMD |\n|---|---|---|---|---|---|---|---|---|---|")
+    gen = " generator |" if COMPLETE else ""
+    print(f"| sys/conv | load | solver | table |{gen} VGPRs | AGPRs | SGPR spills | scratch B/lane | static LDS B | waves/SIMD |\n|---|---|---|---|---|---|---|---|---|---|{'---|' if COMPLETE else ''}")
     for r in sorted(rows, key=lambda r: r["key"]):
-        s, c, ld, sv, tab = r["key"]
-        print(f"| {s}/{c} | {ld} | {sv} | {tab} | {r['VGPRs']} | {r['AGPRs']} | {r.get('SGPRs Spill', 0)} | {r['ScratchSize']} | {r['LDS Size']} | {r['Occupancy']} |")
+        s, c, ld, sv, tab = r["key"][:5]
+        gen = f" {r['key'][5]} |" if COMPLETE else ""
+        print(f"| {s}/{c} | {ld} | {sv} | {tab} |{gen} {r['VGPRs']} | {r['AGPRs']} | {r.get('SGPRs Spill', 0)} | {r['ScratchSize']} | {r['LDS Size']} | {r['Occupancy']} |")
     print(f"\n{len(rows)} instantiations; max VGPRs {max(r['VGPRs'] for r in rows)}, max AGPRs {max(r['AGPRs'] for r in rows)}, "
           f"max scratch {max(r['ScratchSize'] for r in rows)} bytes/lane")
     return 1 if any(r["ScratchSize"] for r in rows) else 0
