@@ -1,6 +1,8 @@
 """A tanh MLP current controller acting inside the fused launch: 256 control steps of 4096 PMSM envs, one physics launch.
 --complete: the same on the complete env -- its own reference generators are stepped inside that launch and the reward pass follows, so
-the results are what a learner collects: state, references, reward, actions, terminated, truncated -> ga.advantages."""
+the results are what a learner collects: state, references, reward, actions, terminated, truncated -> ga.advantages.
+--ppo-data: everything a PPO update reads, from ONE captured graph: the complete policy rollout -> a critic's value and last_value
+(`bind_evaluate_rollout`, last=True) -> its final_value (mode="next") -> `ga.bind_advantages` -> the actor's log-probs and entropy."""
 import sys
 
 import numpy as np
@@ -9,7 +11,8 @@ import torch
 import gym_electric_motor_amd as ga
 
 N, K, M = 4096, 256, 100
-complete = "--complete" in sys.argv[1:]
+ppo = "--ppo-data" in sys.argv[1:]
+complete = ppo or "--complete" in sys.argv[1:]
 env = ga.make("Finite-CC-PMSM-v0", n_envs=N, device=0, max_episode_steps=M, **(dict(reference_generator="default") if complete else {}))
 env.reset()
 n_state, n_actions = len(env.physical_system.state_names), int(env.physical_system.action_space.n)
@@ -22,7 +25,46 @@ def layer(n_out, n_in):
 
 policy = ga.MLPPolicy([layer(64, n_state + 2), layer(64, 64), layer(n_actions, 64)], activation="tanh")  # (the state row and i_sd*, i_sq*)
 gumbel = -torch.log(-torch.log(torch.rand((K, N, n_actions), device="cuda:0")))  # categorical sampling
-if complete:
+if ppo:
+    dev, n_ref = "cuda:0", len(env.reference_names)
+    critic = ga.MLPPolicy([layer(64, n_state + n_ref), layer(64, 64), layer(1, 64)], activation="tanh")
+    f32 = lambda *shape: torch.empty(shape, device=dev)  # noqa: E731
+    u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)  # noqa: E731
+    state, refs, reward, actions = f32(K, N, n_state), f32(K, N, n_ref), f32(K, N), u8(K, N)
+    terminated, truncated, ended = u8(K, N), u8(K, N), u8(K, N)
+    value, last_value, final_value, advantage, returns, log_prob, entropy = f32(K, N), f32(N), f32(K, N), f32(K, N), f32(K, N), f32(K, N), f32(K, N)
+    obs0, shown0 = env.physical_system._obs.clone(), f32(N, n_ref)
+    reset_obs = torch.as_tensor(env.physical_system.reset_observation, dtype=torch.float32).to(dev)
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side):
+        seen = dict(obs0=obs0, ended=ended, reset_obs=reset_obs, refs=refs, shown0=shown0, n_ref=n_ref, stream=side)
+        launches = (
+            env.bind_rollout_policy_complete_episodic(policy, K, state, refs, reward, actions, terminated, truncated, obs0=obs0, noise=gumbel, stream=side),
+            lambda: torch.bitwise_or(terminated, truncated, out=ended),
+            critic.bind_evaluate_rollout(state, head="value", last=True, value_out=value, value_last=last_value, **seen),
+            critic.bind_evaluate_rollout(state, head="value", mode="next", refs=refs, n_ref=n_ref, value_out=final_value, stream=side),
+            ga.bind_advantages(reward, value, terminated, gamma=0.99, lam=0.95, last_value=last_value, ended=ended, final_value=final_value,
+                               advantage_out=advantage, return_out=returns, stream=side),
+            policy.bind_evaluate_rollout(state, head="categorical", actions=actions, system=env.physical_system, log_prob_out=log_prob, entropy_out=entropy, **seen))
+
+        def collect():
+            shown0.copy_(env._refs)  # (the references shown in front of the rollout: the rollout moves the env's own row on)
+            for launch in launches:
+                launch()
+
+        collect()  # (outside the capture: loads the units and builds the handle's one-step map)
+        side.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            collect()
+    for it in range(3):  # (a learner would update `policy` and `critic` here: set_weights, then the next replay reads the new weights)
+        obs0.copy_(state[-1])  # (where row K-1 ended the reset observation would be the exact input; the example keeps the last row)
+        graph.replay()
+        torch.cuda.synchronize()
+        env.physical_system.check_errors()
+        print(it, "mean reward", float(reward.mean()), "mean value", float(value.mean()), "mean advantage", float(advantage.mean()), "mean log-prob", float(log_prob.mean()),
+              "mean entropy", float(entropy.mean()), int(truncated.sum()), "truncations")
+elif complete:
     state, refs, reward, actions, terminated, truncated = env.rollout_policy_complete_episodic(policy, K, noise=gumbel)
     torch.cuda.synchronize()
     print(state.shape, refs.shape, actions.shape, "mean reward", float(reward.mean()), int(truncated.sum()), "truncations", env.physical_system.last_launch())

@@ -231,6 +231,23 @@ class GemxPolicyCall(C.Structure):
                 ("truncated_out_dev", C.c_void_p), ("ended_out_dev", C.c_void_p)]
 
 
+EVAL_SEEN, EVAL_NEXT = 0, 1  # GEMX_EVAL_SEEN / GEMX_EVAL_NEXT
+EVAL_HEAD_NONE, EVAL_HEAD_VALUE, EVAL_HEAD_CATEGORICAL, EVAL_HEAD_GAUSSIAN = range(4)  # GEMX_EVAL_HEAD_*
+EVAL_LAST, EVAL_SQUASH_CORRECTION = 1, 2  # gemx_policy_eval_call.flags
+
+
+class GemxPolicyEvalCall(C.Structure):
+    """Mirror of `gemx_policy_eval_call` (include/gemx.h)."""
+
+    _fields_ = [("struct_size", C.c_int32), ("mode", C.c_int32), ("head", C.c_int32), ("flags", C.c_int32), ("out_dtype", C.c_int32), ("n_state", C.c_int32),
+                ("n_cols", C.c_int32), ("n_ref", C.c_int32), ("columns", C.c_int32 * POLICY_MAX_INPUT), ("reset_per_env", C.c_int32), ("reserved", C.c_int32),
+                ("obs0_dev", C.c_void_p), ("rows_dev", C.c_void_p), ("reset_obs_dev", C.c_void_p), ("ended_dev", C.c_void_p),
+                ("refs_dev", C.c_void_p), ("refs0_dev", C.c_void_p), ("last_refs_dev", C.c_void_p), ("actions_dev", C.c_void_p),
+                ("pre_squash_dev", C.c_void_p), ("log_std_dev", C.c_void_p), ("out_dev", C.c_void_p), ("out_last_dev", C.c_void_p),
+                ("value_out_dev", C.c_void_p), ("value_last_dev", C.c_void_p), ("log_prob_out_dev", C.c_void_p), ("entropy_out_dev", C.c_void_p),
+                ("error_handle", C.c_void_p)]
+
+
 def refprofile_state_bytes(n_envs):
     """`gemx_refprofile_state_bytes` restated: the header, then k, s, e as int32 [3][N]."""
     return REFPROFILE_BLOB_HEADER_BYTES + 12 * int(n_envs)
@@ -257,6 +274,7 @@ EXPORTS = (
     "gemx_rollout_episodic",
     "gemx_policy_create", "gemx_policy_set_weights", "gemx_policy_destroy", "gemx_rollout_policy", "gemx_policy_tanh_probe",
     "gemx_rollout_policy_complete",
+    "gemx_policy_eval_rows",
 )
 
 
@@ -365,6 +383,7 @@ def load():
     L.gemx_rollout_policy.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp]
     L.gemx_policy_tanh_probe.argtypes = [vp, vp, vp, i64, vp]
     L.gemx_rollout_policy_complete.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp, vp, vp, vp]
+    L.gemx_policy_eval_rows.argtypes = [vp, C.POINTER(GemxPolicyEvalCall), i64, i32, C.c_int, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]
     L.gemx_get_switch_state.argtypes = [vp, vp, vp]

@@ -6,7 +6,7 @@ Sources (gym_electric_motor_amd/csrc):
                                         libgemx_u<S>_<C>_<F>.so, which gemx_create loads with dlopen (round 6: a handle maps the C ABI and
                                         the one unit it runs, not all 38)
     gemx_capi.hip                       C ABI (include/gemx.h), validation, small kernels, unit loader  } libgemx.so
-    gemx_support.hpp                    row tile in LDS and entry-point checks of the eight support units below (SUPPORT) }
+    gemx_support.hpp                    row tile in LDS and entry-point checks of the nine support units below (SUPPORT) }
     gemx_refgen.hip                     device-side reference generators: Wiener, the other kinds, switched (gemx_refgen_*) }
     gemx_obsproc.hip                    device-side observation stage (gemx_obsproc_*)                  }
     gemx_fluxobs.hip                    device-side FluxObserver and flux-oriented dq actions (gemx_fluxobs_*) }
@@ -15,6 +15,7 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_episode.hip                    device-side episode time limit and episode statistics (gemx_episode_*) }
     gemx_refprofile.hip                 device-side profile references: drive cycles per env (gemx_refprofile_*) }
     gemx_returns.hip                    discounted returns and GAE(lambda) over stored rollout rows (gemx_returns_rows) }
+    gemx_policy_eval.hip                an MLPPolicy evaluated on every row of a stored policy rollout, with value / log-prob heads (gemx_policy_eval_rows) }
     gemx_envparams.hpp, gemx_envparams.hip   per-env motor / load / supply parameters: the two per-env kernels, compiled once per (system,
                                         converter unit), fp32, into libgemx_ep<S>_<C>.so, which gemx_set_env_params loads with dlopen
     gemx_envparams_dev.hpp              the device helpers the per-env units and the episodic units share (table column, row store, control step)
@@ -31,7 +32,7 @@ Sources (gym_electric_motor_amd/csrc):
                                         stepped in the lane, once per generator kind, compiled once per (system, converter unit), fp32, into
                                         libgemx_pc<S>_<C>.so, which the first gemx_rollout_policy_complete of such a handle loads with dlopen
 The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units, the 19 complete policy
-units and the nine objects of libgemx.so are compiled in parallel.
+units and the ten objects of libgemx.so are compiled in parallel.
 """
 import concurrent.futures as cf
 import glob
@@ -49,7 +50,8 @@ _LANE_HEADERS = ["gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp"]  # gemx_sup
 SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc", "gemx_obsproc.hip", ["gemx_support.hpp"], 0.1),
            ("fluxobs", "gemx_fluxobs.hip", ["gemx_support.hpp"], 0.1), ("rewardpass", "gemx_rewardpass.hip", ["gemx_support.hpp"], 0.1),
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
-           ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05)]
+           ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05),
+           ("policy_eval", "gemx_policy_eval.hip", ["gemx_support.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp"], 0.1)]
 SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
                                            "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip",
                                            "gemx_policy_dev.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]

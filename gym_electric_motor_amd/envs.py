@@ -661,6 +661,42 @@ class BatchedElectricMotorEnv:
         return self._bind_policy("rollout_policy_episodic", False, policy, K, (obs_out, actions_out, terminated_out, truncated_out), obs0, references, noise,
                                  None, episode_statistics)()
 
+    def _evaluate_policy(self, what, policy, outputs, n_lead, head, mode, obs0, kw):
+        """The common part of `evaluate_policy_rollout` / `evaluate_policy_complete_rollout`: the policy and the tuple a rollout returned
+        checked, `ended`, `reset_obs` and the stored actions filled in -> the keyword arguments of `MLPPolicy.evaluate_rollout`."""
+        from .policy import MLPPolicy
+
+        torch = bps._torch()
+        ps = self.physical_system
+        if not isinstance(policy, MLPPolicy):
+            raise ValueError(f"{what}: policy must be an MLPPolicy")
+        if not isinstance(outputs, (tuple, list)) or len(outputs) not in (n_lead + 3, n_lead + 4) or not all(torch.is_tensor(t) for t in outputs[:n_lead + 3]):
+            raise ValueError(f"{what}: rollout_outputs must be the tuple the policy rollout returned ({n_lead + 3} tensors, then the statistics dict if it gave one)")
+        actions, terminated, truncated = outputs[n_lead:n_lead + 3]
+        traj = outputs[0]
+        if head == "categorical":
+            kw["actions"] = actions
+        if mode == "seen":
+            stats = outputs[n_lead + 3] if len(outputs) == n_lead + 4 else None
+            kw["ended"] = stats["ended"] if stats else torch.bitwise_or(terminated, truncated)
+            kw["reset_obs"] = torch.as_tensor(ps.reset_observation, dtype=torch.float32).to(traj.device)
+            kw["obs0"] = obs0
+        elif obs0 is not None:
+            raise ValueError(f"{what}: obs0 belongs to mode='seen'")
+        return dict(kw, head=head, mode=mode, system=ps)
+
+    def evaluate_policy_rollout(self, policy, rollout_outputs, head="none", mode="seen", obs0=None, **kw):
+        """`policy.evaluate_rollout` on what `rollout_policy_episodic` returned, `(traj, actions, terminated, truncated[, stats])`: the
+        env fills in `ended` (the statistics' or terminated | truncated), the reset observation, the stored actions of head="categorical"
+        and itself as the owner of the error word.  `obs0 [N, S]`: the observation in front of step 0 (mode="seen"; the rollout's own
+        `obs0`).  `references` / `last_references` / `references_next`, `pre_squash`, `log_std`, `last`, `dtype`, outputs: as
+        `MLPPolicy.evaluate_rollout` takes them.  An eager convenience: every call allocates `ended` (without statistics) and copies the reset
+        observation to the device, so it cannot be captured -- a graph goes through `policy.bind_evaluate_rollout` with tensors the caller
+        holds (`reset_obs` a device row made once, `ended` written by `torch.bitwise_or(terminated, truncated, out=ended)`)."""
+        what = "evaluate_policy_rollout"
+        return policy.evaluate_rollout(rollout_outputs[0] if isinstance(rollout_outputs, (tuple, list)) and rollout_outputs else None,
+                                       **self._evaluate_policy(what, policy, rollout_outputs, 1, head, mode, obs0, kw))
+
     def rollout_episodic(self, actions, obs_out=None, terminated_out=None, truncated_out=None, episode_statistics=None):
         """K fused control steps of an env built with `max_episode_steps=M`, the time limit INSIDE the launch (csrc/gemx_episodic.hip):
         -> (traj [K, N, S_out], terminated [K, N], truncated [K, N][, stats]) uint8 masks -- what K calls of `step(actions[k])` return,
@@ -963,6 +999,19 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         any other: NotImplementedError.  An env without a time limit: ValueError."""
         return self._bind_policy("rollout_policy_complete_episodic", False, policy, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
                                  obs0, None, noise, None, episode_statistics, complete=True)()
+
+    def evaluate_policy_complete_rollout(self, policy, rollout_outputs, head="none", mode="seen", obs0=None, shown0=None, **kw):
+        """`policy.evaluate_rollout` on what `rollout_policy_complete_episodic` returned, `(state, refs, reward, actions, terminated,
+        truncated[, stats])`, in the complete form: `refs` from the tuple, `n_ref` from the env, `ended`, the reset observation and the
+        stored actions as `evaluate_policy_rollout` fills them.  mode="seen" needs `obs0 [N, S]` and `shown0 [N, n_ref]`, the state row
+        and the reference row of the observation in front of the rollout (clones: the rollout moves the env's own buffers on)."""
+        what = "evaluate_policy_complete_rollout"
+        kw = self._evaluate_policy(what, policy, rollout_outputs, 3, head, mode, obs0, kw)
+        if mode == "seen":
+            kw["shown0"] = shown0
+        elif shown0 is not None:
+            raise ValueError(f"{what}: shown0 belongs to mode='seen'")
+        return policy.evaluate_rollout(rollout_outputs[0], refs=rollout_outputs[1], n_ref=len(self.reference_names), **kw)
 
     def close(self):
         self.reference_generator.close()

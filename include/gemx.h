@@ -858,6 +858,67 @@ int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int
 int gemx_rollout_policy_complete(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *refs_out_dev, gemx_refgen *refgen,
                                  gemx_refprofile *refprofile, void *stream);
 
+/* POLICY EVALUATION OVER STORED ROWS: an MLP of gemx_policy_create on every row of a stored policy rollout, with the rollout kernels' own
+ * arithmetic, as ONE launch (new struct and entry point only, ABI number unchanged).  No physics, no env handle: the pass reads the policy's
+ * device blob (no second copy of the weights) and the tensors a rollout handed out.  Row (k, env), k < K, one lane each:
+ *     x[k] = [o[k][columns[0..n_cols)], r[k]];   out[k] = W_L act(... act(W_1 x[k] + b_1)) + b_L
+ * every dot product the fp32 fma chain gemx_rollout_policy documents (from the bias, the selected columns in ascending column order, then
+ * the references), so for rows and a policy that came from a policy rollout out[k] is, bit for bit, the value that rollout had in front of
+ * `+ noise[k]`.
+ *   GEMX_EVAL_SEEN  o[0] = obs0_dev's row;  o[k] = ended_dev[k-1] ? the reset observation : rows_dev[k-1]
+ *                   r[k] = refs_dev[k] (refs0_dev NULL: the physics-only form), or  r[0] = refs0_dev's row, r[k] = refs_dev[k-1] (refs0_dev
+ *                   given: the complete form, gemx_rollout_policy_complete's refs_dev [N][n_ref] and refs_out_dev)
+ *                   GEMX_EVAL_LAST: one more row, k = K: o[K] as above, r[K] = last_refs_dev's row, or refs_dev[K-1] in the complete form;
+ *                   it goes to the *_last_dev outputs -- a critic's row K is the last_value of gemx_returns_rows
+ *   GEMX_EVAL_NEXT  o[k] = rows_dev[k] without reset substitution, r[k] = refs_dev[k]: a critic's rows are the final_value of
+ *                   gemx_returns_rows.  obs0_dev, ended_dev, reset_obs_dev, refs0_dev, last_refs_dev must be NULL, GEMX_EVAL_LAST clear
+ * Heads: each reads the fp32 out, computes in double with every operation rounded on its own (no FMA across them, as gemx_returns_rows)
+ * and rounds the result once to out_dtype (GEMX_F32 | GEMX_F64):
+ *   GEMX_EVAL_HEAD_NONE         out_dev [K][N][n_out] float (n_out = the last layer's width); out_last_dev [N][n_out] float
+ *   GEMX_EVAL_HEAD_VALUE        n_out == 1: value_out_dev [K][N] = out[0]; value_last_dev [N]
+ *   GEMX_EVAL_HEAD_CATEGORICAL  a = actions_dev[k] ([K][N] uint8);  m = max_i out_i;  s = sum_i exp(out_i - m) (ascending i, from 0);
+ *                               lse = m + log(s);  l_i = out_i - lse;  log_prob = l_a;  entropy = -(sum_i exp(l_i) * l_i) (ascending i, from 0).
+ *                               a >= n_out: log_prob = NaN, and GEMX_ERRFLAG_ACTION is set in the error word of error_handle (a gemx_handle
+ *                               on the policy's device; may be NULL: not reported), where gemx_error_flags finds it
+ *   GEMX_EVAL_HEAD_GAUSSIAN     u = pre_squash_dev[k] ([K][N][n_out] float: out_old + noise, what was squashed into the stored action),
+ *                               ls = log_std_dev ([n_out] float, DEVICE memory: a captured launch reads new values at its next replay):
+ *                               per j ascending, from 0:  sg = exp(ls_j);  d = u_j - out_j;  q = (d * d) / (2 * (sg * sg));
+ *                                   log_prob += ((-q) - ls_j) - 0.5 log(2 pi);   entropy += ls_j + 0.5 log(2 pi e)
+ *                               GEMX_EVAL_SQUASH_CORRECTION: c += 2 * ((log 2 - u_j) - softplus(-2 u_j)), log_prob = log_prob - c (the tanh
+ *                               change of variables); softplus(t) = max(t, 0) + log1p(exp(-|t|))
+ *                               log_prob_out_dev, entropy_out_dev [K][N] of out_dtype; either may be NULL, not both
+ * rows_dev [K][N][n_state] float;  reset_obs_dev [n_state] float, or [N][n_state] with reset_per_env = 1;  obs0_dev [N][n_state] float.
+ * One kernel launch on `stream`: no allocation, no host state, no synchronisation -- the call can be captured in a HIP graph.
+ * GEMX_ERR_ARG, naming the policy evaluation, before anything is launched: a NULL policy or call, struct_size, an unknown mode, head, flag
+ * or out_dtype, K < 1, n_envs < 1, n_state outside [1, GEMX_MAX_OUT], n_ref outside [0, GEMX_MAX_REF], n_cols + n_ref != the policy's input
+ * width, a column outside the row or selected twice, a tensor the mode / head needs that is NULL or one it does not read that is given,
+ * the VALUE head with n_out != 1, GEMX_EVAL_LAST with the CATEGORICAL or GAUSSIAN head, a misaligned tensor, a policy or an error_handle on
+ * another device. */
+enum { GEMX_EVAL_SEEN = 0, GEMX_EVAL_NEXT = 1 };
+enum { GEMX_EVAL_HEAD_NONE = 0, GEMX_EVAL_HEAD_VALUE = 1, GEMX_EVAL_HEAD_CATEGORICAL = 2, GEMX_EVAL_HEAD_GAUSSIAN = 3 };
+enum { GEMX_EVAL_LAST = 1, GEMX_EVAL_SQUASH_CORRECTION = 2 };
+typedef struct gemx_policy_eval_call {
+    int32_t struct_size; /* = sizeof(gemx_policy_eval_call) */
+    int32_t mode;        /* GEMX_EVAL_SEEN | GEMX_EVAL_NEXT */
+    int32_t head;        /* GEMX_EVAL_HEAD_* */
+    int32_t flags;       /* GEMX_EVAL_LAST | GEMX_EVAL_SQUASH_CORRECTION */
+    int32_t out_dtype;   /* GEMX_F32 | GEMX_F64: the head outputs (out_dev is float whatever it says) */
+    int32_t n_state;     /* columns of a stored row */
+    int32_t n_cols, n_ref;
+    int32_t columns[GEMX_POLICY_MAX_INPUT];
+    int32_t reset_per_env; /* 0: reset_obs_dev [n_state]; 1: [N][n_state] */
+    int32_t reserved;      /* 0 */
+    const float *obs0_dev, *rows_dev, *reset_obs_dev;
+    const uint8_t *ended_dev;
+    const float *refs_dev, *refs0_dev, *last_refs_dev;
+    const uint8_t *actions_dev;
+    const float *pre_squash_dev, *log_std_dev;
+    float *out_dev, *out_last_dev;
+    void *value_out_dev, *value_last_dev, *log_prob_out_dev, *entropy_out_dev;
+    gemx_handle *error_handle;
+} gemx_policy_eval_call;
+int gemx_policy_eval_rows(const gemx_policy *p, const gemx_policy_eval_call *call, int64_t n_envs, int32_t K, int device, void *stream);
+
 /* Checkpoint / parity access to the ODE state, SoA [S_ode, N] of R in physical units (angle in rad; the fp32 build keeps the
  * angle as a 32-bit fraction of a turn internally, so a get/set round trip rounds it to fp32 radians, ~1e-7 rad), plus the
  * per-env packed converter switching state, 2 bits per half-bridge: [N] uint8, or [2][N] uint8 (row 0 = bits 0..7,
