@@ -2,6 +2,7 @@
 
 Sources (gym_electric_motor_amd/csrc):
     gemx_common.hpp, gemx_kernels.hpp   device templates
+    gemx_unit_host.hpp                  the host code every dlopen'ed unit repeats: error sink, unit_init, (load, solver) dispatch, one-step map, KArgs
     gemx_inst.hip                       ONE kernel unit, compiled once per (system, converter unit, dtype) into its OWN shared object
                                         libgemx_u<S>_<C>_<F>.so, which gemx_create loads with dlopen (round 6: a handle maps the C ABI and
                                         the one unit it runs, not all 38)
@@ -22,13 +23,14 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_episodic.hip                   K-step rollout with the episode time limit inside the launch: one kernel, with and without a parameter
                                         table, compiled once per (system, converter unit), fp32, into libgemx_tl<S>_<C>.so, which the first
                                         gemx_rollout_episodic of such a handle loads with dlopen
-    gemx_policy.hpp, gemx_policy.hip    the policy rollout: the episodic kernel with a device MLP actor in front of every step, compiled once per
-                                        (system, converter unit), fp32, into libgemx_pl<S>_<C>.so, which the first gemx_rollout_policy of such a
-                                        handle loads with dlopen
-    gemx_policy_dev.hpp                 the actor's device helpers, shared by the two kinds of policy unit
+    gemx_policy_kernel.hpp              THE policy rollout kernel and its launcher: the episodic kernel with a device MLP actor in front of every
+                                        step, with or without a reference generator in the lane; included by the two kinds of policy unit
+    gemx_policy.hpp, gemx_policy.hip    the policy rollout: that kernel without a generator, compiled once per (system, converter unit), fp32,
+                                        into libgemx_pl<S>_<C>.so, which the first gemx_rollout_policy of such a handle loads with dlopen
+    gemx_policy_dev.hpp                 the actor's device helpers, shared by the policy kernel and gemx_policy_eval.hip
     gemx_refgen_lane.hpp, gemx_refprofile_lane.hpp   the per-lane functions of the all-Wiener and the profile generators, shared by their
                                         units of libgemx.so and the complete policy units
-    gemx_policy_complete.hpp, gemx_policy_complete.hip   the policy rollout of the complete env: the policy kernel with the reference generators
+    gemx_policy_complete.hpp, gemx_policy_complete.hip   the policy rollout of the complete env: that kernel with the reference generators
                                         stepped in the lane, once per generator kind, compiled once per (system, converter unit), fp32, into
                                         libgemx_pc<S>_<C>.so, which the first gemx_rollout_policy_complete of such a handle loads with dlopen
 The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units, the 19 complete policy
@@ -52,9 +54,9 @@ SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc",
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
            ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05),
            ("policy_eval", "gemx_policy_eval.hip", ["gemx_support.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp"], 0.1)]
-SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
+SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_unit_host.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
                                            "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip",
-                                           "gemx_policy_dev.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]
+                                           "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")
 
@@ -110,11 +112,12 @@ def _digest(sources=None, header=None):
 
 
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
-_DEPS = {"inst": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_capi.hip"],
-         "envparams": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
-         "episodic": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],
-         "policy": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp", "gemx_policy.hip"],
-         "policy_complete": ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy_dev.hpp"] + _PC_HEADERS +
+_UNIT = ["gemx_common.hpp", "gemx_kernels.hpp", "gemx_unit_host.hpp"]  # every dlopen'ed unit
+_DEPS = {"inst": _UNIT + ["gemx_inst.hip"], "capi": ["gemx_common.hpp", "gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_capi.hip"],
+         "envparams": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
+         "episodic": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],
+         "policy": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_policy.hip"],
+         "policy_complete": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp"] + _PC_HEADERS +
                             ["gemx_support.hpp", "gemx_refprofile.hip", "gemx_policy_complete.hip"],  # (gemx_refprofile.hip: its head section, the one definition of profile_row)
          **{name: ["gemx_common.hpp"] + headers + _LANE_HEADERS + [src] for name, src, headers, _ in SUPPORT}}
 # compile cost of an fp32 unit by system kind (object size, MB: induction > synchronous > DC); fp64 units take the single-wave kernel only

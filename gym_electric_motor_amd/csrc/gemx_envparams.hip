@@ -11,10 +11,8 @@
 // Always the stage-by-stage solver: the one-step map of the constant-speed loads (lin_usable) is built for one parameter set.
 // Not served (refused by gemx_set_env_params): fp64, the Dormand-Prince solver, converter dead time, DeadTimeProcessor, RC supply, random
 // initial states -- so there is no leg state, no FIFO, no supply state and no draw in here.
-#include <cstdarg>
-#include <cstdio>
-
 #include "gemx_kernels.hpp"
+#include "gemx_unit_host.hpp"
 #include "gemx_envparams.hpp"
 #include "gemx_envparams_dev.hpp"
 
@@ -23,17 +21,6 @@
 #endif
 
 namespace gemx {
-static void (*g_set_error)(const char *) = nullptr;
-int fail(int code, const char *fmt, ...) {  // gemx_common.hpp declares it; in a unit it formats and hands the text to libgemx.so's gemx_last_error()
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (g_set_error != nullptr) g_set_error(buf);
-    return code;
-}
-
 // (ep_load, ep_apply, ep_store_row, ep_control_step: gemx_envparams_dev.hpp, shared with the episodic rollout units)
 
 // ------------------------------------------------------------------------------------------------
@@ -221,27 +208,12 @@ template <int SYS, int CONV, int LOAD, int SOLVER>
 static int launch_ep_t(gemx_handle *h, const float *tab, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
     using R = float;
     KArgs<R> a;
-    memset(&a, 0, sizeof(a));
-    a.P = h->pf;
-    a.P.lin_on = 0;  // (never the one-step map: it is built for one parameter set)
-    a.P.kink_split = ((h->cfg.solver_flags & GEMX_SOLVER_SPLIT_KINKS) && LOAD == GEMX_LOAD_POLY_STATIC) ? 1 : 0;  // the FLAG: ep_apply decides per lane
-    a.P.errw = h->err;
-    a.state = (R *)h->state;
-    a.angle = (Angle<R>::T *)h->angle;
-    a.sw = h->sw;
+    fill_unit_kargs<LOAD>(a, h, true, K, obs, done);
     a.actions = (const unsigned char *)actions;
-    a.obs = (R *)obs;
-    a.done = done;
-    a.err = h->err;
     a.rw = h->cur_reward != nullptr ? (const RewardDev<R> *)h->rw_dev : nullptr;
     a.rh = h->rh_f;
     a.refs = (const R *)h->cur_refs;
     a.reward = (R *)h->cur_reward;
-    a.N = h->n;
-    a.K = K;
-    a.obs_every = 1;
-    a.S = 1;
-    a.D = 1;
     const int64_t blocks = (h->n + BLOCK - 1) / BLOCK;
     const bool step = K == 1 && h->cur_reward == nullptr;
     if (step) hipLaunchKernelGGL((envparams_step_kernel<SYS, CONV, LOAD, SOLVER, R>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a, tab);
@@ -253,24 +225,15 @@ static int launch_ep_t(gemx_handle *h, const float *tab, const void *actions, in
 
 template <int SYS, int CONV>
 static int launch_ep_unit(gemx_handle *h, const void *tab, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
-    const int ld = h->cfg.load_kind, sv = h->cfg.solver_kind;
-#define GEMX_EP_CASE(LD, SV) \
-    if (ld == LD && sv == SV) return launch_ep_t<SYS, CONV, LD, SV>(h, (const float *)tab, actions, K, obs, done, st);
-    GEMX_EP_CASE(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_EULER)
-    GEMX_EP_CASE(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_RK4)
-    GEMX_EP_CASE(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_EULER)
-    GEMX_EP_CASE(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_RK4)
-#undef GEMX_EP_CASE
-    return fail(GEMX_ERR_ARG, "per-env parameters: load/solver combination %d/%d is not built (EulerSolver and RK4Solver only)", ld, sv);
+    return dispatch_load_solver(h, "per-env parameters", [&](auto ls) {
+        return launch_ep_t<SYS, CONV, decltype(ls)::LOAD, decltype(ls)::SOLVER>(h, (const float *)tab, actions, K, obs, done, st);
+    });
 }
 }  // namespace gemx
 
 extern "C" {
-// GEMX_OK if this unit was compiled against the caller's handle layout and ABI
 __attribute__((visibility("default"))) int gemx_ep_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
-    if (handle_bytes != (unsigned long long)sizeof(gemx_handle) || abi != GEMX_ABI_VERSION) return GEMX_ERR_ARG;
-    gemx::g_set_error = set_error;
-    return GEMX_OK;
+    return gemx::unit_init(handle_bytes, abi, set_error);
 }
 __attribute__((visibility("default"))) int gemx_ep_unit_launch(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
     if (h->envp == nullptr || h->envp_fields != gemx::ep_fields(GEMX_INST_SYS)) return gemx::fail(GEMX_ERR_ARG, "internal: per-env parameter unit launched without its table");

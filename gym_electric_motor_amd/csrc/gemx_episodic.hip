@@ -21,10 +21,8 @@
 // so the rows are, bit for bit, what K gemx_step calls with the episode stage and the masked reset between them write (tests).
 // Not served (refused by gemx_rollout_episodic): fp64, the Dormand-Prince solvers, converter dead time, DeadTimeProcessor, RC supply,
 // random initial states -- no leg state, no FIFO, no supply state, no carried step size and no draw in here.
-#include <cstdarg>
-#include <cstdio>
-
 #include "gemx_kernels.hpp"
+#include "gemx_unit_host.hpp"
 #include "gemx_envparams.hpp"
 #include "gemx_envparams_dev.hpp"
 
@@ -33,17 +31,6 @@
 #endif
 
 namespace gemx {
-static void (*g_set_error)(const char *) = nullptr;
-int fail(int code, const char *fmt, ...) {  // gemx_common.hpp declares it; in a unit it formats and hands the text to libgemx.so's gemx_last_error()
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    if (g_set_error != nullptr) g_set_error(buf);
-    return code;
-}
-
 template <int SYS, int CONV, int LOAD, int SOLVER, bool TAB, class R>
 __global__ __launch_bounds__(BLOCK) void episodic_rollout_kernel(const KArgs<R> a, const R *__restrict__ tab, const int32_t *__restrict__ length_in, const int32_t M,
                                                                  uint8_t *__restrict__ truncated, uint8_t *__restrict__ ended) {
@@ -165,44 +152,10 @@ template <int SYS, int CONV, int LOAD, int SOLVER>
 static int launch_tl_t(gemx_handle *h, const TlCall &c, hipStream_t st) {
     using R = float;
     const bool tab = h->envp != nullptr;
-    if (!tab && h->linmap_state == 0) {  // once per handle, as launch_advance_t builds it: the electrical subsystem's one-step map
-        if constexpr (linable<SYS, LOAD, SOLVER, false, R>()) {
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(st, &capturing);
-            if ((h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) || h->cfg.solver_nsteps != 1) {  // (sub-steps: stage by stage; initial states are constant here)
-                h->linmap_state = -1;
-            } else if (capturing == hipStreamCaptureStatusNone) {  // (a first launch that is being captured goes without the map, as a stepped one does)
-                hipLaunchKernelGGL((linmap_kernel<SYS, SOLVER, R>), dim3(1), dim3(64), 0, st, params_of<double>(h), (R *)h->linmap_dev);
-                GEMX_HIP_TRY(hipGetLastError());
-                GEMX_HIP_TRY(hipStreamSynchronize(st));
-                h->linmap_state = 1;
-                h->pf.lin_on = 1;
-                if (c.linmap_built != nullptr) *c.linmap_built = 1;
-            }
-        } else {
-            h->linmap_state = -1;
-        }
-    }
+    if (const int rc = ensure_linmap<SYS, LOAD, SOLVER>(h, st, c.linmap_built)) return rc;
     KArgs<R> a;
-    memset(&a, 0, sizeof(a));
-    a.P = h->pf;
-    if (tab) {  // launch_ep_t's view of the handle
-        a.P.lin_on = 0;  // (never the one-step map: it is built for one parameter set)
-        a.P.kink_split = ((h->cfg.solver_flags & GEMX_SOLVER_SPLIT_KINKS) && LOAD == GEMX_LOAD_POLY_STATIC) ? 1 : 0;  // the FLAG: ep_apply decides per lane
-    }
-    a.P.errw = h->err;
-    a.state = (R *)h->state;
-    a.angle = (Angle<R>::T *)h->angle;
-    a.sw = h->sw;
+    fill_unit_kargs<LOAD>(a, h, tab, c.K, c.obs, c.terminated);  // (tab: launch_ep_t's view of the handle)
     a.actions = (const unsigned char *)c.actions;
-    a.obs = (R *)c.obs;
-    a.done = c.terminated;
-    a.err = h->err;
-    a.N = h->n;
-    a.K = c.K;
-    a.obs_every = 1;
-    a.S = 1;
-    a.D = 1;
     const int64_t blocks = (h->n + BLOCK - 1) / BLOCK;
     if (tab)
         hipLaunchKernelGGL((episodic_rollout_kernel<SYS, CONV, LOAD, SOLVER, true, R>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a, (const R *)h->envp, c.length,
@@ -217,24 +170,13 @@ static int launch_tl_t(gemx_handle *h, const TlCall &c, hipStream_t st) {
 
 template <int SYS, int CONV>
 static int launch_tl_unit(gemx_handle *h, const TlCall &c, hipStream_t st) {
-    const int ld = h->cfg.load_kind, sv = h->cfg.solver_kind;
-#define GEMX_TL_CASE(LD, SV) \
-    if (ld == LD && sv == SV) return launch_tl_t<SYS, CONV, LD, SV>(h, c, st);
-    GEMX_TL_CASE(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_EULER)
-    GEMX_TL_CASE(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_RK4)
-    GEMX_TL_CASE(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_EULER)
-    GEMX_TL_CASE(GEMX_LOAD_POLY_STATIC, GEMX_SOLVER_RK4)
-#undef GEMX_TL_CASE
-    return fail(GEMX_ERR_ARG, "episodic rollout: load/solver combination %d/%d is not built (EulerSolver and RK4Solver only)", ld, sv);
+    return dispatch_load_solver(h, "episodic rollout", [&](auto ls) { return launch_tl_t<SYS, CONV, decltype(ls)::LOAD, decltype(ls)::SOLVER>(h, c, st); });
 }
 }  // namespace gemx
 
 extern "C" {
-// GEMX_OK if this unit was compiled against the caller's handle layout and ABI
 __attribute__((visibility("default"))) int gemx_tl_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
-    if (handle_bytes != (unsigned long long)sizeof(gemx_handle) || abi != GEMX_ABI_VERSION) return GEMX_ERR_ARG;
-    gemx::g_set_error = set_error;
-    return GEMX_OK;
+    return gemx::unit_init(handle_bytes, abi, set_error);
 }
 __attribute__((visibility("default"))) int gemx_tl_unit_launch(gemx_handle *h, const void *actions, int K, const int32_t *length, int32_t max_steps, void *obs,
                                                                uint8_t *terminated, uint8_t *truncated, uint8_t *ended, hipStream_t st, int *linmap_built) {

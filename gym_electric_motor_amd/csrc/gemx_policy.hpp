@@ -1,5 +1,6 @@
 // gemx_policy.hpp -- the device MLP actor of the policy rollout (gemx_rollout_policy): what the C ABI (gemx_capi.hip) and the policy
-// rollout units (gemx_policy.hip) share -- the layout of the weight blob, the kernel's view of a policy and the unit's entry points.
+// rollout units (gemx_policy.hip; the kernel: gemx_policy_kernel.hpp) share -- the layout of the weight blob, the kernel's view of a policy
+// and the unit's entry points.
 //
 // THE BLOB (float words, one hipMalloc per policy, rewritten in place by gemx_policy_set_weights): per layer l, weights then biases.
 //   weights  [JB][n_rows][8]: output block jb = outputs 8 jb .. 8 jb + 7, row i = input i.  Layer 0 has n_rows = the policy's input width
@@ -17,6 +18,9 @@ constexpr int PL_MAX_LAYERS = 3, PL_MAX_WIDTH = 64, PL_MAX_INPUT = 48;
 constexpr int PL_ACT_RELU = 0, PL_ACT_TANH = 1;
 constexpr int PL_SQUASH_TANH = 0, PL_SQUASH_CLIP = 1;
 constexpr int EP_LAUNCH_POLICY = 7;  // gemx_handle::LastLaunch::pipe of policy_rollout_kernel (gemx_envparams.hpp lists the others)
+// policy_rollout_kernel's GEN, where the actor's references come from: the complete env's generators stepped in the lane (an all-Wiener
+// gemx_refgen, a gemx_refprofile; LastLaunch::il of such a launch), or none -- row k of the call's tensor
+constexpr int PC_GEN_WIENER = 0, PC_GEN_PROFILE = 1, PC_GEN_NONE = 2;
 
 constexpr int pl_pad8(int n) { return (n + 7) & ~7; }
 // rows of layer l's weight block, and the blob's size in words, for widths n_in -> width[0] -> ... -> width[L - 1]

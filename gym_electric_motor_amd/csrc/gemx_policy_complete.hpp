@@ -2,7 +2,7 @@
 // generator units of libgemx.so (gemx_refgen.hip, gemx_refprofile.hip) and the complete policy rollout units (gemx_policy_complete.hip)
 // share -- the kernel's by-value view of a generator handle, the functions that resolve it and the unit's entry point.
 //
-// The unit's kernel is policy_rollout_kernel with the reference generators stepped in the lane that steps the env: the actor of step k
+// The unit's kernel is policy_rollout_kernel (gemx_policy_kernel.hpp) with the reference generators stepped in the lane that steps the env: the actor of step k
 // reads the reference row shown in front of step k (`shown` at k = 0, refs_out[k - 1] afterwards), and behind the row store of step k the
 // lane restarts its generators where the episode ended, advances them and writes refs_out[k] -- the shell's order, which
 // gemx_refgen_rollout_shell and gemx_refprofile_rollout_shell replay on the ENDED rows.  The generator state is not kept in registers
@@ -14,8 +14,7 @@
 
 namespace gemx {
 
-constexpr int EP_LAUNCH_POLICY_COMPLETE = 8;  // gemx_handle::LastLaunch::pipe of policy_complete_rollout_kernel; LastLaunch::il: the generator kind
-constexpr int PC_GEN_WIENER = 0, PC_GEN_PROFILE = 1;
+constexpr int EP_LAUNCH_POLICY_COMPLETE = 8;  // gemx_handle::LastLaunch::pipe of policy_rollout_kernel with a generator; LastLaunch::il: the generator kind (PC_GEN_*, gemx_policy.hpp)
 
 // (the kernel's views of the two generator handles, PcWienerDev and PcProfileDev, and the functions that resolve them stand beside the lane
 // functions: gemx_refgen_lane.hpp, gemx_refprofile_lane.hpp)

@@ -1,6 +1,6 @@
-// gemx_policy_dev.hpp -- the device helpers of the MLP actor that the policy rollout units (gemx_policy.hip) and the complete policy
-// rollout units (gemx_policy_complete.hip) share: the activations as register vectors, the 8-output FMA block on wave-uniform LDS reads,
-// the activation functions.  What they are for is described at the head of gemx_policy.hip.
+// gemx_policy_dev.hpp -- the device helpers of the MLP actor that the policy rollout kernel (gemx_policy_kernel.hpp: the policy units and
+// the complete policy units) and the evaluation pass (gemx_policy_eval.hip) share: the activations as register vectors, the 8-output FMA
+// block on wave-uniform LDS reads, the activation functions.  What they are for is described at the head of gemx_policy_kernel.hpp.
 #pragma once
 #include "gemx_policy.hpp"
 

@@ -3,7 +3,7 @@
 // actor's log-probability and entropy -- as ONE launch, with the rollout kernels' own arithmetic.  No physics, no env handle, no state
 // that survives a call; the weights are the policy's device blob as it is (gemx_policy.hpp), no second copy.
 //
-// A lane owns one (k, env) row.  It gathers the actor input the rollout kernels build (gemx_policy.hip, gemx_policy_complete.hip),
+// A lane owns one (k, env) row.  It gathers the actor input the rollout kernel builds (gemx_policy_kernel.hpp, with and without a generator),
 //     SEEN: o = k == 0 ? obs0 : ended[k-1] ? reset observation : rows[k-1];   NEXT: o = rows[k]
 //     x = [o[columns], r]            (r: the reference row the header names for the mode and the form)
 // runs the MLP with gemx_policy_dev.hpp's helpers in the policy rollout kernel's order -- layer 0 per 8-output block over the selected

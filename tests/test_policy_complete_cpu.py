@@ -134,6 +134,8 @@ def test_units_headers_and_abi():
     for kind in ("policy_complete", "refgen", "refprofile", "capi"):  # an edit of a lane header recompiles everything that sees it
         assert {"gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp"} <= set(build._DEPS[kind]), kind
     assert "gemx_policy_dev.hpp" in build._DEPS["policy"] and "gemx_policy_dev.hpp" in build._DEPS["policy_complete"]
+    assert {"gemx_policy_kernel.hpp", "gemx_unit_host.hpp"} <= names  # the one kernel of both kinds of policy unit: an edit recompiles both
+    assert "gemx_policy_kernel.hpp" in build._DEPS["policy"] and "gemx_policy_kernel.hpp" in build._DEPS["policy_complete"]
     header = open(os.path.join(REPO, "include", "gemx.h")).read()
     assert re.search(r"^#define GEMX_ABI_VERSION 9\b", header, re.M) and _lib.ABI_VERSION == 9  # one new entry point only
     m = re.search(r"\bint gemx_rollout_policy_complete\(([^;]*)\);", header)
@@ -152,6 +154,8 @@ def test_units_headers_and_abi():
     unit = src["gemx_policy_complete.hip"]
     for fn in ("reset_generator(G", "new_subepisode(G", "walk_step(G", "profile_restart(P", "profile_row<float>(P"):
         assert fn in unit, fn
-    assert 'asm volatile("" : "+v"(y[j]))' in unit and "ep_control_step" in unit and "lin_usable" in unit
+    kernel = open(os.path.join(CSRC, "gemx_policy_kernel.hpp")).read()  # the unit's kernel: the policy units', with a generator kind
+    assert '#include "gemx_policy_kernel.hpp"' in unit and "pc_references<GEN>(" in kernel
+    assert 'asm volatile("" : "+v"(y[j]))' in kernel and "ep_control_step" in kernel and "lin_usable" in kernel
     capi = open(os.path.join(CSRC, "gemx_capi.hip")).read()
     assert 'load_side_unit(g_pc_units, "pc"' in capi and "EP_LAUNCH_POLICY_COMPLETE" in capi and "policy_complete_rollout_kernel<%d" in capi

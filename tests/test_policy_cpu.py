@@ -111,5 +111,7 @@ def test_units_and_header():
     assert re.search(r"^#define GEMX_ABI_VERSION 9\b", header, re.M) and _lib.ABI_VERSION == 9  # new structs and entry points only
     for name in ("gemx_policy_create", "gemx_policy_set_weights", "gemx_policy_destroy", "gemx_rollout_policy", "gemx_policy_tanh_probe"):
         assert name in _lib.EXPORTS and re.search(rf"\bint {name}\(", header), name
-    kernel = open(os.path.join(REPO, "gym_electric_motor_amd", "csrc", "gemx_policy.hip")).read()
+    unit = open(os.path.join(REPO, "gym_electric_motor_amd", "csrc", "gemx_policy.hip")).read()
+    assert '#include "gemx_policy_kernel.hpp"' in unit and "PC_GEN_NONE" in unit  # the kernel: the one both kinds of policy unit include
+    kernel = open(os.path.join(REPO, "gym_electric_motor_amd", "csrc", "gemx_policy_kernel.hpp")).read()
     assert 'asm volatile("" : "+v"(y[j]))' in kernel and "ep_control_step" in kernel and "lin_usable" in kernel

@@ -1,8 +1,9 @@
-"""Registers, LDS and scratch of every policy_rollout_kernel instantiation, from the compiler's own remarks: compiles the 19 policy units
-(csrc/gemx_policy.hip) with build.py's flags plus -Rpass-analysis=kernel-resource-usage into a temporary directory and prints the
-markdown table of profiles/policy_rollout.md.  Exit status 1 if any instantiation has scratch.
---complete: the same for every policy_complete_rollout_kernel instantiation of the 19 complete policy units (csrc/gemx_policy_complete.hip;
-one more column, the generator kind: 0 all-Wiener, 1 profile) -- the table of profiles/policy_complete_rollout.md.
+"""Registers, LDS and scratch of every policy_rollout_kernel (csrc/gemx_policy_kernel.hpp) instantiation, from the compiler's own remarks:
+compiles the 19 policy units (csrc/gemx_policy.hip: the kernel without a generator) with build.py's flags plus
+-Rpass-analysis=kernel-resource-usage into a temporary directory and prints the markdown table of profiles/policy_rollout.md.  Exit status
+1 if any instantiation has scratch.
+--complete: the same for the kernel's instantiations in the 19 complete policy units (csrc/gemx_policy_complete.hip; one more column, the
+generator kind: 0 all-Wiener, 1 profile) -- the table of profiles/policy_complete_rollout.md.
 --eval: the four policy_eval_kernel instantiations of csrc/gemx_policy_eval.hip (one per head), compiled once as libgemx.so's object is --
 the table of profiles/policy_eval.md."""
 import concurrent.futures as cf
@@ -20,7 +21,7 @@ EVAL = "--eval" in sys.argv[1:]
 EVAL_NAME = re.compile(r"policy_eval_kernelILi(\d+)E")
 HEADS = ("none", "value", "categorical", "gaussian")
 SOURCE = "gemx_policy_complete.hip" if COMPLETE else "gemx_policy.hip"
-NAME = re.compile(r"policy_complete_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E" if COMPLETE else r"policy_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])E")
+NAME = re.compile(r"policy_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E")  # SYS, CONV, LOAD, SOLVER, TAB, GEN (2 in the policy units: none)
 FIELD = re.compile(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 
 
@@ -56,19 +57,7 @@ def unit(sc, tmp):
     s, c = sc
     cmd = [build.hipcc_path()] + build.FLAGS + ["-I" + build.CSRC, "-I" + os.path.dirname(build.HEADER), f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}",
            "-fvisibility=hidden", "-shared", os.path.join(build.CSRC, SOURCE), "-o", os.path.join(tmp, f"pl{s}_{c}.so"), "-Rpass-analysis=kernel-resource-usage"]
-    text = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
-    rows, cur = [], None
-    for line in text.splitlines():
-        m = NAME.search(line)
-        if "Function Name" in line:
-            cur = dict(key=tuple(int(x) for x in m.groups())) if m else None
-            if cur is not None:
-                rows.append(cur)
-        elif cur is not None:
-            f = FIELD.search(line)
-            if f:
-                cur[f.group(1).split(" [")[0]] = int(f.group(2))
-    return rows
+    return parse(subprocess.run(cmd, capture_output=True, text=True, check=True).stderr, NAME)
 
 
 def main():
