@@ -165,7 +165,6 @@ using namespace gemx;
 
 void gemx_cov_note(const char *key);  // instantiation coverage (below): a process with GEMX_COVERAGE_FILE set lists every distinct kernel it launches
 #define GEMX_COV(name) gemx_cov_note(name)
-void gemx_rewardpass_note(const gemx_handle *h, const void *desc);  // gemx_rewardpass.hip: the host copy of a handle's reward description (nullptr: none)
 static thread_local char g_err[512] = "";
 namespace gemx {
 int fail(int code, const char *fmt, ...) {
@@ -547,28 +546,6 @@ static int launch_advance(gemx_handle *h, const void *actions, int K, void *obs,
 
 static int elem_size(const gemx_handle *h) { return h->cfg.dtype == GEMX_F64 ? 8 : 4; }
 
-template <class R> static void build_reward(const gemx_handle *h, const gemx_reward_config *rc, RewardDev<R> &W) {
-    memset(&W, 0, sizeof(W));
-    int t = 0;
-    bool referenced[GEMX_MAX_OUT] = {};
-    auto add = [&](int col) {
-        W.col[t] = col;
-        const double pw = rc->power[col];
-        W.kind[t] = pw == 1.0 ? 1 : (pw == 2.0 ? 2 : 3);
-        W.coef[t] = (R)rc->weight[col];
-        W.inv_len[t] = (R)(1.0 / rc->state_length[col]);
-        W.power[t] = (R)pw;
-        ++t;
-    };
-    for (int j = 0; j < rc->n_ref; ++j) { add(rc->ref_index[j]); referenced[rc->ref_index[j]] = true; }
-    W.n_ref = rc->n_ref;
-    for (int i = 0; i < h->nout; ++i)
-        if (!referenced[i] && rc->weight[i] != 0.0) add(i);  // weighted but un-referenced states are compared with 0 (core.py:346)
-    W.n_term = t;
-    W.bias = (R)rc->bias;
-    W.violation_reward = (R)rc->violation_reward;
-}
-
 extern "C" {
 
 int gemx_abi_version(void) { return GEMX_ABI_VERSION; }
@@ -842,7 +819,6 @@ int gemx_create(const gemx_config *cfg, int64_t n_envs, int device, gemx_handle 
 
 int gemx_destroy(gemx_handle *h) {
     if (!h) return GEMX_OK;
-    gemx_rewardpass_note(h, nullptr);
     gemx::DeviceGuard guard(h->device);
     if (h->state) (void)hipFree(h->state);
     if (h->angle) (void)hipFree(h->angle);
@@ -1072,30 +1048,18 @@ int gemx_rollout_half(gemx_handle *h, const void *actions_half_dev, int32_t K, v
 
 int gemx_set_reward(gemx_handle *h, const gemx_reward_config *rc) {
     if (!h) return fail(GEMX_ERR_ARG, "null handle");
-    if (!rc) { h->rw_n_ref = -1; gemx_rewardpass_note(h, nullptr); return GEMX_OK; }
-    if (rc->struct_size != (int32_t)sizeof(gemx_reward_config)) return fail(GEMX_ERR_ARG, "gemx_reward_config size mismatch");
-    if (rc->n_ref < 0 || rc->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "n_ref must be in [0, %d]", GEMX_MAX_REF);
-    for (int j = 0; j < rc->n_ref; ++j) {
-        if (rc->ref_index[j] < 0 || rc->ref_index[j] >= h->nout) return fail(GEMX_ERR_ARG, "ref_index[%d] out of range", j);
-        for (int k = 0; k < j; ++k)
-            if (rc->ref_index[k] == rc->ref_index[j]) return fail(GEMX_ERR_ARG, "ref_index has duplicates");
-    }
-    for (int i = 0; i < h->nout; ++i)
-        if (rc->weight[i] != 0.0 && !(rc->state_length[i] > 0)) return fail(GEMX_ERR_ARG, "state_length[%d] must be positive", i);
+    if (!rc) { h->rw_n_ref = -1; return GEMX_OK; }
+    if (int bad = reward_check(rc, h->nout)) return bad;
     gemx::DeviceGuard guard(h->device);
     if (!h->rw_dev && hipMalloc(&h->rw_dev, sizeof(RewardDev<double>)) != hipSuccess) return fail(GEMX_ERR_ALLOC, "hipMalloc(reward) failed");
     if (h->cfg.dtype == GEMX_F64) {
-        RewardDev<double> W;
-        build_reward(h, rc, W);
-        reward_hot_from(W, h->rh_d);
-        HIP_TRY(hipMemcpy(h->rw_dev, &W, sizeof(W), hipMemcpyHostToDevice));
-        gemx_rewardpass_note(h, &W);
+        reward_build(h->nout, rc, h->rw_d);
+        reward_hot_from(h->rw_d, h->rh_d);
+        HIP_TRY(hipMemcpy(h->rw_dev, &h->rw_d, sizeof(h->rw_d), hipMemcpyHostToDevice));
     } else {
-        RewardDev<float> W;
-        build_reward(h, rc, W);
-        reward_hot_from(W, h->rh_f);
-        HIP_TRY(hipMemcpy(h->rw_dev, &W, sizeof(W), hipMemcpyHostToDevice));
-        gemx_rewardpass_note(h, &W);
+        reward_build(h->nout, rc, h->rw_f);
+        reward_hot_from(h->rw_f, h->rh_f);
+        HIP_TRY(hipMemcpy(h->rw_dev, &h->rw_f, sizeof(h->rw_f), hipMemcpyHostToDevice));
     }
     h->rw_n_ref = rc->n_ref;
     return GEMX_OK;

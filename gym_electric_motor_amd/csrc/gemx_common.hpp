@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "gemx.h"
+#include "gemx_reward.hpp"  // the reward: description, hot terms, checks, builder, the reward of one row
 
 namespace gemx {
 
@@ -434,48 +435,6 @@ __host__ __device__ __forceinline__ float synth_unit(uint32_t x) { return (float
 __host__ __device__ __forceinline__ uint32_t synth_index(uint32_t x, uint32_t n_actions) { return (uint32_t)(((uint64_t)x * n_actions) >> 32); }
 
 // ------------------------------------------------------------------------------------------------
-// fused reward (WeightedSumOfErrors): device-resident description, read through scalar loads when a reward is requested
-// ------------------------------------------------------------------------------------------------
-template <class R> struct RewardDev {
-    // terms 0 .. n_ref-1 compare state column col[t] with reference column t; terms n_ref .. n_term-1 compare with 0
-    int32_t n_ref, n_term;
-    int32_t col[GEMX_MAX_OUT];
-    int32_t kind[GEMX_MAX_OUT];   // 1: power 1, 2: power 2, 3: general power (pow)
-    R coef[GEMX_MAX_OUT];         // weight (applied after the power)
-    R inv_len[GEMX_MAX_OUT];      // 1 / state_length
-    R power[GEMX_MAX_OUT];
-    R bias, violation_reward;
-};
-
-// The first GEMX_REWARD_HOT terms by value, inside the kernel arguments: kernel arguments are read with SCALAR loads (lgkmcnt).  Read
-// through the device pointer (KArgs::rw) the same words are VECTOR loads with a uniform address -- the compiler cannot prove that the
-// kernel's own stores do not alias them -- and their `s_waitcnt vmcnt(0)` waits, vmcnt retiring in order, for every observation store
-// the wave has in flight: ~5000 cycles per block in the pipelined kernel's output waves (s_memtime probe).
-constexpr int GEMX_REWARD_HOT = 4;
-template <class R> struct RewardHot {
-    int32_t n_ref, n_term, general;  // general: some term has a power other than 1 or 2 (pow() path through KArgs::rw)
-    int32_t col[GEMX_REWARD_HOT], kind[GEMX_REWARD_HOT];  // unused terms: column 0, kind 1, weight 0
-    R coef[GEMX_REWARD_HOT], inv_len[GEMX_REWARD_HOT], power[GEMX_REWARD_HOT];
-    R bias, violation_reward;
-};
-template <class R> inline void reward_hot_from(const RewardDev<R> &W, RewardHot<R> &H) {
-    H.n_ref = W.n_ref;
-    H.n_term = W.n_term;
-    H.general = 0;
-    for (int t = 0; t < W.n_term; ++t) H.general |= W.kind[t] == 3;
-    for (int t = 0; t < GEMX_REWARD_HOT; ++t) {
-        const bool used = t < W.n_term;
-        H.col[t] = used ? W.col[t] : 0;
-        H.kind[t] = used ? W.kind[t] : 1;
-        H.coef[t] = used ? W.coef[t] : R(0);
-        H.inv_len[t] = used ? W.inv_len[t] : R(0);
-        H.power[t] = used ? W.power[t] : R(1);
-    }
-    H.bias = W.bias;
-    H.violation_reward = W.violation_reward;
-}
-
-// ------------------------------------------------------------------------------------------------
 // kernel arguments
 // ------------------------------------------------------------------------------------------------
 template <class R> struct KArgs {
@@ -603,6 +562,8 @@ struct gemx_handle {
     void *rinit_dev = nullptr;  // InitDev (random initial states)
     uint32_t *rcnt = nullptr;   // [n] resets so far per env
     void *rw_dev = nullptr;  // RewardDev<R> (gemx_set_reward)
+    gemx::RewardDev<float> rw_f = {};   // its host copy, of the handle's dtype (gemx_reward_rows passes it by value)
+    gemx::RewardDev<double> rw_d = {};
     gemx::RewardHot<float> rh_f = {};   // its first terms by value (kernel argument)
     gemx::RewardHot<double> rh_d = {};
     int rw_n_ref = -1;       // -1: no reward installed

@@ -84,9 +84,10 @@ __global__ __launch_bounds__(BLOCK) void envparams_step_kernel(const KArgs<R> a,
 // action (and the fused reward's references) of step k + 1 is loaded before step k computes and stores -- loads and stores retire through
 // one in-order counter, so a load issued BEHIND a step's stores would wait for them --, every step's row, done byte and reward are written
 // in the layout gemx_rollout / gemx_rollout_reward write ([K][N][S_out] or [K][S_out][N], [K][N], [K][N]).
-// The fused reward is reward_apply's arithmetic (WeightedSumOfErrors) on the row in registers: the hot terms by value from the kernel
-// arguments, further terms and general powers through the description in memory; a column is picked without a dynamic index into the row, which would put
-// it into scratch (ep_pick).
+// The fused reward is reward_row's statements (gemx_reward.hpp, the definition of WeightedSumOfErrors) on the row in registers, kept in
+// place because the call changed this kernel's code (profiles/reward_row_refactor.md): the hot terms by value from the kernel arguments,
+// further terms and general powers through the description in memory; a column is picked without a dynamic index into the row, which
+// would put it into scratch (ep_pick).
 // ------------------------------------------------------------------------------------------------
 // (as AND / OR on the bit patterns: a chain of selects on one index is folded back into an indexed array by the compiler -- the DFIM's
 // 24-value rows went through scratch that way)
@@ -169,7 +170,7 @@ __global__ __launch_bounds__(BLOCK) void envparams_rollout_kernel(const KArgs<R>
             ang = init_ang;
         }
         R rwd = R(0);
-        if (rewarded) {  // reward_apply, term by term in its order
+        if (rewarded) {  // reward_row (gemx_reward.hpp), its statements in place: through the call this kernel compiles to other code
             R acc = R(0);
             if (!W.general) {
 #pragma unroll

@@ -2055,13 +2055,7 @@ template <class R> struct RewardRegs {
         violation_reward = w.violation_reward;
     }
 };
-// GENERAL: reward_power other than 1 or 2 allowed (pow(): a ~300-instruction expansion, so it must not be unrolled per term)
-template <bool GENERAL, class R> __device__ __forceinline__ R reward_term(R o, R ref, R inv_len, int kind, R power, R coef) {
-    const R dlt = fabs(o - ref) * inv_len;
-    R p = dlt * (kind == 2 ? dlt : R(1));  // (a select, not a branch: dlt * 1 == dlt exactly)
-    if (GENERAL && kind == 3) p = pow(dlt, power);
-    return coef * p;
-}
+// (reward_term and the definition of a row's reward, reward_row: gemx_reward.hpp)
 template <int NOUT, int RB, class R, int EB = BLOCK>
 __device__ __forceinline__ void reward_apply(const KArgs<R> &a, const RewardRegs<R> &W, const R *ring, const unsigned char *donebuf, int k0,
                                              int row0, int nr, int tid, int64_t env, bool valid, const R (&rv)[RB][GEMX_MAX_REF]) {
@@ -2086,6 +2080,7 @@ __device__ __forceinline__ void reward_apply(const KArgs<R> &a, const RewardRegs
     for (int s = 0; s < RB; ++s) {
         if (s < nr) {
             const int row = row0 + s;  // row of the ring / done ring
+            // reward_row (gemx_reward.hpp), its statements in place: through the call the stepping kernels compile to other code
             R acc = R(0);
             if (!W.general) {
 #pragma unroll

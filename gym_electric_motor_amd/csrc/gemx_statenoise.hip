@@ -4,7 +4,7 @@
 // physics; under a noise wrapper the physics runs with no constraint, no auto-reset and no reward, and this unit, ONE launch behind it,
 //   1. adds the draw of (env, noisy column, stream position) to the noisy columns of the row,
 //   2. decides `done` on the noisy row with constraint_done's expressions (gemx_kernels.hpp),
-//   3. rewards the noisy row with gemx_reward_rows' arithmetic (gemx_rewardpass.hip), operation for operation,
+//   3. rewards the noisy row with reward_row (gemx_reward.hpp), the one definition gemx_reward_rows and the fused reward call too,
 // and the env feeds the done mask back as the mask of the next step's gemx_reset.
 //
 // Shape: a streaming read-modify-write of N rows of n_in values, sizeof(R) * (2 n_in + n_ref + 1) + 1 bytes per row -- the observation
@@ -70,20 +70,11 @@ template <class R> __device__ inline R noise_value(const NoiseDev &D, int64_t en
     return (R)noise_draw(D.dist[j], D.p0[j], D.p1[j], r[o], r[o + 1]);
 }
 
-// reward_term of gemx_kernels.hpp as gemx_rewardpass.hip restates it
-template <bool GENERAL, class R> __device__ __forceinline__ R rew_term(R o, R ref, R inv_len, int kind, R power, R coef) {
-    const R dlt = fabs(o - ref) * inv_len;
-    R p = dlt * (kind == 2 ? dlt : R(1));
-    if (GENERAL && kind == 3) p = pow(dlt, power);
-    return coef * p;
-}
-
 template <class R>
 __global__ __launch_bounds__(NoiseTile<R>::rows) void state_noise_kernel(const R *state_in, const R *__restrict__ refs, R *state_out, uint8_t *__restrict__ done,
                                                                         R *__restrict__ reward, uint64_t *__restrict__ pos, int64_t rows, uint32_t magic, int vec_in,
-                                                                        int vec_out, int general, NoiseDev D, RewardDev<R> W) {
+                                                                        int vec_out, NoiseDev D, RewardHot<R> H, RewardDev<R> W) {
     constexpr int T = NoiseTile<R>::rows, DW = (int)sizeof(R) / 4, HOT = gemx::GEMX_REWARD_HOT;
-    static_assert(HOT >= GEMX_MAX_REF, "referenced states must be hot terms");
     extern __shared__ __attribute__((aligned(16))) uint32_t noise_smem[];
     const uint32_t L = (uint32_t)D.n_in * DW, S = L | 1u;  // odd row stride: lanes r and r' != r (mod 32) touch distinct banks
     const int64_t tile0 = (int64_t)blockIdx.x * T;
@@ -97,10 +88,10 @@ __global__ __launch_bounds__(NoiseTile<R>::rows) void state_noise_kernel(const R
 #pragma unroll
     for (int j = 0; j < GEMX_MAX_REF; ++j) rv[j] = R(0);
     if (valid && reward != nullptr) {  // this lane's references, in flight across the barrier
-        const R *rp = refs + g * W.n_ref;
+        const R *rp = refs + g * H.n_ref;
 #pragma unroll
         for (int j = 0; j < GEMX_MAX_REF; ++j)
-            if (j < W.n_ref) rv[j] = rp[j];
+            if (j < H.n_ref) rv[j] = rp[j];
     }
     __syncthreads();
     if (valid) {
@@ -133,25 +124,11 @@ __global__ __launch_bounds__(NoiseTile<R>::rows) void state_noise_kernel(const R
         done[g] = dn ? 1 : 0;
         // 3. the reward of the noisy row
         if (reward != nullptr) {
-            R acc = R(0);
-            if (!general) {
+            auto at = [&](int col) { return tile_get(mine + (uint32_t)col * DW, R(0)); };
+            R oh[HOT];
 #pragma unroll
-                for (int t = 0; t < HOT; ++t) {
-                    const bool used = t < W.n_term;
-                    const int col = used ? W.col[t] : 0, kind = used ? W.kind[t] : 1;
-                    const R coef = used ? W.coef[t] : R(0), inv_len = used ? W.inv_len[t] : R(0), power = used ? W.power[t] : R(1);
-                    acc += rew_term<false, R>(tile_get(mine + (uint32_t)col * DW, R(0)), rv[t], inv_len, kind, power, coef);
-                }
-            }
-#pragma nounroll
-            for (int t = general ? 0 : HOT; t < W.n_term; ++t) {
-                R ref = R(0);
-#pragma unroll
-                for (int j = 0; j < GEMX_MAX_REF; ++j) ref = (t == j) ? rv[j] : ref;
-                acc += rew_term<true, R>(tile_get(mine + (uint32_t)W.col[t] * DW, R(0)), ref, W.inv_len[t], W.kind[t], W.power[t], W.coef[t]);
-            }
-            const R wse = W.bias - acc;
-            reward[g] = dn ? W.violation_reward : wse;
+            for (int t = 0; t < HOT; ++t) oh[t] = at(H.col[t]);
+            reward[g] = reward_row<R>(H, &W, oh, at, rv, dn);
         }
     }
     __syncthreads();
@@ -173,49 +150,28 @@ __global__ void noise_fill_kernel(uint64_t *pos, int n, uint64_t value) {
     if (i < n) pos[i] = value;
 }
 
-// build_reward of gemx_capi.hip for a row of n_in columns
-template <class R> void noise_build_reward(int n_in, const gemx_reward_config *rc, RewardDev<R> &W) {
-    memset(&W, 0, sizeof(W));
-    int t = 0;
-    bool referenced[GEMX_MAX_OUT] = {};
-    auto add = [&](int col) {
-        W.col[t] = col;
-        const double pw = rc->power[col];
-        W.kind[t] = pw == 1.0 ? 1 : (pw == 2.0 ? 2 : 3);
-        W.coef[t] = (R)rc->weight[col];
-        W.inv_len[t] = (R)(1.0 / rc->state_length[col]);
-        W.power[t] = (R)pw;
-        ++t;
-    };
-    for (int j = 0; j < rc->n_ref; ++j) { add(rc->ref_index[j]); referenced[rc->ref_index[j]] = true; }
-    W.n_ref = rc->n_ref;
-    for (int i = 0; i < n_in; ++i)
-        if (!referenced[i] && rc->weight[i] != 0.0) add(i);
-    W.n_term = t;
-    W.bias = (R)rc->bias;
-    W.violation_reward = (R)rc->violation_reward;
-}
-
 }  // namespace
 
 struct gemx_noise {
     gemx_noise_config cfg;
     NoiseDev dev;
-    RewardDev<float> wf;
+    RewardDev<float> wf;  // the reward description and its hot terms, both dtypes (zero without a reward)
     RewardDev<double> wd;
+    RewardHot<float> hf;
+    RewardHot<double> hd;
     int64_t n;
-    int device, f64, tiles, general;
+    int device, f64, tiles;
     uint64_t *pos;  // [tiles]
 };
 
 template <class R>
-static int noise_launch(gemx_noise *h, const RewardDev<R> &W, const void *in, const void *refs, void *out, uint8_t *done, void *reward, hipStream_t st) {
+static int noise_launch(gemx_noise *h, const RewardHot<R> &H, const RewardDev<R> &W, const void *in, const void *refs, void *out, uint8_t *done, void *reward, hipStream_t st) {
     constexpr int T = NoiseTile<R>::rows, DW = (int)sizeof(R) / 4;
     const uint32_t L = (uint32_t)h->dev.n_in * DW;
     const size_t lds = (size_t)T * (L | 1u) * 4u;
     gemx_cov_note(sizeof(R) == 4 ? "state_noise_kernel<float>" : "state_noise_kernel<double>");
     hipLaunchKernelGGL(state_noise_kernel<R>, dim3((unsigned)h->tiles), dim3(T), lds, st, (const R *)in, (const R *)refs, (R *)out, done, (R *)reward, h->pos, h->n,
-                       tile_magic(L), (int)(((uintptr_t)in & 15u) == 0), (int)(((uintptr_t)out & 15u) == 0), h->general, h->dev, W);
+                       tile_magic(L), (int)(((uintptr_t)in & 15u) == 0), (int)(((uintptr_t)out & 15u) == 0), h->dev, H, W);
     GEMX_HIP_TRY(hipGetLastError());
     return GEMX_OK;
 }
@@ -244,22 +200,12 @@ int gemx_noise_create(const gemx_noise_config *cfg, int64_t n_envs, int dtype, i
             return gemx::fail(GEMX_ERR_ARG, "slot %d: scale must be >= 0 (uniform: high >= low)", j);
     }
     if (cfg->has_reward != 0 && cfg->has_reward != 1) return gemx::fail(GEMX_ERR_ARG, "has_reward must be 0 or 1");
-    if (cfg->has_reward) {
-        const gemx_reward_config *rc = &cfg->reward;
-        if (rc->struct_size != (int32_t)sizeof(gemx_reward_config)) return gemx::fail(GEMX_ERR_ARG, "gemx_reward_config size mismatch");
-        if (rc->n_ref < 0 || rc->n_ref > GEMX_MAX_REF) return gemx::fail(GEMX_ERR_ARG, "n_ref must be in [0, %d]", GEMX_MAX_REF);
-        for (int j = 0; j < rc->n_ref; ++j) {
-            if (rc->ref_index[j] < 0 || rc->ref_index[j] >= cfg->n_in) return gemx::fail(GEMX_ERR_ARG, "ref_index[%d] out of range", j);
-            for (int k = 0; k < j; ++k)
-                if (rc->ref_index[k] == rc->ref_index[j]) return gemx::fail(GEMX_ERR_ARG, "ref_index has duplicates");
-        }
-        for (int i = 0; i < cfg->n_in; ++i)
-            if (rc->weight[i] != 0.0 && !(rc->state_length[i] > 0)) return gemx::fail(GEMX_ERR_ARG, "state_length[%d] must be positive", i);
-    }
+    if (cfg->has_reward)
+        if (int rc = gemx::reward_check(&cfg->reward, cfg->n_in)) return rc;
     if (int rc = gemx::check_device_dtype(device, dtype)) return rc;
     gemx_noise *h = new (std::nothrow) gemx_noise();
     if (!h) return gemx::fail(GEMX_ERR_ALLOC, "out of host memory");
-    h->cfg = *cfg; h->n = n_envs; h->device = device; h->f64 = dtype == GEMX_F64; h->pos = nullptr; h->general = 0;
+    h->cfg = *cfg; h->n = n_envs; h->device = device; h->f64 = dtype == GEMX_F64; h->pos = nullptr;
     const int T = h->f64 ? NoiseTile<double>::rows : NoiseTile<float>::rows;
     const int64_t tiles = (n_envs + T - 1) / T;
     if (tiles > 0x7fffffffLL) { delete h; return gemx::fail(GEMX_ERR_ARG, "n_envs = %lld exceeds %d tiles of %d rows", (long long)n_envs, 0x7fffffff, T); }
@@ -274,13 +220,14 @@ int gemx_noise_create(const gemx_noise_config *cfg, int64_t n_envs, int dtype, i
     D.pair_form = pair_rows && cfg->squared_mask == 0x60u && cfg->limit_mask == (cfg->n_in == 16 ? 0x80u : 0u);
     D.pair_a = 5; D.pair_b = 6;
     if (cfg->has_reward) {
-        noise_build_reward(cfg->n_in, &cfg->reward, h->wf);
-        noise_build_reward(cfg->n_in, &cfg->reward, h->wd);
-        for (int t = 0; t < h->wd.n_term; ++t) h->general |= h->wd.kind[t] == 3;
+        reward_build(cfg->n_in, &cfg->reward, h->wf);
+        reward_build(cfg->n_in, &cfg->reward, h->wd);
     } else {
         memset(&h->wf, 0, sizeof(h->wf));
         memset(&h->wd, 0, sizeof(h->wd));
     }
+    reward_hot_from(h->wf, h->hf);
+    reward_hot_from(h->wd, h->hd);
     gemx::DeviceGuard guard(device);
     if (hipMalloc(&h->pos, (size_t)tiles * sizeof(uint64_t)) != hipSuccess) { delete h; return gemx::fail(GEMX_ERR_ALLOC, "hipMalloc(noise position) failed"); }
     if (hipMemset(h->pos, 0, (size_t)tiles * sizeof(uint64_t)) != hipSuccess) { (void)hipFree(h->pos); delete h; return gemx::fail(GEMX_ERR_DEVICE, "hipMemset(noise position) failed"); }
@@ -306,8 +253,8 @@ int gemx_noise_step(gemx_noise *h, const void *state_in_dev, const void *refs_de
     if (!gemx::elem_aligned(h->f64 != 0, state_in_dev, state_out_dev, reward_out_dev, refs ? refs_dev : nullptr)) return gemx::fail_unaligned();
     gemx::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    return h->f64 ? noise_launch<double>(h, h->wd, state_in_dev, refs_dev, state_out_dev, done_out_dev, reward_out_dev, st)
-                  : noise_launch<float>(h, h->wf, state_in_dev, refs_dev, state_out_dev, done_out_dev, reward_out_dev, st);
+    return h->f64 ? noise_launch<double>(h, h->hd, h->wd, state_in_dev, refs_dev, state_out_dev, done_out_dev, reward_out_dev, st)
+                  : noise_launch<float>(h, h->hf, h->wf, state_in_dev, refs_dev, state_out_dev, done_out_dev, reward_out_dev, st);
 }
 
 int gemx_noise_draws(gemx_noise *h, uint64_t step0, int32_t K, void *out_dev, void *stream) {
