@@ -4,6 +4,8 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_common.hpp, gemx_kernels.hpp   device templates
     gemx_reward.hpp                     the WeightedSumOfErrors reward, once: description, checks, builder, the reward of one row (gemx_common.hpp includes it)
     gemx_unit_host.hpp                  the host code every dlopen'ed unit repeats: error sink, unit_init, (load, solver) dispatch, one-step map, KArgs
+    gemx_launch_plan.hpp                how a fused rollout is launched (shape, LDS, rate limiter): a pure layer a host compiler builds, and the
+                                        runtime queries behind it; host code only (gemx_kernels.hpp includes it)
     gemx_inst.hip                       ONE kernel unit, compiled once per (system, converter unit, dtype) into its OWN shared object
                                         libgemx_u<S>_<C>_<F>.so, which gemx_create loads with dlopen (round 6: a handle maps the C ABI and
                                         the one unit it runs, not all 38)
@@ -55,7 +57,7 @@ SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc",
            ("statenoise", "gemx_statenoise.hip", ["gemx_support.hpp"], 0.1), ("episode", "gemx_episode.hip", ["gemx_support.hpp"], 0.05),
            ("refprofile", "gemx_refprofile.hip", ["gemx_support.hpp"], 0.05), ("returns", "gemx_returns.hip", ["gemx_support.hpp"], 0.05),
            ("policy_eval", "gemx_policy_eval.hip", ["gemx_support.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp"], 0.1)]
-SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_reward.hpp", "gemx_kernels.hpp", "gemx_unit_host.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
+SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_reward.hpp", "gemx_kernels.hpp", "gemx_launch_plan.hpp", "gemx_unit_host.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
                                            "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip",
                                            "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
@@ -114,7 +116,7 @@ def _digest(sources=None, header=None):
 
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
 _COMMON = ["gemx_common.hpp", "gemx_reward.hpp"]  # every object (gemx_common.hpp includes gemx_reward.hpp)
-_UNIT = _COMMON + ["gemx_kernels.hpp", "gemx_unit_host.hpp"]  # every dlopen'ed unit
+_UNIT = _COMMON + ["gemx_kernels.hpp", "gemx_launch_plan.hpp", "gemx_unit_host.hpp"]  # every dlopen'ed unit
 _DEPS = {"inst": _UNIT + ["gemx_inst.hip"], "capi": _COMMON + ["gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_capi.hip"],
          "envparams": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
          "episodic": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],

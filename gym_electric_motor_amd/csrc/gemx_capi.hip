@@ -446,7 +446,7 @@ __global__ void aux_header_kernel(AuxHeader hd, const uint32_t *fifo_phase, AuxH
 // state access / reference generators: ~2 MB) and the one unit it runs (2-6 MB) instead of 144 MB of all 38.  GEMX_UNIT_DIR names another
 // directory.  A unit exports gemx_unit_init (checks that it was compiled against THIS handle layout and receives the error sink) and
 // gemx_unit_launch (what gemx::launch_unit_S_C_F used to be).
-typedef int (*gemx_unit_launch_fn)(gemx_handle *, const void *, int, void *, uint8_t *, int, hipStream_t);
+typedef gemx::advance_fn gemx_unit_launch_fn;
 typedef int (*gemx_unit_init_fn)(unsigned long long handle_bytes, int abi, void (*set_error)(const char *));
 struct UnitLib { void *dl = nullptr; gemx_unit_launch_fn launch = nullptr; };
 static UnitLib g_units[8][12][2];
@@ -521,15 +521,15 @@ static void cov_note_launch(const gemx_handle *h, bool linmap_built) {
     if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, %s>", l.sys, l.solver, R); gemx_cov_note(key); }
 }
 
-static int launch_advance(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st) {
+static int launch_advance(gemx_handle *h, const RolloutCall &call, hipStream_t st) {
     if (h->envp != nullptr) {  // per-env parameters (gemx_set_env_params): the two kernels of the handle's per-env unit serve every launch
-        if (h->cur_synth) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_synthetic is not available on a handle with a parameter table (gemx_synthetic_actions + gemx_rollout)");
-        if (h->cur_half) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_half is not available on a handle with a parameter table (fp32 actions)");
-        if (!obs_every) return fail(GEMX_ERR_ARG, "per-env parameters: last-step-only launches (obs_every = 0) are not available on a handle with a parameter table");
+        if (call.synth) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_synthetic is not available on a handle with a parameter table (gemx_synthetic_actions + gemx_rollout)");
+        if (call.half) return fail(GEMX_ERR_ARG, "per-env parameters: gemx_rollout_half is not available on a handle with a parameter table (fp32 actions)");
+        if (!call.obs_every) return fail(GEMX_ERR_ARG, "per-env parameters: last-step-only launches (obs_every = 0) are not available on a handle with a parameter table");
         if (h->ep_launch == nullptr) return fail(GEMX_ERR_ARG, "internal: the handle's per-env parameter unit is not loaded");
-        const int rc = ((gemx_ep_unit_launch_fn)h->ep_launch)(h, actions, K, obs, done, st);
+        const int rc = ((gemx_ep_unit_launch_fn)h->ep_launch)(h, call, st);
         if (rc != GEMX_OK) return rc;
-        h->steps_total += (unsigned long long)K;
+        h->steps_total += (unsigned long long)call.K;
         char key[256];
         snprintf(key, sizeof(key), "%s<%d, %d, %d, %d, float>", h->ll.pipe == EP_LAUNCH_STEP ? "envparams_step_kernel" : "envparams_rollout_kernel", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver);
         gemx_cov_note(key);
@@ -537,9 +537,9 @@ static int launch_advance(gemx_handle *h, const void *actions, int K, void *obs,
     }
     if (h->unit_launch == nullptr) return fail(GEMX_ERR_ARG, "internal: the handle's kernel unit is not loaded");
     const int lin_before = h->linmap_state;
-    const int rc = ((gemx_unit_launch_fn)h->unit_launch)(h, actions, K, obs, done, obs_every, st);
+    const int rc = ((gemx_unit_launch_fn)h->unit_launch)(h, call, st);
     if (rc != GEMX_OK) return rc;
-    h->steps_total += (unsigned long long)K;  // (only what was launched: a refused launch leaves the count the checkpoint header carries alone)
+    h->steps_total += (unsigned long long)call.K;  // (only what was launched: a refused launch leaves the count the checkpoint header carries alone)
     cov_note_launch(h, lin_before == 0 && h->linmap_state == 1);
     return GEMX_OK;
 }
@@ -864,31 +864,20 @@ int gemx_reset_observation(const gemx_handle *h, double *obs_host) {
     return GEMX_OK;
 }
 
-int gemx_reset(gemx_handle *h, const uint8_t *mask_dev, void *obs_out_dev, void *stream) {
+// gemx_reset (advance = 1) and gemx_reset_again (advance = 0: launch_reset)
+static int reset_envs(gemx_handle *h, const uint8_t *mask_dev, void *obs_out_dev, void *stream, int advance) {
     if (!h) return fail(GEMX_ERR_ARG, "null handle");
     gemx::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    const int rc = h->cfg.dtype == GEMX_F64 ? launch_reset<double>(h, mask_dev, obs_out_dev, st) : launch_reset<float>(h, mask_dev, obs_out_dev, st);
+    const int rc = h->cfg.dtype == GEMX_F64 ? launch_reset<double>(h, mask_dev, obs_out_dev, st, advance) : launch_reset<float>(h, mask_dev, obs_out_dev, st, advance);
     // host-side knowledge "every env's omega is init[0]" (dc_stream_kernel's premise).  A call that is being CAPTURED into a graph runs
     // later, any number of times: from then on the host knows nothing (the kernels that decide on the device serve the handle)
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &capturing);
-    if (capturing != hipStreamCaptureStatusNone) { h->omega_unknown = true; h->omega_is_init = false; }
+    if (gemx::stream_capturing(st)) { h->omega_unknown = true; h->omega_is_init = false; }
     else if (rc == GEMX_OK && mask_dev == nullptr && h->cfg.init_kind == GEMX_INIT_CONST && !h->omega_unknown) h->omega_is_init = true;
     return rc;
 }
-
-int gemx_reset_again(gemx_handle *h, const uint8_t *mask_dev, void *obs_out_dev, void *stream) {
-    if (!h) return fail(GEMX_ERR_ARG, "null handle");
-    gemx::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    const int rc = h->cfg.dtype == GEMX_F64 ? launch_reset<double>(h, mask_dev, obs_out_dev, st, 0) : launch_reset<float>(h, mask_dev, obs_out_dev, st, 0);
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &capturing);
-    if (capturing != hipStreamCaptureStatusNone) { h->omega_unknown = true; h->omega_is_init = false; }
-    else if (rc == GEMX_OK && mask_dev == nullptr && h->cfg.init_kind == GEMX_INIT_CONST && !h->omega_unknown) h->omega_is_init = true;
-    return rc;
-}
+int gemx_reset(gemx_handle *h, const uint8_t *mask_dev, void *obs_out_dev, void *stream) { return reset_envs(h, mask_dev, obs_out_dev, stream, 1); }
+int gemx_reset_again(gemx_handle *h, const uint8_t *mask_dev, void *obs_out_dev, void *stream) { return reset_envs(h, mask_dev, obs_out_dev, stream, 0); }
 
 int64_t gemx_aux_state_bytes(const gemx_handle *h) {
     if (!h) return GEMX_ERR_ARG;
@@ -930,9 +919,7 @@ int gemx_set_aux_state(gemx_handle *h, const void *blob_in_dev, void *stream) {
     if (!h || !blob_in_dev) return fail(GEMX_ERR_ARG, "null argument");
     gemx::DeviceGuard guard(h->device);
     hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &capturing);
-    if (capturing != hipStreamCaptureStatusNone) return fail(GEMX_ERR_ARG, "gemx_set_aux_state validates the blob on the host: not inside a stream capture");
+    if (gemx::stream_capturing(st)) return fail(GEMX_ERR_ARG, "gemx_set_aux_state validates the blob on the host: not inside a stream capture");
     AuxHeader hd;
     HIP_TRY(hipMemcpyAsync(&hd, blob_in_dev, sizeof(hd), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -960,15 +947,20 @@ int gemx_set_aux_state(gemx_handle *h, const void *blob_in_dev, void *stream) {
     return GEMX_OK;
 }
 
+// gemx_rollout's checks and launch: also what gemx_rollout_reward runs, with the reward's tensors in the call
+static int rollout_checked(gemx_handle *h, const RolloutCall &call, void *stream) {
+    if (!h) return fail(GEMX_ERR_ARG, "null handle");
+    if (!call.actions || !call.obs) return fail(GEMX_ERR_ARG, "actions_dev and obs_out_dev must not be null");
+    if (call.K < 1) return fail(GEMX_ERR_ARG, "K must be >= 1");
+    if (((uintptr_t)call.obs & 15u) != 0) return fail(GEMX_ERR_ARG, "obs_out_dev must be 16-byte aligned");
+    gemx::DeviceGuard guard(h->device);
+    return launch_advance(h, call, (hipStream_t)stream);
+}
 int gemx_rollout(gemx_handle *h, const void *actions_dev, int32_t K, void *obs_out_dev, uint8_t *done_out_dev, int32_t obs_every,
                  void *stream) {
-    if (!h) return fail(GEMX_ERR_ARG, "null handle");
-    if (!actions_dev || !obs_out_dev) return fail(GEMX_ERR_ARG, "actions_dev and obs_out_dev must not be null");
-    if (K < 1) return fail(GEMX_ERR_ARG, "K must be >= 1");
-    if (((uintptr_t)obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "obs_out_dev must be 16-byte aligned");
-    gemx::DeviceGuard guard(h->device);
-    hipStream_t st = (hipStream_t)stream;
-    return launch_advance(h, actions_dev, K, obs_out_dev, done_out_dev, obs_every ? 1 : 0, st);
+    RolloutCall call;
+    call.actions = actions_dev; call.K = K; call.obs = obs_out_dev; call.done = done_out_dev; call.obs_every = obs_every ? 1 : 0;
+    return rollout_checked(h, call, stream);
 }
 
 // number of discrete actions of the handle's converter (0: continuous)
@@ -1023,12 +1015,10 @@ int gemx_rollout_synthetic(gemx_handle *h, uint64_t seed, uint32_t step0, int32_
     if (((uintptr_t)obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "obs_out_dev must be 16-byte aligned");
     if (h->cfg.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "gemx_rollout_synthetic: fp32 handles only (the fp64 build runs gemx_synthetic_actions + gemx_rollout)");
     gemx::DeviceGuard guard(h->device);
-    h->cur_synth = true;
-    h->cur_seed = seed;
-    h->cur_step0 = step0;
-    const int rc = launch_advance(h, nullptr, K, obs_out_dev, done_out_dev, 1, (hipStream_t)stream);
-    h->cur_synth = false;
-    return rc;
+    RolloutCall call;
+    call.K = K; call.obs = obs_out_dev; call.done = done_out_dev;
+    call.synth = true; call.seed = seed; call.step0 = step0;
+    return launch_advance(h, call, (hipStream_t)stream);
 }
 
 int gemx_rollout_half(gemx_handle *h, const void *actions_half_dev, int32_t K, void *obs_out_dev, uint8_t *done_out_dev, void *stream) {
@@ -1040,10 +1030,10 @@ int gemx_rollout_half(gemx_handle *h, const void *actions_half_dev, int32_t K, v
     if (h->cfg.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "gemx_rollout_half: fp32 handles only");
     if (n_discrete_actions(h) > 0) return fail(GEMX_ERR_ARG, "gemx_rollout_half: continuous converters only (a discrete action is one byte already)");
     gemx::DeviceGuard guard(h->device);
-    h->cur_half = true;
-    const int rc = launch_advance(h, actions_half_dev, K, obs_out_dev, done_out_dev, 1, (hipStream_t)stream);
-    h->cur_half = false;
-    return rc;
+    RolloutCall call;
+    call.actions = actions_half_dev; call.K = K; call.obs = obs_out_dev; call.done = done_out_dev;
+    call.half = true;
+    return launch_advance(h, call, (hipStream_t)stream);
 }
 
 int gemx_set_reward(gemx_handle *h, const gemx_reward_config *rc) {
@@ -1070,12 +1060,10 @@ int gemx_rollout_reward(gemx_handle *h, const void *actions_dev, int32_t K, cons
     if (!h) return fail(GEMX_ERR_ARG, "null handle");
     if (h->rw_n_ref < 0) return fail(GEMX_ERR_ARG, "no reward function installed (gemx_set_reward)");
     if (!reward_out_dev || (h->rw_n_ref > 0 && !refs_dev)) return fail(GEMX_ERR_ARG, "refs_dev and reward_out_dev must not be null");
-    h->cur_refs = refs_dev;
-    h->cur_reward = reward_out_dev;
-    const int rc = gemx_rollout(h, actions_dev, K, obs_out_dev, done_out_dev, 1, stream);
-    h->cur_refs = nullptr;
-    h->cur_reward = nullptr;
-    return rc;
+    RolloutCall call;
+    call.actions = actions_dev; call.K = K; call.obs = obs_out_dev; call.done = done_out_dev;
+    call.refs = refs_dev; call.reward = reward_out_dev;
+    return rollout_checked(h, call, stream);
 }
 
 int gemx_step(gemx_handle *h, const void *actions_dev, void *obs_out_dev, uint8_t *done_out_dev, void *stream) {
@@ -1111,9 +1099,7 @@ int gemx_set_state(gemx_handle *h, const void *soa_in_dev, void *stream) {
                            (const float *)soa_in_dev, h->n, h->nd, h->has_angle);
     HIP_TRY(hipGetLastError());
     h->omega_is_init = false;  // (dc_stream_kernel assumes omega == init[0]; the next full reset restores that)
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &capturing);
-    if (capturing != hipStreamCaptureStatusNone) h->omega_unknown = true;  // replayed at times the host cannot know
+    if (gemx::stream_capturing(st)) h->omega_unknown = true;  // replayed at times the host cannot know
     return GEMX_OK;
 }
 int gemx_get_switch_state(gemx_handle *h, uint8_t *out_dev, void *stream) {

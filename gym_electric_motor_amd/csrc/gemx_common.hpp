@@ -567,12 +567,6 @@ struct gemx_handle {
     gemx::RewardHot<float> rh_f = {};   // its first terms by value (kernel argument)
     gemx::RewardHot<double> rh_d = {};
     int rw_n_ref = -1;       // -1: no reward installed
-    bool cur_half = false;           // set by gemx_rollout_half around the launch: the action tensor holds IEEE halves
-    bool cur_synth = false;          // set by gemx_rollout_synthetic around the launch: actions come from synth_u32(cur_seed, env, cur_step0 + k, i)
-    uint64_t cur_seed = 0;
-    uint32_t cur_step0 = 0;
-    const void *cur_refs = nullptr;  // set by gemx_rollout_reward around the launch
-    void *cur_reward = nullptr;
     void *ring = nullptr;    // DeadTimeProcessor FIFO [delay][n][nact_conv] R | [delay][n] uint8
     size_t ring_bytes = 0;
     int nact_conv = 1;       // converter-side action width (== nact unless a dq action frame is configured)
@@ -644,8 +638,30 @@ template <> inline const DevParams<double> &params_of<double>(const gemx_handle 
 
 int fail(int code, const char *fmt, ...);  // sets gemx_last_error(); defined in gemx_capi.hip
 
-// one launcher per (system, converter, dtype) instantiation unit; dispatches on load / solver / interlocking
-typedef int (*advance_fn)(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st);
+// What one launch of K control steps is given (gemx_step / gemx_rollout and its reward, half and synthetic forms fill one; the handle
+// carries nothing of a call).
+struct RolloutCall {
+    const void *actions = nullptr;  // [K][N][A] R | [K][N] uint8 | [K][N][A] IEEE half (`half`) | not read (`synth`)
+    int K = 1;
+    void *obs = nullptr;            // [K][N][NOUT], or one step's rows if !obs_every
+    uint8_t *done = nullptr;        // [K][N] | [N]; may be null
+    int obs_every = 1;
+    const void *refs = nullptr;     // fused reward (gemx_rollout_reward): references [K][N][n_ref] ...
+    void *reward = nullptr;         //   ... and the output [K][N]; nullptr: no reward in this launch
+    bool half = false;              // gemx_rollout_half: the action tensor holds IEEE halves
+    bool synth = false;             // gemx_rollout_synthetic: actions come from synth_u32(seed, env, step0 + k, i)
+    uint64_t seed = 0;
+    uint32_t step0 = 0;
+};
+// one launcher per (system, converter, dtype) instantiation unit (gemx_unit_launch); dispatches on load / solver / interlocking
+typedef int (*advance_fn)(gemx_handle *h, const RolloutCall &call, hipStream_t st);
+
+// true while `st` is being captured into a graph: what is enqueued now runs later, any number of times
+inline bool stream_capturing(hipStream_t st) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(st, &capturing);
+    return capturing != hipStreamCaptureStatusNone;
+}
 }  // namespace gemx
 
 namespace gemx {

@@ -206,17 +206,18 @@ __global__ __launch_bounds__(BLOCK) void envparams_rollout_kernel(const KArgs<R>
 // host launcher
 // ------------------------------------------------------------------------------------------------
 template <int SYS, int CONV, int LOAD, int SOLVER>
-static int launch_ep_t(gemx_handle *h, const float *tab, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
+static int launch_ep_t(gemx_handle *h, const float *tab, const RolloutCall &c, hipStream_t st) {
     using R = float;
+    const int K = c.K;
     KArgs<R> a;
-    fill_unit_kargs<LOAD>(a, h, true, K, obs, done);
-    a.actions = (const unsigned char *)actions;
-    a.rw = h->cur_reward != nullptr ? (const RewardDev<R> *)h->rw_dev : nullptr;
+    fill_unit_kargs<LOAD>(a, h, true, K, c.obs, c.done);
+    a.actions = (const unsigned char *)c.actions;
+    a.rw = c.reward != nullptr ? (const RewardDev<R> *)h->rw_dev : nullptr;
     a.rh = h->rh_f;
-    a.refs = (const R *)h->cur_refs;
-    a.reward = (R *)h->cur_reward;
+    a.refs = (const R *)c.refs;
+    a.reward = (R *)c.reward;
     const int64_t blocks = (h->n + BLOCK - 1) / BLOCK;
-    const bool step = K == 1 && h->cur_reward == nullptr;
+    const bool step = K == 1 && c.reward == nullptr;
     if (step) hipLaunchKernelGGL((envparams_step_kernel<SYS, CONV, LOAD, SOLVER, R>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a, tab);
     else hipLaunchKernelGGL((envparams_rollout_kernel<SYS, CONV, LOAD, SOLVER, R>), dim3((unsigned)blocks), dim3(BLOCK), 0, st, a, tab);
     GEMX_HIP_TRY(hipGetLastError());
@@ -225,9 +226,9 @@ static int launch_ep_t(gemx_handle *h, const float *tab, const void *actions, in
 }
 
 template <int SYS, int CONV>
-static int launch_ep_unit(gemx_handle *h, const void *tab, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
+static int launch_ep_unit(gemx_handle *h, const void *tab, const RolloutCall &c, hipStream_t st) {
     return dispatch_load_solver(h, "per-env parameters", [&](auto ls) {
-        return launch_ep_t<SYS, CONV, decltype(ls)::LOAD, decltype(ls)::SOLVER>(h, (const float *)tab, actions, K, obs, done, st);
+        return launch_ep_t<SYS, CONV, decltype(ls)::LOAD, decltype(ls)::SOLVER>(h, (const float *)tab, c, st);
     });
 }
 }  // namespace gemx
@@ -236,8 +237,8 @@ extern "C" {
 __attribute__((visibility("default"))) int gemx_ep_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
     return gemx::unit_init(handle_bytes, abi, set_error);
 }
-__attribute__((visibility("default"))) int gemx_ep_unit_launch(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st) {
+__attribute__((visibility("default"))) int gemx_ep_unit_launch(gemx_handle *h, const gemx::RolloutCall &call, hipStream_t st) {
     if (h->envp == nullptr || h->envp_fields != gemx::ep_fields(GEMX_INST_SYS)) return gemx::fail(GEMX_ERR_ARG, "internal: per-env parameter unit launched without its table");
-    return gemx::launch_ep_unit<GEMX_INST_SYS, GEMX_INST_CONV>(h, h->envp, actions, K, obs, done, st);
+    return gemx::launch_ep_unit<GEMX_INST_SYS, GEMX_INST_CONV>(h, h->envp, call, st);
 }
 }

@@ -34,7 +34,7 @@ constexpr int EP_LAUNCH_EPISODIC = 6;
 
 // a per-env unit, libgemx_ep<S>_<C>.so (fp32): gemx_ep_unit_init as gemx_unit_init; gemx_ep_unit_launch runs K >= 1 control steps of every env
 // with the parameters of the handle's table (gemx_handle::envp; K == 1 without a fused reward: envparams_step_kernel, else envparams_rollout_kernel), every step's row stored
-typedef int (*gemx_ep_unit_launch_fn)(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, hipStream_t st);
+typedef int (*gemx_ep_unit_launch_fn)(gemx_handle *h, const gemx::RolloutCall &call, hipStream_t st);
 
 // an episodic rollout unit, libgemx_tl<S>_<C>.so (fp32): gemx_tl_unit_init as gemx_unit_init; gemx_tl_unit_launch runs K >= 1 control steps
 // of every env with the episode time limit `max_steps` inside the launch (episodic_rollout_kernel): length [N] is read, never written;

@@ -22,7 +22,7 @@ extern "C" {
 __attribute__((visibility("default"))) int gemx_unit_init(unsigned long long handle_bytes, int abi, void (*set_error)(const char *)) {
     return gemx::unit_init(handle_bytes, abi, set_error);
 }
-__attribute__((visibility("default"))) int gemx_unit_launch(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st) {
-    return gemx::launch_advance_unit<GEMX_INST_SYS, GEMX_INST_CONV, gemx::InstReal>(h, actions, K, obs, done, obs_every, st);
+__attribute__((visibility("default"))) int gemx_unit_launch(gemx_handle *h, const gemx::RolloutCall &call, hipStream_t st) {
+    return gemx::launch_advance_unit<GEMX_INST_SYS, GEMX_INST_CONV, gemx::InstReal>(h, call, st);
 }
 }

@@ -24,6 +24,7 @@
 #include <cstdio>
 
 #include "gemx_common.hpp"
+#include "gemx_launch_plan.hpp"  // the host launcher's policy: which shape, how much LDS, the rate limiter
 
 namespace gemx {
 
@@ -2619,10 +2620,6 @@ __global__ __launch_bounds__(BLOCK) void step_kernel(const KArgs<R> a) {
 // ScipyOdeSolver() in two rounds instead of one: tools/vgpr_report.py, profiles/r04j_vgpr_report.md), and which side of it a kernel falls
 // on moves with every unrelated edit.  So the line is REQUESTED where the natural count is close to it (everything but the DFIM's rows and
 // the dead-time variants of the fixed DP5 step, which need 160-170: forcing those would spill into the step loop).
-// target of the large-batch rate limiter: chip-wide algorithmic GB/s (tools/microbench_rowpitch.hip, profiles/r04k_*; GEMX_PACE_GBPS overrides)
-#ifndef GEMX_PACE_DEFAULT_ON
-#define GEMX_PACE_DEFAULT_ON 1
-#endif
 // prepared draws per lane (FULL pipelined kernel, random initialisers): four; eight for the induction machines, whose episodes under random
 // initial states are short (a third of them a few steps) and whose draw takes the loader three to four passes -- with four entries 7.7 % of
 // the SCIM's resets found the queue empty and drew inline (round 5 A/B: +10 % for the SCIM, -5 to -15 % for the PMSM, hence per system)
@@ -4422,6 +4419,8 @@ template <int SYS, int CONV, int LOAD, int SOLVER, bool IL, class R> inline void
 // ------------------------------------------------------------------------------------------------
 // host launcher
 // ------------------------------------------------------------------------------------------------
+// (gemx_unit_host.hpp, which every unit includes behind this header)
+template <int SYS, int LOAD, int SOLVER, bool IL, class R> static int ensure_linmap(gemx_handle *h, hipStream_t st, int *linmap_built);
 // I/O block depth S (control steps staged in LDS between global-memory bursts): as deep as the LDS allows for the
 // number of workgroups that should be co-resident per CU, capped by the per-lane action-prefetch registers.
 inline int choose_steps_per_block(const gemx_handle *h, int K, int es, int abytes, int max_wg_per_cu = 16) {
@@ -4449,7 +4448,10 @@ inline int choose_steps_per_block(const gemx_handle *h, int K, int es, int abyte
 }
 
 template <int SYS, int CONV, int LOAD, int SOLVER, bool IL, class R>
-int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st) {
+int launch_advance_t(gemx_handle *h, const RolloutCall &c, hipStream_t st) {
+    const void *actions = c.actions;
+    uint8_t *done = c.done;
+    const int K = c.K, obs_every = c.obs_every;
     constexpr int ABYTES = ConvTraits<CONV>::DISCRETE ? 1 : ConvTraits<CONV>::NACT * (int)sizeof(R);
     KArgs<R> a;
     a.P = params_of<R>(h);
@@ -4457,54 +4459,32 @@ int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint
     a.angle = (typename Angle<R>::T *)h->angle;
     a.sw = h->sw;
     a.actions = (const unsigned char *)actions;
-    a.act_synth = h->cur_synth ? 1 : 0;
-    a.act_seed = h->cur_seed;
+    a.act_synth = c.synth ? 1 : 0;
+    a.act_seed = c.seed;
     a.act_env_base = h->cfg.env_base;
-    a.act_half = h->cur_half ? 1 : 0;
+    a.act_half = c.half ? 1 : 0;
 #ifdef GEMX_PREP_PHASES
     a.prep_phases = GEMX_PREP_PHASES;
 #else
     a.prep_phases = ((SYS == GEMX_SYS_SCIM || SYS == GEMX_SYS_DFIM) && (h->n + BLOCK - 1) / BLOCK <= (int64_t)h->n_cu) ? 2 : 1;
 #endif
-    a.act_step0 = h->cur_step0;
-    a.obs = (R *)obs;
+    a.act_step0 = c.step0;
+    a.obs = (R *)c.obs;
     a.done = done;
     a.ring = (unsigned char *)h->ring;
     const int delay = h->cfg.action_delay;
     a.fifo_phase = h->fifo_phase;
     a.err = h->err;
-    if (h->linmap_state == 0) {  // once per handle: the electrical subsystem's one-step map (constant-speed loads)
-        // (random initialisers that draw OMEGA per episode keep the stage-by-stage solver.  Round 5: only those -- a random MOTOR initialiser
-        // beside a constant-speed load leaves omega at init[0], the map stays valid, and the kernels check every lane's omega at launch
-        // anyway (lin_usable); until then every random-initialiser handle ran the full Runge-Kutta stages, 2.2 x the integrator time)
-        if constexpr (linable<SYS, LOAD, SOLVER, IL, R>()) {
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(st, &capturing);
-            const bool omega_drawn = h->cfg.init_kind != GEMX_INIT_CONST && h->cfg.init_lo[0] < h->cfg.init_hi[0];
-            if (omega_drawn || (h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) || h->cfg.solver_nsteps != 1) {  // (error control, sub-steps: stage by stage)
-                h->linmap_state = -1;
-            } else if (capturing == hipStreamCaptureStatusNone) {
-                // built and COMPLETED here, so that later launches on any stream (or from a captured graph) find it; a first launch
-                // that is itself being captured into a graph goes without the map and leaves the attempt to the next eager launch
-                hipLaunchKernelGGL((linmap_kernel<SYS, SOLVER, R>), dim3(1), dim3(64), 0, st, params_of<double>(h), (R *)h->linmap_dev);
-                GEMX_HIP_TRY(hipGetLastError());
-                GEMX_HIP_TRY(hipStreamSynchronize(st));
-                h->linmap_state = 1;
-                h->pf.lin_on = 1;
-            }
-        } else {
-            h->linmap_state = -1;
-        }
-    }
+    if (const int rc = ensure_linmap<SYS, LOAD, SOLVER, IL, R>(h, st, nullptr)) return rc;  // once per handle: the one-step map (gemx_unit_host.hpp)
     a.P = params_of<R>(h);
     a.P.errw = h->err;
     a.rinit = (const InitDev *)h->rinit_dev;
     a.rcnt = h->rcnt;
-    a.rw = h->cur_reward != nullptr ? (const RewardDev<R> *)h->rw_dev : nullptr;
+    a.rw = c.reward != nullptr ? (const RewardDev<R> *)h->rw_dev : nullptr;
     if constexpr (sizeof(R) == 4) a.rh = h->rh_f;
     else a.rh = h->rh_d;
-    a.refs = (const R *)h->cur_refs;
-    a.reward = (R *)h->cur_reward;
+    a.refs = (const R *)c.refs;
+    a.reward = (R *)c.reward;
     a.N = h->n;
     a.K = K;
     a.obs_every = obs_every;
@@ -4545,7 +4525,7 @@ int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint
     // PermExDc, us per 1000 steps at 4096 / 8192 / 12288 / 16384 envs: 39 / 41 / 88 / 94 against 71 / 72 / 72 / 72; tools/ab_dc_stream.py)
     if constexpr (sizeof(R) == 4 && LOAD == GEMX_LOAD_CONST_SPEED && !IL &&
                   (SYS == GEMX_SYS_DC_PERMEX || SYS == GEMX_SYS_DC_SERIES || SYS == GEMX_SYS_DC_SHUNT || SYS == GEMX_SYS_DC_EXTEX)) {
-        bool dcs_ok = pipe_ok && fast_step && !h->cur_synth && !h->cur_half && (h->n % BLOCK) == 0 && a.coop && a.obs_vec && h->use_dc_stream != 0 && !need_full && delay == 0 && !(h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) && h->cur_reward == nullptr && (h->omega_is_init || h->use_dc_stream >= 3) &&
+        bool dcs_ok = pipe_ok && fast_step && !c.synth && !c.half && (h->n % BLOCK) == 0 && a.coop && a.obs_vec && h->use_dc_stream != 0 && !need_full && delay == 0 && !(h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) && c.reward == nullptr && (h->omega_is_init || h->use_dc_stream >= 3) &&
                       params_of<R>(h).obs_layout == GEMX_OBS_AOS && params_of<R>(h).t_il == R(0) &&
                       (h->use_dc_stream > 1 || 2 * blocks <= (int64_t)h->n_cu) && dcs_smem_bytes<SYS, CONV>() <= h->lds_max &&
                       (int64_t)h->n * h->nout * 64 < ((int64_t)1 << 31);  // (SIGNED 32-bit store offsets: lane offsets across the rows of a (double)
@@ -4555,9 +4535,7 @@ int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint
         if (dcs_ok) {
             // never into a graph: `omega_is_init` is what the host knows NOW, a captured launch runs later, possibly behind a gemx_set_state.
             // The pipelined kernel decides on the device (lin_usable), so it is what a graph gets.
-            hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing(st, &capturing);
-            dcs_ok = capturing == hipStreamCaptureStatusNone;
+            dcs_ok = !stream_capturing(st);
         }
         if (dcs_ok) {
             // 32 envs per workgroup -- twice the workgroups and CUs for the same batch, half the store instructions per CU -- whenever they
@@ -4585,304 +4563,45 @@ int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint
         }
     }
     if constexpr (sizeof(R) == 4) if (pipe_ok) {
+        // the compile-time numbers of this instantiation; which shape, how much LDS and the rate limiter's intervals: gemx_launch_plan.hpp
         using ST = Stepper<SYS, conv_base<CONV>(), LOAD, SOLVER, IL, R>;
-        const int NHT = SysTraits<SYS>::ND + (SysTraits<SYS>::HAS_ANGLE ? 1 : 0) + ST::NH + 1 + (need_full ? 1 : 0);
-        // LDS footprint of one workgroup at hand-off depth D (steps per barrier): ring + done ring + double-buffered hand-off rows + ...
-        auto smem_of = [&](int D) {
-            size_t b = (size_t)D * BLOCK * h->nout * sizeof(R) + (size_t)D * BLOCK + 2 * (size_t)D * BLOCK * NHT * sizeof(R);
-            b += (size_t)pipe_queue_rows(D, delay, conv_dq<CONV>() && h->pf.dq_processor != 0, need_full) * BLOCK * conv_nact_c<CONV>() * sizeof(R);  // DeadTimeProcessor queue
-            b += pipe_act_bufs(D) * (size_t)((D + 3) / 4 * 4) * BLOCK * ABYTES;  // action staging (global -> LDS direct, one or two blocks ahead)
-            if (h->cur_reward != nullptr) b += pipe_ref_bufs(D) * (size_t)D * BLOCK * h->rw_n_ref * sizeof(R);  // reference staging for the fused reward
-            if (ST::NVT > 0 && ConvTraits<CONV>::DISCRETE) b += (size_t)ConvTraits<CONV>::NACTIONS * 8 * sizeof(R);  // per-action voltage table
-            if (h->cfg.init_kind != GEMX_INIT_CONST) b += (size_t)(prep_q<SYS>() * 8 + 1) * BLOCK * sizeof(uint32_t) + ((sizeof(InitDev) + 15) & ~(size_t)15);  // prepared draws (random initialisers) + the description
-            return (b + 15) & ~(size_t)15;
-        };
-        // workgroups of a shape one CU holds: LDS, wave slots -- and REGISTERS (round 4: the arithmetic used to stop at the first two and
-        // took four resident workgroups of a shallow shape for granted; a kernel at 129-136 VGPRs holds three, and a "one round" rule that
-        // does not know runs a round plus a tail.  hipFuncGetAttributes once per handle and shape.)
-        auto regs_limit = [&](int shape_, int waves_per_wg) -> int64_t {
-            if (h->pipe_regs[shape_] == 0) {
-                const void *kp = (const void *)pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(shape_);
-                if (kp == nullptr) return 0;  // (a shape that is not built holds no workgroup)
-                hipFuncAttributes fa;
-                h->pipe_regs[shape_] = (hipFuncGetAttributes(&fa, kp) == hipSuccess && fa.numRegs > 0) ? fa.numRegs : 128;
-            }
-            int waves_per_simd = 512 / ((h->pipe_regs[shape_] + 7) & ~7);  // gfx950: 512 VGPRs per SIMD lane, allocation granule 8
-            if (waves_per_simd < 1) waves_per_simd = 1;
-            if (waves_per_simd > 8) waves_per_simd = 8;
-            return (int64_t)(4 * waves_per_simd) / waves_per_wg;
-        };
-        // ... and what the runtime itself says a CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor with this launch's LDS bytes, once
-        // per handle and shape): the rate limiter below prices every workgroup's interval with the number of workgroups that are
-        // RUNNING, and the PermExDc <4, 2> kernel, eight per CU by LDS, wave slots and registers, runs five (r04m: 98304 envs paced for
-        // 1536 concurrent workgroups with ~1280 resident ran 0.54 of the roofline against 0.90 at 65536)
-        auto occ_limit = [&](int shape_, int threads, size_t smem_b) -> int64_t {
-            if (h->pipe_occ[shape_] == 0 || h->pipe_occ_smem[shape_] != smem_b) {  // (the LDS bytes move with the fused reward / the queue depth)
-                const void *kp = (const void *)pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(shape_);
-                if (kp == nullptr) return 0;  // (a shape that is not built holds no workgroup)
-                int nb_ = 0;
-                h->pipe_occ_smem[shape_] = smem_b;
-                if (!(h->pipe_attr_set & (1u << shape_))) {  // (the bit only on success: the launch path then repeats the call, checked, and reports the error)
-                    if (hipFuncSetAttribute(kp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_max) == hipSuccess) h->pipe_attr_set |= 1u << shape_;
-                    else (void)hipGetLastError();
-                }
-                h->pipe_occ[shape_] = (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb_, kp, threads, smem_b) == hipSuccess && nb_ > 0) ? nb_ : 64;
-                (void)hipGetLastError();
-            }
-            return (int64_t)h->pipe_occ[shape_];
-        };
-        auto resident = [&](int D, int OW, int shape_full = -1) {  // (shape_full: one of the FULL / SLOW instantiations of <4, 2>, shapes 4-7)
-            int64_t w = (int64_t)(h->lds_max / smem_of(D));
-            const int waves_per_wg = 1 + OW + pipe_loader_waves(D);
-            const int64_t wmax = 32 / waves_per_wg;
-            const int shape_ = shape_full >= 0 ? shape_full : (D == PIPE_D ? (OW == PIPE_OUT_WAVES ? 0 : 3) : (D == PIPE_D2 ? 1 : 2));
-            const int64_t wreg = regs_limit(shape_, waves_per_wg);
-            w = w > wmax ? wmax : w;
-            w = w > wreg ? wreg : w;
-            if (smem_of(D) <= h->lds_max) {
-                const int64_t wocc = occ_limit(shape_, waves_per_wg * BLOCK, smem_of(D));
-                w = w > wocc ? wocc : w;
-            }
-            if (wreg == 0) return (int64_t)0;  // not built (pipe_deep_built)
-            return (w < 1 ? 1 : w) * (int64_t)h->n_cu;
-        };
-        // one resident round of the 4-wave shape if N is that small, else the 3-wave shape at ANY N: measured at 131072 and 1048576
-        // envs over all motor families (profiles/r01d_matrix.md) it is on par with or ahead of the single-wave kernel (PMSM
-        // 1M envs: 100 vs 86 G env-steps/s) -- the split keeps stores fire-and-forget and the integrator free of vmcnt waits
-        int D = 0, OW = 0, shape = 0;
-        // six output waves (eight waves in all: still one workgroup per CU) where the output side carries more than three waves keep up
-        // with: the fused reward, and the COMPACT hand-off rows of the synchronous machines behind a finite converter (advance_pipe_kernel,
-        // COMPACT_K: the integrator is 8 % faster per block there, 3555 against 3875 cycles, and the output waves look the phase voltages
-        // up themselves -- three of them need 4100 cycles per block, six 2500; PMSM headline 147.6 -> 140 us per launch)
-        constexpr bool COMPACT_L = SYS == GEMX_SYS_SYNC && ST::NVT > 0 && ConvTraits<CONV>::DISCRETE && linable<SYS, LOAD, SOLVER, IL, R>();
-        const bool compact_l = COMPACT_L && h->pf.lin_on != 0 && !need_full;
-        // ... and with those rows the deep shape is ahead of <4, 2> at ANY N whose workgroups fill its rounds of one workgroup per CU: same box,
-        // PMSM finite, of the roofline at 28672 / 32768 / 49152 / 65536 / 131072 envs: 0.71 / 0.72 / 0.70 / 0.77 / 0.79 against 0.68 / 0.68 / 0.67 /
-        // 0.65 / 0.70 (profiles/r03s_shapes_compact.md); a last round less than ~85 % full loses instead (24576 envs: 0.59 against 0.65)
-        // -- and a launch too short to amortise a workgroup's ~10 us outside its block loop, which <4, 2>'s four co-resident workgroups overlap
-        // (1M envs x 100 steps: 0.53 against 0.68): K >= 400
-        bool deep_rounds = false;
-        // (not behind a DeadTimeProcessor: its delayed-read blocks are slower in the deep shape than <4, 2>'s queue: 131072 envs 0.57 against 0.69)
-        // (nor with the fused reward, whose output waves are the bound at large N either way: 131072 envs 0.56 against 0.60)
-        // (round 4: only while the rate limiter is OFF.  With it the shallow shapes hold 0.79 at every size from 32768 envs on, the deep shape in
-        // rounds 0.64-0.77: profiles/r04m_pace_shapes.txt)
-        const bool pacing_on = (h->pace_gbps < 0.0 ? GEMX_PACE_DEFAULT_ON != 0 : h->pace_gbps > 0.0) && K >= 64;
-        if (pipe_deep_built<SYS, SOLVER, IL>() && compact_l && !pacing_on && K >= 400 && delay == 0 && h->cur_reward == nullptr && smem_of(PIPE_D) <= h->lds_max) {
-            const int64_t res0 = resident(PIPE_D, PIPE_OUT_WAVES_RW), rounds = (blocks + res0 - 1) / res0;
-            deep_rounds = blocks > res0 && 100 * blocks >= 85 * rounds * res0;
-        }
-        // (limiter on: the deep shape up to TWO workgroups per CU -- at three, 49152 envs, the DC machines it fits run 0.76 / 0.59 / 0.33 (PermExDc /
-        // ShuntDc / SeriesDc SC) against 0.86 / 0.85 / 0.60 through <4, 2> under the limiter: profiles/r04p_shape_32768.txt)
-        // LONG launches at one workgroup per CU lose their rate as well: the headline holds 0.80-0.83 of the roofline up to 1000 steps per launch,
-        // 0.75 at 2000, 0.70 at 3000, 0.68 at 6000 -- workgroups that start in the same phase drift apart, and the stores of a CU's neighbours
-        // stop landing in the same DRAM rows.  The limiter is also a clock that keeps them together: the same launches through <12, 3> at
-        // the 32768-env target run 0.83 / 0.84 at 3000 / 6000 steps (PMSM cont 0.69 / 0.70 -> 0.77 / 0.79; profiles/r04r_probe5.txt).  Only the
-        // rows whose integrator is faster than the target gain (the synchronous machines on the one-step map); an integrator-bound
-        // row pays 3-6 % for the clock reads (SCIM finite 0.66 -> 0.62, ShuntDc 0.54 -> 0.52) and keeps its unpaced launch.  From 1200 steps on: at
-        // 1000 the unpaced <12, 6> is ahead (0.84 against 0.81), at 1400 behind (0.77 against 0.81-0.83: profiles/r04q_probe3.txt A, r04r_probe5.txt).
-        const bool long_one = pacing_on && h->pace_gbps < 0.0 && K >= 1200 && SYS == GEMX_SYS_SYNC && h->pf.lin_on != 0 && !need_full && h->cur_reward == nullptr &&
-                              blocks <= (int64_t)h->n_cu;
-        const int64_t deep_max = pacing_on && resident(PIPE_D, PIPE_OUT_WAVES) > 2 * (int64_t)h->n_cu ? 2 * (int64_t)h->n_cu : resident(PIPE_D, PIPE_OUT_WAVES);
-        if (pipe_deep_built<SYS, SOLVER, IL>() && smem_of(PIPE_D) <= h->lds_max && (blocks <= deep_max || deep_rounds)) {
-            D = PIPE_D; OW = PIPE_OUT_WAVES; shape = 0;
-            // (long launches of the synchronous machines' one-step-map rows: <12, 3>, which carries the rate limiter -- see `long_one` below)
-            if (h->cur_reward != nullptr || (compact_l && !long_one)) { OW = PIPE_OUT_WAVES_RW; shape = 3; }
-        }
-        else if (pipe_d3_built<SOLVER, IL>() && smem_of(PIPE_D3) <= h->lds_max && blocks <= resident(PIPE_D3, PIPE_OUT_WAVES3) &&
-                 blocks > resident(PIPE_D2, PIPE_OUT_WAVES2) && 2 * blocks <= 3 * resident(PIPE_D2, PIPE_OUT_WAVES2)) {
-            // (round 4: EVERY system.  Rounds 2-3 kept this to the induction machines on one sample -- ExtExDc at 131072 envs, which is not
-            // this case at all (two full rounds of <4, 2>) -- but where <4, 2> runs a round plus a tail of at most half a round and <2, 2>
-            // fits everything into one, the interleaved same-box A/B (tools/ab_matrix_shapes.py, profiles/r04c_shapes_ab.md, 65536 envs,
-            // of the roofline) has it ahead almost everywhere: PMSM cont 0.57 -> 0.71, PMSM cont SC 0.50 -> 0.69, ShuntDc 0.61 -> 0.73,
-            // EESM 0.57 -> 0.64 / 0.56 -> 0.61, DqToAbc + DeadTime 0.59 -> 0.75, PermExDc 0.78 -> 0.85, fused reward 0.56 -> 0.62;
-            // level: SeriesDc SC, ExtExDc.)
-            // (induction machines only: lighter steppers lose with the shallow shape -- ExtExDc 131072 envs 133 -> 104 G; PMSM finite at
-            // 98304 envs, where this rule used to apply: 75.8 G against 84.2 G through <4, 2>, profiles/r03k_shapes_pmsm.md)
-            // one resident round with the shallow shape where <4, 2> would run one round plus a tail of at most half a round: SCIM,
-            // 65536 envs (BASELINE config 4) 49 -> 67 G env-steps/s.  Everywhere else <4, 2> is 5-20 % ahead of <2, 2> (fewer barriers,
-            // fewer waves per SIMD): PMSM finite at 131072 envs = two FULL rounds of <4, 2>: 89-92 G against 79 G in one round of <2, 2>
-            D = PIPE_D3; OW = PIPE_OUT_WAVES3; shape = 2;
-        } else if (smem_of(PIPE_D2) <= h->lds_max) { D = PIPE_D2; OW = PIPE_OUT_WAVES2; shape = 1; }
-        if (h->pipe_shape >= 0 && h->pipe_shape <= 3) {  // forced shape (tests)
-            const int fd[4] = {PIPE_D, PIPE_D2, PIPE_D3, PIPE_D}, fo[4] = {PIPE_OUT_WAVES, PIPE_OUT_WAVES2, PIPE_OUT_WAVES3, PIPE_OUT_WAVES_RW};
-            if (smem_of(fd[h->pipe_shape]) <= h->lds_max && pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(h->pipe_shape) != nullptr) { shape = h->pipe_shape; D = fd[shape]; OW = fo[shape]; }
-        }
-        if (need_full) {  // one instantiation serves these handles
-            // ~180 VGPRs = two resident workgroups per CU.  RC supply: ahead of the single-wave kernel at every size (PMSM finite, same box:
-            // 52 vs 14 G env-steps/s at 16384 envs, 89 vs 26 at 32768, 89 vs 47 at 65536).  Random initialisers (the fp64 draw sits in the
-            // integrator's reset path): ahead up to 32768 envs (28 vs 16), level at 65536, behind beyond (28 vs 43 at 131072) --
-            // tools/ab_full_variant.py
-            // Round 5: random initialisers have their own instantiation (RINIT) whose loader wave prepares the draws; same box, PMSM finite:
-            // 21 -> 54-57 G env-steps/s at 32768 / 65536 envs, and 57 against the single-wave kernel's 32 at 131072 -- the size rule
-            // ("at most four workgroups per CU") is gone (profiles/r05r_ab_prep.txt).
-            if (smem_of(PIPE_D2) <= h->lds_max) { D = PIPE_D2; OW = PIPE_OUT_WAVES2; shape = h->cfg.init_kind != GEMX_INIT_CONST ? 7 : 4; }
-            else D = 0;
-        }
-        if (!fast_step && D != 0) {  // solver sub-steps / a custom constraint set: the SLOW instantiations of <4, 2> (no limiter: integrator-bound)
-            if (smem_of(PIPE_D2) <= h->lds_max && h->cfg.init_kind == GEMX_INIT_CONST) { D = PIPE_D2; OW = PIPE_OUT_WAVES2; shape = 6; }
-            else D = 0;  // (together with random initialisers: the single-wave kernel)
-        }
-        if (D != 0) {
-            a.S = D;
-            a.D = D;
-            // the rate limiter (advance_pipe_kernel): only where the batch oversubscribes the write path -- more workgroups than CUs; at one
-            // workgroup per CU in one round the integrator's instruction stream is the pacing, and an s_memrealtime per block would only cost
-            // it time.  interval per row and workgroup = algorithmic bytes of a 64-env step x workgroups resident on the chip / target rate.
-            int64_t pace_res = 0;
-            int cal_slot = -1, cal_cand = 0;
-            double pace_scale_used = 1.0;
-            a.pace_block_ticks = 0;
-            a.pace_tail_ticks = 0;
-            a.pace_tail_from = 0xFFFFFFFFu;
-            {
-                // Target: a few per cent under the knee the sweeps over the real kernels found (profiles/r04l_pace_sweep.txt, r04n_pace_sweep2.txt;
-                // same box, of the 8 TB/s).  Under the limiter a launch runs at ~0.98 x target / 8000 up to the knee and collapses beyond it:
-                // rows of 14-24 values (3.5-6 KB per workgroup and step) at 32768 / 65536 / 131072 envs peak at 7000-7200 / 6800-7000 / 6400-6600
-                // GB/s (PMSM finite 0.65 / 0.66 / 0.65 unpaced -> 0.85 / 0.84 / 0.80 at the knee, 0.66 / 0.79 / 0.76 one step beyond it; SCIM,
-                // EESM, DFIM finite alike), the DC machines' 5-7 values (1.3-1.8 KB) at 7200-7600 / 7200 / 7000 (ShuntDc 0.62 / 0.61 / 0.65 ->
-                // 0.85 / 0.87 / 0.80).  The knee moves down with the number of workgroups in flight.  Kernels whose integrators offer less
-                // than the target (the speed-control rows, 16384 envs) never wait and are unchanged.
-                const bool few = blocks <= 2 * (int64_t)h->n_cu, some = blocks <= 4 * (int64_t)h->n_cu;
-                // Launches that also READ eight bytes or more per env-step (continuous duty cycles through the loader wave) have the knee lower and
-                // a softer landing beyond it (back to the unpaced level, not below): 65536 / 131072 envs PMSM cont 0.66 / 0.63 unpaced -> 0.68 / 0.63
-                // at 6000 / 5600, EESM cont 0.62 / 0.59 -> 0.73 / 0.66, DFIM cont 0.60 / 0.70 -> 0.72 / 0.69, control_space='dq' 0.62 / 0.62 -> 0.68 /
-                // 0.65, ExtExDc cont 0.72 / 0.64 -> 0.77 / 0.64 at 6400 (profiles/r04p_pace_sweep3.txt).
-                const int abytes_eff = h->cur_half ? ABYTES / 2 : ABYTES;  // (gemx_rollout_half: two bytes per value)
-                const bool reads = abytes_eff >= 8 && !h->cur_synth;  // (synthetic actions are generated in the launch: nothing is read)
-                const double dflt = h->nout <= 8 ? (reads ? (few ? 7000.0 : 6400.0) : (some ? 7000.0 : 6600.0))
-                                    : reads      ? (few ? 6400.0 : (some ? 6000.0 : 5800.0))
-                                                 : (few ? 6800.0 : (some ? 6600.0 : 6400.0));
-                double target = h->pace_gbps < 0.0 ? (GEMX_PACE_DEFAULT_ON ? dflt : 0.0) : h->pace_gbps;
-                // closed loop: which candidate this launch runs (gemx_handle::PaceCal)
-                constexpr double CAL_SCALE[gemx_handle::PaceCal::NC] = {1.0, 0.93, 1.07, 0.86, 0.0};  // (0: unpaced)
-                auto &pc = h->pcal;
-                cal_slot = -1;
-                const bool cal_eligible = h->pace_cal_on != 0 && h->pace_gbps < 0.0 && target > 0.0 && (blocks > (int64_t)h->n_cu || long_one) && K >= 64 && shape != 3 && shape < 5;
-                if (cal_eligible) {
-                    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-                    (void)hipStreamIsCapturing(st, &capturing);
-                    // (the interval per hand-off block does not depend on the launch's length: K enters only through its class -- short launches,
-                    // whose fixed costs weigh on the timings, and the long launches at one workgroup per CU, which pace a different shape.  A
-                    // training loop that varies K within a class keeps its calibration; round 5 keyed it by K itself and re-calibrated, up to 240
-                    // launches, at every change.)
-                    const int k_class = long_one ? 2 : (K < 256 ? 0 : 1);
-                    const long long sig = ((long long)k_class << 40) ^ ((long long)blocks << 8) ^ (long long)shape ^ (h->cur_reward != nullptr ? 0x80 : 0) ^ (h->cur_synth ? 0x40 : 0) ^ (h->cur_half ? 0x20 : 0);
-                    if (pc.sig != sig) {  // a new kind of launch: start over (events are kept)
-                        pc.sig = sig; pc.next = 0; pc.chosen = -1; pc.center = 1.0f; pc.recenters = 0;
-                        for (int c = 0; c < gemx_handle::PaceCal::NC; ++c) { pc.best[c] = 1e30f; pc.count[c] = 0; pc.issued[c] = 0; }
-                        if (pc.ev_init) for (int i = 0; i < gemx_handle::PaceCal::RING; ++i) pc.ev_cand[i] = -1;
-                    }
-                    if (pc.chosen < 0 && capturing == hipStreamCaptureStatusNone) {
-                        if (!pc.ev_init) {
-                            bool ok = true;
-                            for (int i = 0; i < gemx_handle::PaceCal::RING && ok; ++i) {
-                                ok = hipEventCreate((hipEvent_t *)&pc.ev0[i]) == hipSuccess && hipEventCreate((hipEvent_t *)&pc.ev1[i]) == hipSuccess;
-                                pc.ev_cand[i] = -1;
-                            }
-                            pc.ev_init = ok;
-                            if (!ok) { (void)hipGetLastError(); h->pace_cal_on = 0; }
-                        }
-                        if (pc.ev_init) {
-                            // harvest the pairs whose launches have finished (never blocks)
-                            for (int i = 0; i < gemx_handle::PaceCal::RING; ++i) {
-                                if (pc.ev_cand[i] < 0 || hipEventQuery((hipEvent_t)pc.ev1[i]) != hipSuccess) continue;
-                                float ms = 0.0f;
-                                if (hipEventElapsedTime(&ms, (hipEvent_t)pc.ev0[i], (hipEvent_t)pc.ev1[i]) == hipSuccess && ms > 0.0f) {
-                                    const int c = pc.ev_cand[i];
-                                    pc.best[c] = ms < pc.best[c] ? ms : pc.best[c];
-                                    pc.count[c]++;
-                                }
-                                pc.ev_cand[i] = -1;
-                            }
-                            (void)hipGetLastError();
-                            bool done_cal = true;
-                            for (int c = 0; c < gemx_handle::PaceCal::NC; ++c) done_cal &= pc.count[c] >= gemx_handle::PaceCal::SAMPLES;
-                            if (done_cal) {
-                                int bi = 0;
-                                for (int c = 1; c < gemx_handle::PaceCal::NC; ++c) if (pc.best[c] < pc.best[bi]) bi = c;
-                                // (a candidate must beat the starting point by more than 1 % to replace it: timing noise)
-                                const int win = pc.best[bi] < 0.99f * pc.best[0] ? bi : 0;
-                                // the winner at an EDGE of the bracket (x 1.07 or x 0.86): the optimum may lie beyond -- move the bracket there
-                                // and calibrate again (the built-in targets are one box's knees; a launch that reads nothing, e.g. with
-                                // synthetic actions, peaks well above them)
-                                if ((win == 2 || win == 3) && pc.recenters < gemx_handle::PaceCal::MAX_RECENTER) {
-                                    pc.center *= (float)CAL_SCALE[win];
-                                    pc.recenters++;
-                                    for (int c = 0; c < gemx_handle::PaceCal::NC; ++c) { pc.best[c] = 1e30f; pc.count[c] = 0; pc.issued[c] = 0; }
-                                    // (pairs still in flight were timed at the OLD centre: they must not be harvested into the new bracket --
-                                    // best[] keeps the minimum, one stale fast sample could pick the wrong candidate for good; advisor, round 5)
-                                    for (int i = 0; i < gemx_handle::PaceCal::RING; ++i) pc.ev_cand[i] = -1;
-                                } else {
-                                    pc.chosen = win;
-                                }
-                            } else {
-                                for (int i = 0; i < gemx_handle::PaceCal::RING; ++i)
-                                    if (pc.ev_cand[i] < 0) { cal_slot = i; break; }
-                                if (cal_slot >= 0) {  // (no free pair: this launch runs the starting point, untimed)
-                                    // the candidate handed out least often so far goes next (round robin, starting with the built-in target)
-                                    int c = 0;
-                                    for (int q = 1; q < gemx_handle::PaceCal::NC; ++q) if (pc.issued[q] < pc.issued[c]) c = q;
-                                    pc.issued[c]++;
-                                    pc.next++;
-                                    pc.ev_cand[cal_slot] = c;
-                                    cal_cand = c;
-                                }
-                            }
-                        }
-                    }
-                    const int use = pc.chosen >= 0 ? pc.chosen : (cal_slot >= 0 ? cal_cand : 0);
-                    target *= CAL_SCALE[use] * pc.center;
-                    pace_scale_used = CAL_SCALE[use] * pc.center;
-                }
-                // (round 5: the FULL instantiations are priced with their own registers and occupancy too -- without the draw code the RC-supply
-                // kernel went from 207 to 118 VGPRs, four workgroups per CU instead of the two that used to be written here)
-                int64_t res = shape >= 4 ? resident(D, OW, shape) : resident(D, OW);
-                // More than four workgroups per CU (the DC machines' small rows) and a launch that needs the LAST slot of every CU to be one round:
-                // count one slot less.  Registers, LDS, wave slots and the occupancy API said seven of the ShuntDc <4, 2> kernel; 114688 envs = 1792
-                // workgroups were priced as one round of 1792 -- and ran 0.41 of the roofline against 0.63 unpaced: whichever workgroups do not
-                // find their slot at once run alone afterwards at an interval meant for 1792.  Priced for six per CU they are a tail round,
-                // 0.64.  (Only in that band: at 131072 envs, one round of 1792 and a tail of 256, the seven slots price right -- 0.79 against 0.65
-                // with six; profiles/r04final_odd_sizes.txt, r04final_dc_residency.txt.)
-                if (res > 4 * (int64_t)h->n_cu && blocks <= res && blocks > res - (int64_t)h->n_cu) res -= (int64_t)h->n_cu;
-                pace_res = res;
-                if (target > 0.0 && (blocks > (int64_t)h->n_cu || h->pace_gbps > 0.0 || long_one) && K >= 64 && shape != 3 && shape < 5) {  // (<12, 6> carries no limiter: see the kernel; nor do the SLOW ones)
-                    const double wg_step_bytes = (double)BLOCK * ((h->cur_synth ? 0 : abytes_eff) + h->nout * sizeof(R) + 1 + (h->cur_reward != nullptr ? (h->rw_n_ref + 1) * sizeof(R) : 0));
-                    auto ticks_for = [&](double active) {
-                        const double t = wg_step_bytes * active / target * D / 10.0;  // bytes / (GB/s) = ns; 10 ns per tick; D rows per block
-                        return t < 1.0 ? 1u : (t > 4.0e9 ? 0u : (uint32_t)(t + 0.5));
-                    };
-                    const int64_t full = blocks / res, tail = blocks - full * res;
-                    a.pace_block_ticks = ticks_for((double)(blocks < res ? blocks : res));
-                    if (full >= 1 && tail > 0) {  // the last round: `tail` workgroups on the chip
-                        a.pace_tail_from = (uint32_t)(full * res);
-                        a.pace_tail_ticks = ticks_for((double)(tail < (int64_t)h->n_cu ? (int64_t)h->n_cu : tail));
-                    }
-                }
-            }
-            const size_t psmem = smem_of(D);
-            auto pkern = pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(shape);
-            if (pkern == nullptr) return fail(GEMX_ERR_ARG, "internal: pipelined shape %d is not built for this solver", shape);
-            if (!(h->pipe_attr_set & (1u << shape))) {
-                GEMX_HIP_TRY(hipFuncSetAttribute((const void *)pkern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_max));
-                h->pipe_attr_set |= 1u << shape;
-            }
-            const int threads = (1 + OW + pipe_loader_waves(D)) * BLOCK;
-            if (cal_slot >= 0) (void)hipEventRecord((hipEvent_t)h->pcal.ev0[cal_slot], st);
-            hipLaunchKernelGGL(pkern, dim3((unsigned)blocks), dim3(threads), psmem, st, a);
-            if (cal_slot >= 0 && hipEventRecord((hipEvent_t)h->pcal.ev1[cal_slot], st) != hipSuccess) { h->pcal.ev_cand[cal_slot] = -1; (void)hipGetLastError(); }
+        plan::Facts f = {};
+        f.abytes = ABYTES;
+        f.nht = SysTraits<SYS>::ND + (SysTraits<SYS>::HAS_ANGLE ? 1 : 0) + ST::NH + 1;
+        f.nact_c = conv_nact_c<CONV>();
+        f.vt_bytes = (ST::NVT > 0 && ConvTraits<CONV>::DISCRETE) ? ConvTraits<CONV>::NACTIONS * 8 * (int)sizeof(R) : 0;
+        f.prep_q = prep_q<SYS>();
+        f.init_desc_bytes = (int)((sizeof(InitDev) + 15) & ~(size_t)15);
+        f.dq = conv_dq<CONV>();
+        f.compact_l = SYS == GEMX_SYS_SYNC && ST::NVT > 0 && ConvTraits<CONV>::DISCRETE && linable<SYS, LOAD, SOLVER, IL, R>();
+        f.sync = SYS == GEMX_SYS_SYNC;
+        f.deep_built = pipe_deep_built<SYS, SOLVER, IL>();
+        f.d3_built = pipe_d3_built<SOLVER, IL>();
+        for (int s = 0; s < plan::NSHAPE; ++s) f.kernel[s] = (const void *)pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(s);
+        plan::Plan p;
+        if (const int rc = plan::plan_rollout(h, f, c, need_full, fast_step, st, p)) return rc;
+        if (p.D != 0) {
+            a.S = p.D;
+            a.D = p.D;
+            a.pace_block_ticks = p.pace.block_ticks;
+            a.pace_tail_ticks = p.pace.tail_ticks;
+            a.pace_tail_from = p.pace.tail_from;
+            plan::cal_begin(h, p, st);
+            hipLaunchKernelGGL((pipe_kernel_of<SYS, CONV, LOAD, SOLVER, IL, R>(p.shape)), dim3((unsigned)blocks), dim3(p.threads), p.lds, st, a);
+            plan::cal_end(h, p, st);
             GEMX_HIP_TRY(hipGetLastError());
-            h->pace_scale_last = pace_scale_used;
-            h->pace_cal_state = h->pcal.chosen >= 0 ? 2 : (cal_slot >= 0 ? 1 : 0);
-            h->ll = {1, SYS, CONV, LOAD, SOLVER, (int)IL, (int)sizeof(R), D, threads, K, D, (long long)blocks, psmem, a.pace_block_ticks, a.pace_tail_ticks, (long long)pace_res};
-            h->ll.shape = shape;
+            h->pace_scale_last = p.cal_scale;
+            h->pace_cal_state = p.cal_state;
+            h->ll = {1, SYS, CONV, LOAD, SOLVER, (int)IL, (int)sizeof(R), p.D, p.threads, K, p.D, (long long)blocks, p.lds, a.pace_block_ticks, a.pace_tail_ticks, (long long)p.pace.res};
+            h->ll.shape = p.shape;
             return GEMX_OK;
         }
     }
-    if (h->cur_half)
+    if (c.half)
         return fail(GEMX_ERR_ARG, "gemx_rollout_half needs the pipelined kernel: fp32, K >= 2, a continuous converter (and no random initial states together with solver sub-steps / a custom constraint set)");
-    if (h->cur_synth)  // (only the pipelined kernel's loader wave generates actions; gemx_synthetic_actions writes the same stream for any other path)
+    if (c.synth)  // (only the pipelined kernel's loader wave generates actions; gemx_synthetic_actions writes the same stream for any other path)
         return fail(GEMX_ERR_ARG, "gemx_rollout_synthetic needs the pipelined kernel: fp32, K >= 2 (and no random initial states together with solver sub-steps / a custom constraint set)");
-    if (K == 1 && h->cur_reward == nullptr && h->use_step_kernel != 0) {  // the closed-loop path: see step_kernel
+    if (K == 1 && c.reward == nullptr && h->use_step_kernel != 0) {  // the closed-loop path: see step_kernel
         // one launch per control step is bound by the HOST's launch path: the function handle is resolved once per handle and the
         // arguments go as one buffer -- 3.36 against 3.55 us per launch through hipLaunchKernelGGL (tools/microbench_launch.hip)
         if (h->step_fn == nullptr && !h->step_fn_failed) {
@@ -4923,7 +4642,7 @@ int launch_advance_t(gemx_handle *h, const void *actions, int K, void *obs, uint
 // run-time -> compile-time dispatch on (load, solver, interlocking) for one (system, converter, dtype) unit.
 // IL = false only exists for fp32 (the product path); the fp64 diagnostic build always takes the general code.
 template <int SYS, int CONV, class R>
-int launch_advance_unit(gemx_handle *h, const void *actions, int K, void *obs, uint8_t *done, int obs_every, hipStream_t st) {
+int launch_advance_unit(gemx_handle *h, const RolloutCall &c, hipStream_t st) {
     // (finite converters behind an RC supply need the leg states of the previous step for i_sup: the dead-time-free instantiation
     // keeps them too, from Stepper::legs_of -- so an RC supply no longer forces the slower IL code)
     const bool il = sizeof(R) == 8 || h->cfg.interlocking_time > 0.0;
@@ -4935,12 +4654,12 @@ int launch_advance_unit(gemx_handle *h, const void *actions, int K, void *obs, u
 #define GEMX_CASE(LD, SV)                                                                                                  \
     if constexpr (LD == GEMX_DEV_LOAD && SV == GEMX_DEV_SOLVER)                                                             \
         if (ld == LD && sv == SV && il == (GEMX_DEV_IL != 0))                                                              \
-            return launch_advance_t<SYS, CONV, LD, SV, GEMX_DEV_IL != 0, R>(h, actions, K, obs, done, obs_every, st);
+            return launch_advance_t<SYS, CONV, LD, SV, GEMX_DEV_IL != 0, R>(h, c, st);
 #else
 #define GEMX_CASE(LD, SV)                                                                                                  \
     if (ld == LD && sv == SV) {                                                                                            \
-        if constexpr (IL_BUILT) if (il) return launch_advance_t<SYS, CONV, LD, SV, true, R>(h, actions, K, obs, done, obs_every, st); \
-        if constexpr (sizeof(R) == 4) return launch_advance_t<SYS, CONV, LD, SV, false, R>(h, actions, K, obs, done, obs_every, st); \
+        if constexpr (IL_BUILT) if (il) return launch_advance_t<SYS, CONV, LD, SV, true, R>(h, c, st); \
+        if constexpr (sizeof(R) == 4) return launch_advance_t<SYS, CONV, LD, SV, false, R>(h, c, st); \
     }
 #endif
     GEMX_CASE(GEMX_LOAD_CONST_SPEED, GEMX_SOLVER_EULER)

@@ -3,9 +3,10 @@
 // libgemx.so, so each one carries its own copy of what stands here.  Host code only: no kernel and no device function.
 //   fail(), unit_init            the error sink and the body of every gemx_*_unit_init
 //   dispatch_load_solver         a side unit's four (load, solver) pairs -> its launcher template
-//   ensure_linmap                the once-per-handle build of the one-step map, as the episodic-family launchers do it
+//   ensure_linmap                the once-per-handle build of the one-step map: the stepping units' launch_advance_t and the
+//                                episodic-family launchers all call this one
 //   fill_unit_kargs              the KArgs of a single-wave side-unit launch
-// (gemx_kernels.hpp's own launch path, launch_advance_t, is not served from here.)
+// (How a fused rollout of the stepping units is launched -- shape, LDS, rate limiter -- is gemx_launch_plan.hpp's.)
 #pragma once
 #include <cstdarg>
 #include <cstdio>
@@ -42,17 +43,22 @@ template <class F> static int dispatch_load_solver(const gemx_handle *h, const c
     return fail(GEMX_ERR_ARG, "%s: load/solver combination %d/%d is not built (EulerSolver and RK4Solver only)", what, ld, sv);
 }
 
-// Once per handle, as launch_advance_t builds it: the electrical subsystem's one-step map, for a handle WITHOUT a parameter table (the map
-// is built for one parameter set).  Sub-steps go stage by stage; initial states are constant here.
-template <int SYS, int LOAD, int SOLVER> static int ensure_linmap(gemx_handle *h, hipStream_t st, int *linmap_built) {
-    using R = float;
+// Once per handle: the electrical subsystem's one-step map (constant-speed loads), for a handle WITHOUT a parameter table (the map is
+// built for one parameter set).  THE one place that builds it: launch_advance_t and the episodic-family launchers all come here (the side
+// units are fp32 without dead time, the defaults).
+// (random initialisers that draw OMEGA per episode keep the stage-by-stage solver.  Round 5: only those -- a random MOTOR initialiser
+// beside a constant-speed load leaves omega at init[0], the map stays valid, and the kernels check every lane's omega at launch
+// anyway (lin_usable); until then every random-initialiser handle ran the full Runge-Kutta stages, 2.2 x the integrator time)
+template <int SYS, int LOAD, int SOLVER, bool IL = false, class R = float> static int ensure_linmap(gemx_handle *h, hipStream_t st, int *linmap_built) {
     if (h->envp != nullptr || h->linmap_state != 0) return GEMX_OK;
-    if constexpr (linable<SYS, LOAD, SOLVER, false, R>()) {
-        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &capturing);
-        if ((h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) || h->cfg.solver_nsteps != 1) {
+    if constexpr (linable<SYS, LOAD, SOLVER, IL, R>()) {
+        const bool capturing = stream_capturing(st);
+        const bool omega_drawn = h->cfg.init_kind != GEMX_INIT_CONST && h->cfg.init_lo[0] < h->cfg.init_hi[0];
+        if (omega_drawn || (h->cfg.solver_flags & GEMX_SOLVER_ADAPTIVE) || h->cfg.solver_nsteps != 1) {  // (error control, sub-steps: stage by stage)
             h->linmap_state = -1;
-        } else if (capturing == hipStreamCaptureStatusNone) {  // (a first launch that is being captured goes without the map, as a stepped one does)
+        } else if (!capturing) {
+            // built and COMPLETED here, so that later launches on any stream (or from a captured graph) find it; a first launch
+            // that is itself being captured into a graph goes without the map and leaves the attempt to the next eager launch
             hipLaunchKernelGGL((linmap_kernel<SYS, SOLVER, R>), dim3(1), dim3(64), 0, st, params_of<double>(h), (R *)h->linmap_dev);
             GEMX_HIP_TRY(hipGetLastError());
             GEMX_HIP_TRY(hipStreamSynchronize(st));

@@ -41,7 +41,7 @@ def test_build_lists_one_episodic_unit_per_per_env_unit():
         assert os.path.basename(e) == f"libgemx_ep{s}_{c}.so" and os.path.basename(t) == f"libgemx_tl{s}_{c}.so"
         assert os.path.dirname(t) == os.path.dirname(build.LIB)  # (load_tl_unit looks beside libgemx.so)
     deps = build._DEPS["episodic"]
-    assert set(deps) == {"gemx_common.hpp", "gemx_reward.hpp", "gemx_kernels.hpp", "gemx_unit_host.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"}
+    assert set(deps) == {"gemx_common.hpp", "gemx_reward.hpp", "gemx_kernels.hpp", "gemx_launch_plan.hpp", "gemx_unit_host.hpp", "gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"}
     assert "gemx_envparams_dev.hpp" in build._DEPS["envparams"]  # the shared helpers: an edit recompiles both kinds of unit
     assert "gemx_envparams.hpp" in build._DEPS["capi"]  # (the launch kind and the unit's entry point type)
     names = {os.path.basename(p) for p in build.SOURCES}
