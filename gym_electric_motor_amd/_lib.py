@@ -274,6 +274,7 @@ EXPORTS = (
     "gemx_rollout_episodic",
     "gemx_policy_create", "gemx_policy_set_weights", "gemx_policy_destroy", "gemx_rollout_policy", "gemx_policy_tanh_probe",
     "gemx_rollout_policy_complete",
+    "gemx_rollout_lookahead_complete",
     "gemx_policy_eval_rows",
 )
 
@@ -383,6 +384,7 @@ def load():
     L.gemx_rollout_policy.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp]
     L.gemx_policy_tanh_probe.argtypes = [vp, vp, vp, i64, vp]
     L.gemx_rollout_policy_complete.argtypes = [vp, vp, C.POINTER(GemxPolicyCall), vp, vp, vp, vp]
+    L.gemx_rollout_lookahead_complete.argtypes = [vp, C.POINTER(GemxPolicyCall), vp, vp, vp, vp, vp, vp, vp]
     L.gemx_policy_eval_rows.argtypes = [vp, C.POINTER(GemxPolicyEvalCall), i64, i32, C.c_int, vp]
     L.gemx_get_state.argtypes = [vp, vp, vp]
     L.gemx_set_state.argtypes = [vp, vp, vp]

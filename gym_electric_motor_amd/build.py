@@ -36,8 +36,12 @@ Sources (gym_electric_motor_amd/csrc):
     gemx_policy_complete.hpp, gemx_policy_complete.hip   the policy rollout of the complete env: that kernel with the reference generators
                                         stepped in the lane, once per generator kind, compiled once per (system, converter unit), fp32, into
                                         libgemx_pc<S>_<C>.so, which the first gemx_rollout_policy_complete of such a handle loads with dlopen
+    gemx_lookahead.hpp, gemx_lookahead.hip   one-step finite-control-set predictive control: the episodic kernel with every switching action
+                                        tried one step ahead and scored with the env's reward, generators in the lane, compiled once per
+                                        (system, FINITE converter unit), fp32, into libgemx_la<S>_<C>.so, which the first
+                                        gemx_rollout_lookahead_complete of such a handle loads with dlopen
 The 38 units (19 system/converter pairs x fp32, fp64), the 19 per-env units, the 19 episodic units, the 19 policy units, the 19 complete policy
-units and the ten objects of libgemx.so are compiled in parallel.
+units, the 8 lookahead units and the ten objects of libgemx.so are compiled in parallel.
 """
 import concurrent.futures as cf
 import glob
@@ -59,7 +63,8 @@ SUPPORT = [("refgen", "gemx_refgen.hip", ["gemx_support.hpp"], 0.2), ("obsproc",
            ("policy_eval", "gemx_policy_eval.hip", ["gemx_support.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp"], 0.1)]
 SOURCES = [os.path.join(CSRC, f) for f in ["gemx_common.hpp", "gemx_reward.hpp", "gemx_kernels.hpp", "gemx_launch_plan.hpp", "gemx_unit_host.hpp", "gemx_inst.hip", "gemx_capi.hip", "gemx_support.hpp",
                                            "gemx_envparams.hpp", "gemx_envparams.hip", "gemx_envparams_dev.hpp", "gemx_episodic.hip", "gemx_policy.hpp", "gemx_policy.hip",
-                                           "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip"] + [u[1] for u in SUPPORT]]
+                                           "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_refgen_lane.hpp", "gemx_refprofile_lane.hpp", "gemx_policy_complete.hpp", "gemx_policy_complete.hip",
+                                           "gemx_lookahead.hpp", "gemx_lookahead.hip"] + [u[1] for u in SUPPORT]]
 HEADER = os.path.join(REPO, "include", "gemx.h")
 LIB = os.path.join(PKG_DIR, "libgemx.so")
 
@@ -84,6 +89,11 @@ def pc_unit_lib(s, c):
     return os.path.join(PKG_DIR, f"libgemx_pc{s}_{c}.so")
 
 
+def la_unit_lib(s, c):
+    """the shared object of one lookahead rollout unit (fp32, finite converters only; gemx_capi.hip's load_la_unit looks beside libgemx.so)"""
+    return os.path.join(PKG_DIR, f"libgemx_la{s}_{c}.so")
+
+
 def pl_unit_lib(s, c):
     """the shared object of one policy rollout unit (fp32 only; gemx_capi.hip's load_pl_unit looks beside libgemx.so)"""
     return os.path.join(PKG_DIR, f"libgemx_pl{s}_{c}.so")
@@ -94,6 +104,8 @@ STAMP = LIB + ".sha256"  # next to the library (the object directory does not tr
 
 # (system_kind, converter_kind) pairs on the accelerated path; each for fp32 (0) and fp64 (1)
 UNITS = [(0, 0), (1, 1), (1, 2), (2, 1), (2, 2), (0, 3), (3, 0), (3, 3), (4, 0), (4, 3), (5, 4), (5, 5), (6, 6), (6, 7), (7, 8), (7, 9), (1, 10), (2, 10), (6, 11)]
+FINITE_CONVERTERS = (1, 3, 5, 7, 9)  # GEMX_CONV_FINITE_*: the converter units with a finite action set (ConvTraits<...>::DISCRETE)
+LA_UNITS = [(s, c) for s, c in UNITS if c in FINITE_CONVERTERS]  # the lookahead units: a continuous converter has no action set to enumerate
 # --offload-compress: the gfx950 code objects are stored zstd-compressed in the shared objects (the HIP runtime inflates them when a library
 # is loaded): 144 MB of libraries -> ~20 MB pushed to every GPU lease, nothing else changes
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-fPIC", "-Wno-unused-variable", "--offload-compress"]
@@ -117,12 +129,13 @@ def _digest(sources=None, header=None):
 # what each kind of object is compiled from (an edit to the C ABI alone does not recompile the 38 kernel units)
 _COMMON = ["gemx_common.hpp", "gemx_reward.hpp"]  # every object (gemx_common.hpp includes gemx_reward.hpp)
 _UNIT = _COMMON + ["gemx_kernels.hpp", "gemx_launch_plan.hpp", "gemx_unit_host.hpp"]  # every dlopen'ed unit
-_DEPS = {"inst": _UNIT + ["gemx_inst.hip"], "capi": _COMMON + ["gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_capi.hip"],
+_DEPS = {"inst": _UNIT + ["gemx_inst.hip"], "capi": _COMMON + ["gemx_envparams.hpp"] + _PC_HEADERS + ["gemx_lookahead.hpp", "gemx_capi.hip"],
          "envparams": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_envparams.hip"],
          "episodic": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_episodic.hip"],
          "policy": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy.hpp", "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp", "gemx_policy.hip"],
          "policy_complete": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp", "gemx_policy_dev.hpp", "gemx_policy_kernel.hpp"] + _PC_HEADERS +
                             ["gemx_support.hpp", "gemx_refprofile.hip", "gemx_policy_complete.hip"],  # (gemx_refprofile.hip: its head section, the one definition of profile_row)
+         "lookahead": _UNIT + ["gemx_envparams.hpp", "gemx_envparams_dev.hpp"] + _PC_HEADERS + ["gemx_lookahead.hpp", "gemx_support.hpp", "gemx_refprofile.hip", "gemx_lookahead.hip"],
          **{name: _COMMON + headers + _LANE_HEADERS + [src] for name, src, headers, _ in SUPPORT}}
 # compile cost of an fp32 unit by system kind (object size, MB: induction > synchronous > DC); fp64 units take the single-wave kernel only
 _COST = {7: 6.0, 2: 5.3, 6: 4.9, 1: 4.5, 5: 4.0, 4: 3.9, 3: 3.5, 0: 3.5}
@@ -152,8 +165,13 @@ def pc_libs():
     return [pc_unit_lib(s, c) for s, c in UNITS]
 
 
+def la_libs():
+    """the lookahead rollout units (one per system/converter pair with a finite converter, fp32)"""
+    return [la_unit_lib(s, c) for s, c in LA_UNITS]
+
+
 def is_stale():
-    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs() + pl_libs() + pc_libs()):
+    if not os.path.exists(STAMP) or not all(os.path.exists(p) for p in all_libs() + ep_libs() + tl_libs() + pl_libs() + pc_libs() + la_libs()):
         return True
     return open(STAMP).read().strip() != _digest()
 
@@ -213,6 +231,10 @@ def _build_locked(hipcc, force, verbose, jobs):
         out = pc_unit_lib(s, c)
         cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
                                                   os.path.join(csrc, "gemx_policy_complete.hip"), "-o", out], "policy_complete", 0.2))
+    for s, c in LA_UNITS:  # the lookahead units: the episodic kernel around a rolled loop over the actions, once per generator kind
+        out = la_unit_lib(s, c)
+        cmds.append((out, [hipcc] + FLAGS + inc + [f"-DGEMX_INST_SYS={s}", f"-DGEMX_INST_CONV={c}", "-fvisibility=hidden", "-shared",
+                                                  os.path.join(csrc, "gemx_lookahead.hip"), "-o", out], "lookahead", 0.1))
     objects = []  # of libgemx.so
     for name, src, cost in [("capi", "gemx_capi.hip", 0.3)] + [(u[0], u[1], u[3]) for u in SUPPORT]:
         obj = os.path.join(OBJ_DIR, os.path.splitext(src)[0] + ".o")
@@ -238,7 +260,7 @@ def _build_locked(hipcc, force, verbose, jobs):
     with cf.ThreadPoolExecutor(max_workers=jobs) as ex:  # longest first: the big induction-machine units do not end up as the tail
         list(ex.map(compile_one, sorted(cmds, key=lambda j: -j[3])))
     run([hipcc, "--offload-arch=gfx950", "--offload-compress", "-shared", "-fPIC", "-o", LIB] + objects + ["-ldl"])
-    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pc*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
+    for stale in glob.glob(os.path.join(PKG_DIR, "libgemx_u*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_ep*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_tl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pl*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_pc*.so")) + glob.glob(os.path.join(PKG_DIR, "libgemx_la*.so")):  # a unit that is no longer in UNITS must not be found by dlopen
         if stale not in [j[0] for j in cmds]:
             os.remove(stale)
     with open(STAMP, "w") as fh:

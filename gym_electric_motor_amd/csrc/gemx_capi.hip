@@ -17,6 +17,7 @@
 #include "gemx_envparams.hpp"
 #include "gemx_policy.hpp"
 #include "gemx_policy_complete.hpp"
+#include "gemx_lookahead.hpp"
 
 namespace gemx {
 
@@ -1171,6 +1172,9 @@ static int load_pl_unit(int s, int c, gemx_pl_unit_launch_fn *out) { return load
 // ... and the complete policy rollout units, libgemx_pc<S>_<C>.so, by the first gemx_rollout_policy_complete
 extern "C++" { static SideUnitLib<gemx_pc_unit_launch_fn> g_pc_units[8][12]; }
 static int load_pc_unit(int s, int c, gemx_pc_unit_launch_fn *out) { return load_side_unit(g_pc_units, "pc", "complete policy rollout", "complete policy rollout", s, c, out); }
+// ... and the lookahead rollout units, libgemx_la<S>_<C>.so (finite converters only), by the first gemx_rollout_lookahead_complete
+extern "C++" { static SideUnitLib<gemx_la_unit_launch_fn> g_la_units[8][12]; }
+static int load_la_unit(int s, int c, gemx_la_unit_launch_fn *out) { return load_side_unit(g_la_units, "la", "lookahead rollout", "lookahead rollout", s, c, out); }
 
 int gemx_env_params_fields(const gemx_handle *h) { return h ? ep_fields(h->cfg.system_kind) : GEMX_ERR_ARG; }
 
@@ -1360,6 +1364,18 @@ int gemx_policy_destroy(gemx_policy *p) {
     delete p;
     return GEMX_OK;
 }
+// what the kernels of the episodic family do not serve (the episodic rollout's list), for the policy rollouts and the lookahead rollout:
+// refused before anything is launched; `what` names the entry point in the messages
+static int episodic_family_refusals(const gemx_config &c, const char *what) {
+    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "%s: fp32 handles only (the fp64 build is a diagnostic; step it)", what);
+    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "%s: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver", what);
+    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "%s: solver kind %d is not built; EulerSolver or RK4Solver", what, c.solver_kind);
+    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "%s: a converter interlocking time (dead time) is not available", what);
+    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "%s: a DeadTimeProcessor (action_delay > 0) is not available", what);
+    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "%s: an RCVoltageSupply is not available", what);
+    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "%s: random initial states are not available (an env restarts inside the launch from the handle's one initial state)", what);
+    return GEMX_OK;
+}
 // what gemx_rollout_policy and gemx_rollout_policy_complete check of the handle, the policy and the call -> the kernel's view of the policy; `what` names
 // the entry point in the messages
 static int policy_prepare(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, const char *what, gemx::PolicyDev &pol) {
@@ -1373,15 +1389,7 @@ static int policy_prepare(gemx_handle *h, const gemx_policy *p, const gemx_polic
     if (((uintptr_t)call->obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "%s: obs_out_dev must be 16-byte aligned", what);
     if ((((uintptr_t)call->length_dev | (uintptr_t)call->obs0_dev | (uintptr_t)call->refs_dev | (uintptr_t)call->noise_dev | (uintptr_t)call->actions_out_dev) & 3u) != 0)
         return fail(GEMX_ERR_ARG, "%s: length_dev, obs0_dev, refs_dev, noise_dev and actions_out_dev must be 4-byte aligned", what);
-    const gemx_config &c = h->cfg;
-    // what the kernel does not serve (the episodic rollout's list): refused here, before anything is launched
-    if (c.dtype == GEMX_F64) return fail(GEMX_ERR_ARG, "%s: fp32 handles only (the fp64 build is a diagnostic; step it)", what);
-    if (c.solver_flags & GEMX_SOLVER_ADAPTIVE) return fail(GEMX_ERR_ARG, "%s: the error-controlled Dormand-Prince solver (GEMX_SOLVER_ADAPTIVE) is not available; EulerSolver or RK4Solver", what);
-    if (c.solver_kind != GEMX_SOLVER_EULER && c.solver_kind != GEMX_SOLVER_RK4) return fail(GEMX_ERR_ARG, "%s: solver kind %d is not built; EulerSolver or RK4Solver", what, c.solver_kind);
-    if (c.interlocking_time > 0.0) return fail(GEMX_ERR_ARG, "%s: a converter interlocking time (dead time) is not available", what);
-    if (c.action_delay > 0) return fail(GEMX_ERR_ARG, "%s: a DeadTimeProcessor (action_delay > 0) is not available", what);
-    if (c.supply_kind != GEMX_SUPPLY_IDEAL) return fail(GEMX_ERR_ARG, "%s: an RCVoltageSupply is not available", what);
-    if (c.init_kind != GEMX_INIT_CONST) return fail(GEMX_ERR_ARG, "%s: random initial states are not available (an env restarts inside the launch from the handle's one initial state)", what);
+    if (const int rc = episodic_family_refusals(h->cfg, what)) return rc;
     if (p->device != h->device) return fail(GEMX_ERR_ARG, "%s: the policy lives on device %d, the handle on device %d", what, p->device, h->device);
     if (call->n_ref < 0 || call->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "%s: n_ref = %d; 0 to %d", what, call->n_ref, GEMX_MAX_REF);
     if (call->n_ref > 0 && !call->refs_dev) return fail(GEMX_ERR_ARG, "%s: refs_dev must not be null with n_ref = %d", what, call->n_ref);
@@ -1465,6 +1473,67 @@ int gemx_rollout_policy_complete(gemx_handle *h, const gemx_policy *p, const gem
     if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
     return GEMX_OK;
 }
+// ---- the lookahead rollout: every switching action one step ahead, the best one taken, inside the launch (include/gemx.h; gemx_lookahead.hpp, gemx_lookahead.hip)
+static bool conv_finite_unit(int conv_unit) {  // ConvTraits<...>::DISCRETE of a handle's converter unit
+    return conv_unit == GEMX_CONV_FINITE_B6 || conv_unit == GEMX_CONV_FINITE_4QC || conv_unit == GEMX_CONV_FINITE_2X4QC || conv_unit == GEMX_CONV_FINITE_B6_4QC ||
+           conv_unit == GEMX_CONV_FINITE_2XB6;
+}
+int gemx_rollout_lookahead_complete(gemx_handle *h, const gemx_policy_call *call, void *refs_out_dev, uint8_t *actions_out_dev, void *scores_out_dev, const void *noise_dev,
+                                    gemx_refgen *refgen, gemx_refprofile *refprofile, void *stream) {
+    static const char *const what = "lookahead rollout";
+    if (!h) return fail(GEMX_ERR_ARG, "null handle");
+    if (!call) return fail(GEMX_ERR_ARG, "%s: the call must not be null", what);
+    if (call->struct_size != (int32_t)sizeof(gemx_policy_call)) return fail(GEMX_ERR_ARG, "gemx_policy_call size mismatch");
+    if (call->n_cols != 0 || call->obs0_dev || call->noise_dev || call->actions_out_dev)
+        return fail(GEMX_ERR_ARG, "%s: the call's actor fields (n_cols, obs0_dev, noise_dev, actions_out_dev) must be zero: there is no actor, and noise and actions are arguments", what);
+    if (!call->length_dev || !call->obs_out_dev || !call->refs_dev || !actions_out_dev)
+        return fail(GEMX_ERR_ARG, "%s: length_dev, obs_out_dev, refs_dev and actions_out_dev must not be null", what);
+    if (call->K < 1) return fail(GEMX_ERR_ARG, "%s: K must be >= 1", what);
+    if (call->max_steps < 1) return fail(GEMX_ERR_ARG, "%s: max_steps must be >= 1 (pass a large limit for none)", what);
+    if (((uintptr_t)call->obs_out_dev & 15u) != 0) return fail(GEMX_ERR_ARG, "%s: obs_out_dev must be 16-byte aligned", what);
+    if ((((uintptr_t)call->length_dev | (uintptr_t)call->refs_dev | (uintptr_t)noise_dev | (uintptr_t)scores_out_dev) & 3u) != 0)
+        return fail(GEMX_ERR_ARG, "%s: length_dev, refs_dev, noise_dev and scores_out_dev must be 4-byte aligned", what);
+    const gemx_config &c = h->cfg;
+    if (const int rc = episodic_family_refusals(c, what)) return rc;
+    if (!conv_finite_unit(h->conv_unit))
+        return fail(GEMX_ERR_ARG, "%s: a continuous converter has no finite action set to enumerate (finite converters only)", what);
+    if (c.obs_layout != GEMX_OBS_AOS) return fail(GEMX_ERR_ARG, "%s: the rows are rewarded by the reward pass behind the launch: it needs GEMX_OBS_AOS", what);
+    if (h->rw_n_ref < 0) return fail(GEMX_ERR_ARG, "%s: no reward function installed (gemx_set_reward): the score of an action is its reward", what);
+    if ((refgen != nullptr) == (refprofile != nullptr)) return fail(GEMX_ERR_ARG, "%s: exactly one of the gemx_refgen and the gemx_refprofile must be given", what);
+    if (call->n_ref < 1 || call->n_ref > GEMX_MAX_REF) return fail(GEMX_ERR_ARG, "%s: n_ref = %d; the generator's 1 to %d columns", what, call->n_ref, GEMX_MAX_REF);
+    if (call->n_ref != h->rw_n_ref) return fail(GEMX_ERR_ARG, "%s: the reward reads %d reference columns, the call n_ref = %d", what, h->rw_n_ref, call->n_ref);
+    if (!refs_out_dev || ((uintptr_t)refs_out_dev & 3u) != 0) return fail(GEMX_ERR_ARG, "%s: refs_out_dev must not be null and must be 4-byte aligned", what);
+    gemx::PcWienerDev wiener;
+    gemx::PcProfileDev profile;
+    int gen_n_ref = 0;
+    if (refgen != nullptr) {
+        if (const int rc = gemx::refgen_policy_view(refgen, what, h->n, h->device, c.env_base, &wiener, &gen_n_ref)) return rc;
+    } else if (const int rc = gemx::refprofile_policy_view(refprofile, what, h->n, h->device, c.env_base, &profile)) return rc;
+    else gen_n_ref = profile.P.n_ref;
+    if (gen_n_ref != call->n_ref) return fail(GEMX_ERR_ARG, "%s: the generator has %d columns, the call n_ref = %d", what, gen_n_ref, call->n_ref);
+    gemx::DeviceGuard guard(h->device);
+    gemx_la_unit_launch_fn fn = nullptr;
+    if (const int rc = load_la_unit(c.system_kind, h->conv_unit, &fn)) return rc;
+    // (all-Wiener: the K * N * n_ref standard normals of these steps into refs_out, in front; the lanes write the references over them)
+    if (refgen != nullptr)
+        if (const int rc = gemx::refgen_policy_normals(refgen, call->K, refs_out_dev, (hipStream_t)stream)) return rc;
+    int linmap_built = 0;
+    gemx::RolloutCall rc_call;  // the rollout call record: K, the rows, the terminated rows, the references shown in front of step 0
+    rc_call.K = call->K;
+    rc_call.obs = call->obs_out_dev;
+    rc_call.done = call->terminated_out_dev;
+    rc_call.refs = call->refs_dev;
+    const gemx::LaCall la = {call->length_dev, call->max_steps, call->n_ref, call->truncated_out_dev, call->ended_out_dev, (float *)refs_out_dev, actions_out_dev,
+                             (float *)scores_out_dev, (const float *)noise_dev, refgen != nullptr ? &wiener : nullptr, refgen != nullptr ? nullptr : &profile, &linmap_built};
+    const int rc = fn(h, &rc_call, &la, (hipStream_t)stream);
+    if (rc != GEMX_OK) return rc;
+    h->steps_total += (unsigned long long)call->K;
+    char key[256];
+    snprintf(key, sizeof(key), "lookahead_rollout_kernel<%d, %d, %d, %d, %s, %d, float>", h->ll.sys, h->ll.conv, h->ll.load, h->ll.solver, h->ll.d ? "true" : "false", h->ll.il);
+    gemx_cov_note(key);
+    if (linmap_built) { snprintf(key, sizeof(key), "linmap_kernel<%d, %d, float>", h->ll.sys, h->ll.solver); gemx_cov_note(key); }
+    return GEMX_OK;
+}
 int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int64_t n, void *stream) {
     if (!h || !x_dev || !y_dev || n < 0) return fail(GEMX_ERR_ARG, "policy tanh probe: invalid argument");
     gemx::DeviceGuard guard(h->device);
@@ -1478,7 +1547,10 @@ int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int
 const char *gemx_last_launch(const gemx_handle *h) {
     if (!h) return "";
     const auto &l = h->ll;
-    if (l.pipe == gemx::EP_LAUNCH_POLICY_COMPLETE)
+    if (l.pipe == gemx::EP_LAUNCH_LOOKAHEAD)
+        snprintf(h->last_launch, sizeof(h->last_launch), "gemx::lookahead_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,gen=%s,f32> grid=%lld x %d threads, K=%d, max_steps=%d, unit libgemx_la%d_%d.so%s",
+                 l.sys, l.conv, l.load, l.solver, l.d, l.il == gemx::PC_GEN_WIENER ? "wiener" : "profile", l.blocks, l.threads, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
+    else if (l.pipe == gemx::EP_LAUNCH_POLICY_COMPLETE)
         snprintf(h->last_launch, sizeof(h->last_launch), "gemx::policy_complete_rollout_kernel<sys=%d,conv=%d,load=%d,solver=%d,tab=%d,gen=%s,f32> grid=%lld x %d threads, lds=%zu B, K=%d, max_steps=%d, unit libgemx_pc%d_%d.so%s",
                  l.sys, l.conv, l.load, l.solver, l.d, l.il == gemx::PC_GEN_WIENER ? "wiener" : "profile", l.blocks, l.threads, l.lds, l.k, l.s, l.sys, l.conv, l.d ? ", per-env parameters" : "");
     else if (l.pipe == gemx::EP_LAUNCH_POLICY)

@@ -1000,6 +1000,103 @@ class CompleteBatchedElectricMotorEnv(BatchedElectricMotorEnv):
         return self._bind_policy("rollout_policy_complete_episodic", False, policy, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
                                  obs0, None, noise, None, episode_statistics, complete=True)()
 
+    # ------------------------------------------------------------------ lookahead rollouts: one-step finite-control-set predictive control in the loop
+    def n_lookahead_actions(self, what="rollout_lookahead_complete_episodic"):
+        """The size of the finite action set the lookahead enumerates (a multi-converter: its flat action index); a continuous
+        converter: NotImplementedError.  Needs no device."""
+        space = self.physical_system.action_space
+        if not (hasattr(space, "n") or hasattr(space, "nvec")):
+            raise NotImplementedError(f"{what} tries every switching action of a finite converter one step ahead; this env's converter is continuous "
+                                      f"(action space {space}): it has no finite action set")
+        return int(getattr(space, "n", 0) or np.prod(space.nvec))
+
+    def _bind_lookahead(self, what, bound, K, outs, noise, scores, stream, episode_statistics):
+        """-> launch() of the lookahead entry point `what`: the refusals of the complete policy rollout and the converter's (no device
+        call), the tensors, then what `_bind_policy` does -- allocate what an eager call did not give, plan.  outs: (state_out, refs_out,
+        reward_out, actions_out, terminated_out, truncated_out); scores: None | True (eager: allocated) | a [K, N, n_actions] tensor."""
+        import ctypes as C
+
+        from .episodes import episodic_refusal
+
+        pipe, ps = self.pipeline, self.physical_system
+        pipe.need_episodic()
+        torch = bps._torch()
+        if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            raise ValueError(f"{what}: K must be an integer >= 1, not {K!r}")
+        if pipe.stage is not None or pipe.flux is not None:
+            raise NotImplementedError(f"{what} is not available with a FluxObserver or any observation-side processor: the controller scores the raw state row")
+        if getattr(ps, "_obs_layout", "aos") != "aos":
+            raise NotImplementedError(f"{what} is not available with obs_layout='soa': the tensors are [K, N, S_out]")
+        self._policy_generator(what)
+        n_actions, N = self.n_lookahead_actions(what), ps.n_envs
+        for name, t in (("noise", noise), ("scores_out", scores)):
+            if torch.is_tensor(t) and t.dtype in (torch.float16, torch.bfloat16):
+                raise NotImplementedError(episodic_refusal(ps, f"a half-precision {name} tensor (fp32 tensors)"))
+        if noise is not None:
+            self._check_tensor(what, noise, "noise", torch.float32, (K, N, n_actions))
+        if scores is True and bound:
+            raise ValueError(f"{what}: scores_out must be a tensor (a bound launch allocates nothing)")
+        if scores is not None and scores is not True and scores is not False:
+            self._check_tensor(what, scores, "scores_out", torch.float32, (K, N, n_actions))
+        _, specs = self._check_call(what, K, None, outs, bound, episode_statistics, complete=True, episodic=True, actions_out=True)
+        state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out = self._allocate(specs, outs)
+        if scores is True:
+            scores = torch.empty((K, N, n_actions), dtype=torch.float32, device=ps._tdev)
+        elif scores is False:
+            scores = None
+        n_ref = len(self.reference_names)
+
+        def physics(raw, terminated, truncated, ended, st):
+            """the pending masked reset, then `gemx_rollout_lookahead_complete` on fixed tensors (the counterpart of `_policy_physics`)"""
+            lib = bps._lib
+            call = lib.GemxPolicyCall()
+            call.struct_size, call.K, call.n_cols, call.n_ref, call.max_steps = C.sizeof(call), K, 0, n_ref, pipe.episode.max_steps
+            call.refs_dev, call.length_dev, call.obs_out_dev = self._refs.data_ptr(), pipe.episode.length.data_ptr(), raw.data_ptr()
+            call.terminated_out_dev, call.truncated_out_dev, call.ended_out_dev = terminated.data_ptr(), truncated.data_ptr(), ended.data_ptr()
+            gen = self.reference_generator
+            profile = isinstance(gen, ProfileReferences)
+            args = (C.byref(call), C.c_void_p(refs_out.data_ptr()), C.c_void_p(actions_out.data_ptr()), C.c_void_p(scores.data_ptr()) if scores is not None else None,
+                    C.c_void_p(noise.data_ptr()) if noise is not None else None, None if profile else gen._handle, gen._handle if profile else None,
+                    C.c_void_p(st.cuda_stream))
+            keep = (call, noise, scores, actions_out, refs_out, raw, terminated, truncated, ended, st, pipe.episode.length, self._refs, gen)
+            return lib.sequence(pipe.bind_before_step(st), lib.counting_call(ps._L.gemx_rollout_lookahead_complete, ps, K, args, keep))
+
+        launch = self._plan(physics, K, (state_out, refs_out, reward_out, terminated_out), truncated_out, stream, episode_statistics, eager=not bound,
+                            extra=(actions_out,), generators=False)
+        if scores is None:
+            return launch
+
+        def launch_with_scores():
+            result = launch()
+            return result[:6] + (scores,) + result[6:]
+
+        return launch_with_scores
+
+    def bind_rollout_lookahead_complete_episodic(self, K, state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out, noise=None, scores_out=None,
+                                                 stream=None, episode_statistics=None):
+        """-> zero-argument launch() of `rollout_lookahead_complete_episodic` on fixed tensors (every output must be given; `scores_out
+        [K, N, n_actions]` float32 is optional); `launch()` returns `(state_out, refs_out, reward_out, actions_out, terminated_out,
+        truncated_out[, scores_out][, stats])`.  One stream, nothing on the host: capturable with `torch.cuda.graph` (make one launch
+        outside the capture first: it loads the kernel unit and builds the one-step map)."""
+        return self._bind_lookahead("bind_rollout_lookahead_complete_episodic", True, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
+                                    noise, scores_out, stream, episode_statistics)
+
+    def rollout_lookahead_complete_episodic(self, K, noise=None, return_scores=False, state_out=None, refs_out=None, reward_out=None, actions_out=None,
+                                            terminated_out=None, truncated_out=None, scores_out=None, episode_statistics=None):
+        """K calls of `step()` under one-step finite-control-set model predictive control, fused (csrc/gemx_lookahead.hip): in every
+        control step the launch tries each of the finite converter's actions once from the state the step starts at, scores the outcome
+        with the env's own reward against the references shown before the step, and takes the lowest index among the maxima of
+        `score + noise[k]` -- the policy rollouts' rule; a `-inf` noise entry masks an action, Gumbel noise samples from softmax(score).
+        -> (state [K, N, S_out], refs [K, N, n_ref], reward [K, N], actions [K, N] uint8, terminated [K, N], truncated [K, N][, scores
+        [K, N, n_actions]][, stats]); `scores` (return_scores=True or `scores_out`) are the scores before the noise, and
+        `reward[k, n] == scores[k, n, actions[k, n]]` bit for bit.  A multi-converter's action is its flat index.  Everything else is
+        `rollout_policy_complete_episodic`'s: bit for bit `rollout_complete_episodic(actions)` of a twin env, the env afterwards stands
+        where that leaves it, the same generators are served and the same configurations refused; a continuous converter has no finite
+        action set: NotImplementedError.  An env without a time limit: ValueError."""
+        scores = scores_out if scores_out is not None else bool(return_scores)
+        return self._bind_lookahead("rollout_lookahead_complete_episodic", False, K, (state_out, refs_out, reward_out, actions_out, terminated_out, truncated_out),
+                                    noise, scores, None, episode_statistics)()
+
     def evaluate_policy_complete_rollout(self, policy, rollout_outputs, head="none", mode="seen", obs0=None, shown0=None, **kw):
         """`policy.evaluate_rollout` on what `rollout_policy_complete_episodic` returned, `(state, refs, reward, actions, terminated,
         truncated[, stats])`, in the complete form: `refs` from the tuple, `n_ref` from the env, `ended`, the reset observation and the

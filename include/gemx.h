@@ -858,6 +858,30 @@ int gemx_policy_tanh_probe(gemx_handle *h, const float *x_dev, float *y_dev, int
 int gemx_rollout_policy_complete(gemx_handle *h, const gemx_policy *p, const gemx_policy_call *call, void *refs_out_dev, gemx_refgen *refgen,
                                  gemx_refprofile *refprofile, void *stream);
 
+/* LOOKAHEAD ROLLOUT OF THE COMPLETE ENV: one-step finite-control-set predictive control inside the fused launch (one new entry point, no
+ * new struct, ABI number unchanged).  In control step k every one of the finite converter's n_actions switching actions (the flat index of
+ * a multi-converter) is stepped ONCE from the state the step starts at -- the episodic rollout's control step -- and scored with the
+ * handle's reward (gemx_set_reward) against the references shown in front of step k:
+ *     score[a] = reward(row_a, refs_prev, done_a);   action = the lowest index among the maxima of score[a] + noise[k][a]
+ * (best = 0; for a = 1 .. n_actions - 1: if (s[a] > s[best]) best = a -- the policy rollout's rule; a -inf noise entry masks an action).
+ * The chosen trial is committed as it was computed, then the step proceeds as gemx_rollout_policy_complete's: the episode rule, the row
+ * store, the generators (restart where the episode ended, advance, refs_out_dev[k]).  Fed to gemx_rollout_episodic, actions_out_dev gives
+ * the same rows bit for bit; gemx_reward_rows over them gives reward[k] == score[actions[k]] bit for bit.
+ * The call is a gemx_policy_call read as gemx_rollout_policy_complete reads it, without an actor: K, n_ref, max_steps, refs_dev [N][n_ref]
+ * (the references shown in front of step 0), length_dev, obs_out_dev, terminated / truncated / ended are read; n_cols must be 0 and
+ * obs0_dev, noise_dev, actions_out_dev NULL -- the outputs and the noise of this entry point are arguments:
+ *   refs_out_dev     [K][N][n_ref] R
+ *   actions_out_dev  [K][N] uint8
+ *   scores_out_dev   [K][N][n_actions] R, the scores in front of `+ noise`; may be NULL
+ *   noise_dev        [K][N][n_actions] R; may be NULL
+ *   refgen | refprofile   exactly one, as gemx_rollout_policy_complete takes them
+ * The kernels live in libgemx_la<S>_<C>.so beside the library (finite converters only; loaded by the first call).  Asynchronous on
+ * `stream`, allocates nothing, can be captured.  GEMX_ERR_ARG, naming the lookahead rollout, before anything is launched: what
+ * gemx_rollout_policy_complete refuses of the handle, the call and the generator; a continuous converter (no finite action set); a handle
+ * without a reward or with GEMX_OBS_SOA; n_ref other than the reward's; actor fields of the call that are set. */
+int gemx_rollout_lookahead_complete(gemx_handle *h, const gemx_policy_call *call, void *refs_out_dev, uint8_t *actions_out_dev, void *scores_out_dev,
+                                    const void *noise_dev, gemx_refgen *refgen, gemx_refprofile *refprofile, void *stream);
+
 /* POLICY EVALUATION OVER STORED ROWS: an MLP of gemx_policy_create on every row of a stored policy rollout, with the rollout kernels' own
  * arithmetic, as ONE launch (new struct and entry point only, ABI number unchanged).  No physics, no env handle: the pass reads the policy's
  * device blob (no second copy of the weights) and the tensors a rollout handed out.  Row (k, env), k < K, one lane each:

@@ -5,7 +5,9 @@ compiles the 19 policy units (csrc/gemx_policy.hip: the kernel without a generat
 --complete: the same for the kernel's instantiations in the 19 complete policy units (csrc/gemx_policy_complete.hip; one more column, the
 generator kind: 0 all-Wiener, 1 profile) -- the table of profiles/policy_complete_rollout.md.
 --eval: the four policy_eval_kernel instantiations of csrc/gemx_policy_eval.hip (one per head), compiled once as libgemx.so's object is --
-the table of profiles/policy_eval.md."""
+the table of profiles/policy_eval.md.
+--lookahead: the lookahead_rollout_kernel instantiations of the 8 lookahead units (csrc/gemx_lookahead.hip, finite converters only; the
+generator column as with --complete) -- the table of profiles/lookahead_rollout.md."""
 import concurrent.futures as cf
 import os
 import re
@@ -18,10 +20,12 @@ from gym_electric_motor_amd import build  # noqa: E402
 
 COMPLETE = "--complete" in sys.argv[1:]
 EVAL = "--eval" in sys.argv[1:]
+LOOKAHEAD = "--lookahead" in sys.argv[1:]
 EVAL_NAME = re.compile(r"policy_eval_kernelILi(\d+)E")
 HEADS = ("none", "value", "categorical", "gaussian")
-SOURCE = "gemx_policy_complete.hip" if COMPLETE else "gemx_policy.hip"
-NAME = re.compile(r"policy_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E")  # SYS, CONV, LOAD, SOLVER, TAB, GEN (2 in the policy units: none)
+SOURCE = "gemx_lookahead.hip" if LOOKAHEAD else "gemx_policy_complete.hip" if COMPLETE else "gemx_policy.hip"
+COMPLETE = COMPLETE or LOOKAHEAD  # (the generator column)
+NAME = re.compile(r"(?:policy|lookahead)_rollout_kernelILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)ELb([01])ELi(\d+)E")  # SYS, CONV, LOAD, SOLVER, TAB, GEN (2 in the policy units: none)
 FIELD = re.compile(r"remark:\s+(VGPRs|AGPRs|ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)")
 
 
@@ -64,7 +68,7 @@ def main():
     if EVAL:
         return eval_main()
     with tempfile.TemporaryDirectory() as tmp, cf.ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 4)) as ex:
-        rows = [r for unit_rows in ex.map(lambda sc: unit(sc, tmp), build.UNITS) for r in unit_rows]
+        rows = [r for unit_rows in ex.map(lambda sc: unit(sc, tmp), build.LA_UNITS if LOOKAHEAD else build.UNITS) for r in unit_rows]
     gen = " generator |" if COMPLETE else ""
     print(f"| sys/conv | load | solver | table |{gen} VGPRs | AGPRs | SGPR spills | scratch B/lane | static LDS B | waves/SIMD |\n|---|---|---|---|---|---|---|---|---|---|{'---|' if COMPLETE else ''}")
     for r in sorted(rows, key=lambda r: r["key"]):
